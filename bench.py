@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the Kapre time-frequency hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic waveforms already resident in HBM.
 
@@ -24,6 +24,11 @@ that) with the contract's keys + `roofline`, `roofline_compute`, `cpu_baseline`,
 one-row-per-workload `also` summary.  Everything longer -- per-workload detail, the CPU sweep, the notes on how to read
 the fractions -- goes to gpurun_out/bench_full.json and to earlier stdout lines (one small JSON object per `also`
 workload).  (Round 3 printed all of it on one 22 KB line; the driver keeps 8 KB of stdout and could not parse it.)
+
+--dump-outputs DIR: after the timed steps, what the headline workload's last timed step returned to its caller is written as
+DIR/<workload>.npy (DIR/<workload>_rank<r>.npy for N > 1), float32 or float64, complex as a trailing axis of 2.  The inputs are
+seeded per workload, so two builds given the same arguments can be compared output for output.  Above 64 MiB in all, each
+array is cut to a fixed, seeded sample of its elements (the same flat positions on every run).
 """
 import argparse
 import json
@@ -38,6 +43,7 @@ sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 achievable
 MFMA_F32_PEAK_TF = 157.3       # v_mfma_f32_16x16x4_f32 dense peak = the fp32 VALU FMA peak of 256 CUs
+DUMP_CAP_BYTES = 64 * 2 ** 20  # --dump-outputs: at most this many bytes of .npy payload per run
 
 # kind: mel = fused kpr_mel_f32 ; stft = kpr_stft_f32 (complex out) ; istft = kpr_istft_f32
 WORKLOADS = {
@@ -178,7 +184,8 @@ def make_input(w, rank, device, batch):
 
 
 def timed_steps(model, x, steps, warmup, world):
-    """W untimed + exactly K timed steps, bracketed by barrier + synchronize; max over ranks."""
+    """W untimed + exactly K timed steps, bracketed by barrier + synchronize; max over ranks.
+    Returns (seconds, device ms, what the last timed step returned)."""
     import torch
     import torch.distributed as dist
 
@@ -205,8 +212,39 @@ def timed_steps(model, x, steps, warmup, world):
         t = torch.tensor([dt, dev_ms], dtype=torch.float64, device=x.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dev_ms = float(t[0]), float(t[1])
-    del y
-    return dt, dev_ms
+    return dt, dev_ms, y
+
+
+def host_arrays(y):
+    """A step's return value (a tensor, or a tuple / list of them) as host float32 / float64 arrays; complex tensors
+    become real ones with a trailing axis of 2 (real, imaginary)."""
+    import torch
+
+    out = []
+    for t in (y if isinstance(y, (tuple, list)) else [y]):
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        out.append(t.cpu().numpy())
+    return out
+
+
+def dump_outputs(arrays, out_dir, cap=DUMP_CAP_BYTES, seed=0):
+    """Write {name: array} as out_dir/<name>.npy.  If the arrays hold more than `cap` bytes in all, each is cut to the
+    same fraction of its elements: a sample of flat positions drawn from a generator seeded with `seed`, in ascending
+    order, so that every run with the same shapes writes the same positions.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in sorted(arrays.items()):
+        if total > cap:
+            n = max(1, a.size * cap // total)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def kernel_time_us(model, x, launches=100, settle_s=0.0, rotate=None):
@@ -462,8 +500,9 @@ def rooflines(name, w, batch, step_us, kernel):
     return out, comp
 
 
-def measure(name, w, rank, world, device, steps, warmup, with_kernel=True, settle_s=1.0, rotating=True):
-    """One workload on this rank's shard; returns the result dict on every rank (values are whole-job)."""
+def measure(name, w, rank, world, device, steps, warmup, with_kernel=True, settle_s=1.0, rotating=True, keep_output=False):
+    """One workload on this rank's shard; returns the result dict on every rank (values are whole-job).
+    keep_output: the dict also holds "last_output", host_arrays() of what the last timed step returned."""
     import torch
     from kapre_amd import _ffi
     from kapre_amd import dist as kdist
@@ -488,7 +527,9 @@ def measure(name, w, rank, world, device, steps, warmup, with_kernel=True, settl
         xs = [x] + [make_input(w, rank + 17 * (i + 1), device, batch) for i in range(n_rot - 1)]
         k_rot, _ = kernel_time_us(model, x, settle_s=min(settle_s, 0.5), rotate=xs)
         del xs
-    dt, dev_ms = timed_steps(model, x, steps, warmup, world)
+    dt, dev_ms, y = timed_steps(model, x, steps, warmup, world)
+    last_output = host_arrays(y) if keep_output else None
+    del y
     frames_rank = batch * w["ch"] * frames_of(w)
     res = {"workload": name, "value": frames_rank * world * steps / dt, "unit": "mel-frames/s" if w["kind"] == "mel" else "frames/s",
            "audio_sec_per_sec": batch * w["ch"] * w["t"] / w["sr"] * world * steps / dt,
@@ -518,6 +559,8 @@ def measure(name, w, rank, world, device, steps, warmup, with_kernel=True, settl
         res["roofline"] = hbm
         if comp:
             res["roofline_compute"] = comp
+    if keep_output:
+        res["last_output"] = last_output
     del x, model
     torch.cuda.empty_cache()
     return res
@@ -640,7 +683,11 @@ def main():
     ap.add_argument("--no-also", action="store_true")
     ap.add_argument("--sustain", type=float, default=10.0, help="seconds of continuous headline replay at the end (0 = off)")
     ap.add_argument("--settle", type=float, default=1.5, help="seconds of continuous replay before the headline is timed (clock settling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from kapre_amd import dist as kdist
@@ -656,7 +703,14 @@ def main():
     torch.cuda.set_device(device)
 
     w = WORKLOADS[args.workload]
-    head = measure(args.workload, w, rank, world, device, args.steps, args.warmup, settle_s=args.settle)
+    head = measure(args.workload, w, rank, world, device, args.steps, args.warmup, settle_s=args.settle,
+                   keep_output=args.dump_outputs is not None)
+    dumped = None
+    if args.dump_outputs is not None:
+        outs = head.pop("last_output")
+        stem = args.workload if world == 1 else "%s_rank%d" % (args.workload, rank)
+        arrays = {stem if len(outs) == 1 else "%s_%d" % (stem, i): a for i, a in enumerate(outs)}
+        dumped = dump_outputs(arrays, args.dump_outputs, cap=DUMP_CAP_BYTES // world)
     result = {
         "metric": "mel-frames/sec", "value": head["value"], "unit": head["unit"],
         "audio_sec_per_sec": head["audio_sec_per_sec"],
@@ -671,6 +725,8 @@ def main():
                    "parallelism": "batch-shard x%d" % world,
                    "constants_broadcast_bytes": head["constants_broadcast_bytes"]},
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if world > 1:
         # K x ~40 us sits between two barriers: their skew (tens of us) would read as scaling loss, so the per-rank HIP-event
         # time (max over ranks) is the figure to compare across N; `value` keeps the contract's wall-clock definition

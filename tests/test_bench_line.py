@@ -87,3 +87,31 @@ def test_cpu_baseline_protocol_on_a_toy_workload():
     import cpu_graph
     order, n_phys = cpu_graph.physical_cpus()
     assert len(set(order)) == len(order) >= n_phys >= 1
+
+
+def test_dump_outputs_types_cap_and_fixed_sample(tmp_path):
+    """--dump-outputs: host_arrays turns a step's return value into float32 / float64 arrays (complex -> trailing axis of 2);
+    dump_outputs writes them whole under the cap and, above it, the same seeded sample of positions on every call."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    c = torch.complex(torch.arange(6.0).reshape(2, 3), -torch.arange(6.0).reshape(2, 3))
+    (a,) = bench.host_arrays(c)
+    assert a.dtype == np.float32 and a.shape == (2, 3, 2) and a[1, 2, 0] == 5.0 and a[1, 2, 1] == -5.0
+    a16, a64 = bench.host_arrays((torch.ones(4, dtype=torch.float16), torch.ones(4, dtype=torch.float64)))
+    assert a16.dtype == np.float32 and a64.dtype == np.float64
+
+    x = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    assert bench.dump_outputs({"y": x}, str(tmp_path / "whole")) == {"y": [10, 100]}
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "y.npy"), x)
+
+    arrays = {"y": x, "z": np.arange(500, dtype=np.float64)}          # 4000 + 4000 bytes
+    first = bench.dump_outputs(arrays, str(tmp_path / "s1"), cap=2000)
+    second = bench.dump_outputs(arrays, str(tmp_path / "s2"), cap=2000)
+    assert first == second == {"y": [250], "z": [125]}
+    for name in ("y", "z"):
+        s1, s2 = np.load(tmp_path / "s1" / (name + ".npy")), np.load(tmp_path / "s2" / (name + ".npy"))
+        np.testing.assert_array_equal(s1, s2)
+        assert np.all(np.diff(s1) > 0)                                  # ascending flat positions, no repeats
+    assert sum((tmp_path / "s1" / (n + ".npy")).stat().st_size - 128 for n in ("y", "z")) <= 2000

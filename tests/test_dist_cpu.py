@@ -35,8 +35,10 @@ def _free_port():
 
 
 def _worker(rank, world, port, tmpdir):
+    # KAPRE_AMD_SHARE_DEVICE: where a GPU is visible, init_from_env selects a device; every rank takes device 0, so that
+    # the test of the host logic runs on a box with fewer GPUs than ranks as well
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), KAPRE_AMD_SHARE_DEVICE="1")
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "oracle"))
     import torch
@@ -93,7 +95,12 @@ def test_two_rank_gloo_shard_broadcast_gather(tmp_path):
     procs = [ctx.Process(target=_worker, args=(r, 2, port, str(tmp_path))) for r in range(2)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    try:
+        for p in procs:
+            p.join(120)
+            assert p.exitcode == 0
+    finally:                           # a rank left waiting for a failed peer must not keep pytest from exiting
+        for p in procs:
+            if p.is_alive():
+                p.kill()
     assert sorted(os.listdir(tmp_path)) == ["ok0", "ok1"]
