@@ -430,9 +430,8 @@ static int run_gemm(const float* a, const float* bm, const GemmArgs& ga, float* 
     return launch_check("k_gemm");
 }
 
-// STFT of every frame into `out` (complex64), through the DFT-as-GEMM path
-static int stft_gemm(const float* x, const kpr_stft_geom* s, const Geom& g, const float* window,
-                     float* out_cplx, bool out_contig, hipStream_t st) {
+// STFT of every frame into `out` (complex64, in g's output layout), through the DFT-as-GEMM path
+static int stft_gemm(const float* x, const Geom& g, const float* window, float* out_cplx, hipStream_t st) {
     const float* dft = nullptr;
     if (int e = get_dft_fwd(g.n_fft, &dft)) return e;
     GemmArgs ga{};
@@ -440,13 +439,12 @@ static int stft_gemm(const float* x, const kpr_stft_geom* s, const Geom& g, cons
     if (g.in_cl) { ga.in.s2 = g.T * g.C; ga.in.s1 = 1; ga.t_es = g.C; }
     else { ga.in.s2 = (long long)g.C * g.T; ga.in.s1 = g.T; ga.t_es = 1; }
     ga.in.s0 = 0; ga.in.es = 0;
-    ga.out = out_contig ? frames_contig_map(g, g.K) : frames_out_map(g, g.K);
+    ga.out = frames_out_map(g, g.K);
     ga.Kdim = std::min(g.win, g.n_fft);
     ga.N = 2 * g.K;
     ga.ldb = 2 * g.K;
     ga.T = g.T; ga.hop = g.hop; ga.pad_left = g.pad_left;
     ga.window = window; ga.win = g.win;
-    (void)s;
     return run_gemm<A_FRAME, E_CPLX>(x, dft, ga, out_cplx, st);
 }
 
@@ -467,14 +465,43 @@ static int allow_big_lds(LdsOptIn& st, const void* fn) {
 }
 static long long* g_debug_stamps = nullptr;   // development aid: kpr_debug_stamps()
 
-template <int NC, int NW>
-static int launch_istft_fused(const float2* spec, const kpr_stft_geom* s, long long F,
-                              const float* synth, const float2* tw, float* out, hipStream_t st,
-                              bool* launched) {
-    constexpr int L = NC / kPts, G = 64 / L;
-    *launched = false;
+// n -> f(std::integral_constant<int, n>) for the power-of-two template sizes n = 128, 256, 512, 1024 (anything else: 1024) -- the
+// half transform size NC = n_fft / 2 of the power-of-two kernels, the Bluestein length M, the bin count of k_fb_pw
+template <class Fn>
+static int with_pow2(int n, Fn&& f) {
+    switch (n) {
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+        default:  return f(std::integral_constant<int, 1024>{});
+    }
+}
+// the branch of a with_pow2 / with_mr body that the route never selects
+static int no_instance(const char* what) { return fail(KPR_E_UNSUPPORTED, "no %s instance for this call", what); }
+
+// ---- dispatch routes: which kernel (family, template instance, launch plan) a call runs, from host-side facts only --------
+// The route functions (stft_route, mel_route, istft_route, fb_route next to their entry points) never launch and never
+// synchronise; the launchers below take the route's plan and always launch.
+enum { FAM_POW2, FAM_MR, FAM_BS, FAM_BIG, FAM_GEN, FAM_GEMM,            // FFT families (fft_family)
+       IST_PW, IST_WS, IST_FUSED, IST_WS_MR };                          // one-launch inverse kernels (istft_route)
+enum { STFT_K, STFT_K3, STFT_K3_CL };                                   // power-of-two STFT kernels (stft_pow2_kernel)
+
+struct IstftRoute {
+    int fam;                   // IST_*, else the irFFT family (FAM_*) of the two-kernel path
+    int S, il;                 // IST_PW: register slots per hop, interleaved instance
+    int rj;                    // IST_WS / IST_WS_MR: rows read per sample group
+    IstftPwPlan pw;
+    IstftWsPlan ws;
+    IstftPlan fused;
+    size_t lds;
+    unsigned grid;
+    long long nitems;          // IST_WS / IST_WS_MR: items, IST_FUSED: blocks
+};
+
+static bool istft_fused_plan(const kpr_stft_geom* s, long long F, const float* out, int cus, IstftRoute* r) {
+    const int NC = s->n_fft / 2, L = NC / kPts, G = 64 / L, NW = NC == 1024 ? 8 : 4;
     const int win = s->win_length, hop = s->hop_length;
-    if (hop > win || F < 1) return 0;                       // gaps between frames: two-kernel path
+    if (hop > win || F < 1) return false;                   // gaps between frames: two-kernel path
     const int R = (win + hop - 1) / hop;
     const int RS = ((std::max(win, NC) + 3) & ~3) + 4;
     const int spare = (G > 1) ? NW * (G - 1) : 0;           // scratch rows for idle frame slots
@@ -483,8 +510,8 @@ static int launch_istft_fused(const float2* spec, const kpr_stft_geom* s, long l
     // (an 8-wave workgroup at ~190 VGPRs fills the CU's register file on its own)
     int NR = (NW == 8) ? 0 : std::min(16, (int)(80 * 1024 / (sizeof(float) * RS)) - spare);
     if (NR < R + 3) NR = std::min(16, (int)(160 * 1024 / (sizeof(float) * RS)) - spare);
-    if (NR < R + 1) return 0;
-    IstftPlan pl;
+    if (NR < R + 1) return false;
+    IstftPlan& pl = r->fused;
     pl.n_sig = (long long)s->batch * s->channels;
     pl.t_out = (F - 1) * (long long)hop + win;
     pl.F = (int)F; pl.C = s->channels; pl.win = win; pl.hop = hop;
@@ -496,20 +523,24 @@ static int launch_istft_fused(const float2* spec, const kpr_stft_geom* s, long l
     pl.vec4 = hop % 4 == 0 && win % 4 == 0 && !(pl.wave_cl && s->channels > 1) &&
               (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     const size_t lds = sizeof(float) * (size_t)(NR + spare) * pl.RS;
-    if (lds > 160 * 1024) return 0;
-    static LdsOptIn lds_opt_in;
-    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_istft_fused<NC, NW>))) return e;
-    const long long nblocks = pl.n_sig * pl.chunks;
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
+    if (lds > 160 * 1024) return false;
+    r->fam = IST_FUSED;
+    r->lds = lds;
+    r->nitems = pl.n_sig * pl.chunks;
     const int per_cu = std::max(1, (int)(160 * 1024 / lds));
-    const unsigned grid = (unsigned)std::min<long long>(nblocks, (long long)std::min(per_cu, 2) * cus);
-    hipLaunchKernelGGL((k_istft_fused<NC, NW>), dim3(grid), dim3(NW * 64), lds, st, spec, pl, synth,
-                       tw, out, nblocks);
-    *launched = true;
-    return launch_check("k_istft_fused", NC);
+    r->grid = (unsigned)std::min<long long>(r->nitems, (long long)std::min(per_cu, 2) * cus);
+    return true;
 }
 
+template <int NC, int NW>
+static int launch_istft_fused(const float2* spec, const IstftRoute& r, const float* synth, const float2* tw, float* out,
+                              hipStream_t st) {
+    static LdsOptIn lds_opt_in;
+    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_istft_fused<NC, NW>))) return e;
+    hipLaunchKernelGGL((k_istft_fused<NC, NW>), dim3(r.grid), dim3(NW * 64), r.lds, st, spec, r.fused, synth,
+                       tw, out, r.nitems);
+    return launch_check("k_istft_fused", NC);
+}
 
 static int device_cus(int* cus) {
     int dev = 0;
@@ -605,24 +636,23 @@ static bool istft_ws_plan(const kpr_stft_geom* s, long long F, const float* out,
     return true;
 }
 
+// k_istft_ws at a power-of-two n_fft
+static bool istft_ring_plan(const kpr_stft_geom* s, long long F, const float* out, int cus, IstftRoute* r) {
+    const int NC = s->n_fft / 2, G = 64 / (NC / kPts);
+    int vec;
+    if (!istft_ws_plan(s, F, out, NC, G, kIwProd * (G - 1), 0, cus, 4, &r->ws, &r->lds, &r->rj, &vec, &r->nitems)) return false;
+    r->fam = IST_WS;
+    r->grid = (unsigned)std::min<long long>(r->nitems, cus);
+    return true;
+}
+
 template <int NC>
-static int launch_istft_ws(const float2* spec, const kpr_stft_geom* s, long long F, const float* synth,
-                           const float2* tw, float* out, hipStream_t st, bool* launched) {
-    constexpr int L = NC / kPts, G = 64 / L;
-    *launched = false;
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
-    IstftWsPlan pl;
-    size_t lds;
-    int RJ, VEC;
-    long long nitems;
-    if (!istft_ws_plan(s, F, out, NC, G, kIwProd * (G - 1), 0, cus, 4, &pl, &lds, &RJ, &VEC, &nitems)) return 0;
-    const unsigned grid = (unsigned)std::min<long long>(nitems, cus);
-    *launched = true;
-    switch (RJ) {
-        case 2:  return launch_istft_ws_inst<NC, 2>(spec, pl, lds, grid, synth, tw, out, (int)nitems, st);
-        case 4:  return launch_istft_ws_inst<NC, 4>(spec, pl, lds, grid, synth, tw, out, (int)nitems, st);
-        default: return launch_istft_ws_inst<NC, 8>(spec, pl, lds, grid, synth, tw, out, (int)nitems, st);
+static int launch_istft_ws(const float2* spec, const IstftRoute& r, const float* synth, const float2* tw, float* out,
+                           hipStream_t st) {
+    switch (r.rj) {
+        case 2:  return launch_istft_ws_inst<NC, 2>(spec, r.ws, r.lds, r.grid, synth, tw, out, (int)r.nitems, st);
+        case 4:  return launch_istft_ws_inst<NC, 4>(spec, r.ws, r.lds, r.grid, synth, tw, out, (int)r.nitems, st);
+        default: return launch_istft_ws_inst<NC, 8>(spec, r.ws, r.lds, r.grid, synth, tw, out, (int)r.nitems, st);
     }
 }
 
@@ -645,35 +675,30 @@ static int launch_istft_pw_inst(const float2* spec, const IstftPwPlan& pl_in, un
     hipLaunchKernelGGL((k_istft_pw<NC, S, W, IL>), dim3(grid), dim3(W * 64), lds, st, spec, pl, synth, tw, out);
     return launch_check(IL ? "k_istft_pw_il" : "k_istft_pw", NC, S == 2 ? "s2" : S == 4 ? "s4" : "s8");
 }
-template <int NC>
-static int launch_istft_pw(const float2* spec, const kpr_stft_geom* s, long long F, const float* synth,
-                           const float2* tw, float* out, hipStream_t st, bool* launched) {
-    constexpr int L = NC / kPts, G = 64 / L, NSTR = 16 * G;
-    *launched = false;
+static bool istft_pw_plan(const kpr_stft_geom* s, long long F, int cus, IstftRoute* r) {
+    const int NC = s->n_fft / 2, L = NC / kPts, G = 64 / L, NSTR = 16 * G;
     const int win = s->win_length, hop = s->hop_length;
     // hop = S x (2 L samples), S = 2 / 4 / 8: the next frame's samples sit S register slots further down in the same lane
-    if (hop % (2 * L) || win > 2 * NC || hop > win || F < 1) return 0;
+    if (hop % (2 * L) || win > 2 * NC || hop > win || F < 1) return false;
     const int S = hop / (2 * L);
-    if (S != 2 && S != 4 && S != 8) return 0;
+    if (S != 2 && S != 4 && S != 8) return false;
     // contiguous waveform and contiguous spectrogram rows (channels_first, or one channel): a stream = a frame run of one
     // signal.  An interleaved side (channels_last, C > 1; round 4): the IL instances, streams = (frame run, channel) with
     // the channel fastest, an item = a segment of one batch item -- C a power of two that divides the streams of a workgroup,
     // hop = n_fft / 4 or / 2 (the instances that are built)
     const bool il = (s->in_layout == KPR_CHANNELS_LAST && s->channels > 1) || (s->out_layout == KPR_CHANNELS_LAST && s->channels > 1);
     const int C = s->channels;
-    if (il && ((C & (C - 1)) != 0 || C > NSTR || S == 2)) return 0;
+    if (il && ((C & (C - 1)) != 0 || C > NSTR || S == 2)) return false;
     const int runs = il ? NSTR / C : NSTR;                                       // frame runs per item
     const long long n_sig = il ? (long long)s->batch : (long long)s->batch * s->channels;
     const long long t_out = (F - 1) * (long long)hop + win;
-    if (n_sig * 4096 >= (1LL << 31) || t_out + 2LL * NC >= (1LL << 31) || F >= (1LL << 30)) return 0;
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
+    if (n_sig * 4096 >= (1LL << 31) || t_out + 2LL * NC >= (1LL << 31) || F >= (1LL << 30)) return false;
     // segments per signal: every stream of a segment needs R - 1 frames of its own (run boundaries are two-party sums);
     // cost of a schedule = rounds of `cus` workgroups x (frames per stream + a fixed start)
     const int R = kPts / S;
     const long long need = (long long)runs * (R - 1);
     const int segs_max = (int)std::min<long long>(4096, F / need);
-    if (segs_max < 1) return 0;
+    if (segs_max < 1) return false;
     int segs = 1;
     double best = 1e300;
     for (int sg = 1; sg <= segs_max; ++sg) {
@@ -683,8 +708,8 @@ static int launch_istft_pw(const float2* spec, const kpr_stft_geom* s, long long
         if (n_sig * sg > 8LL * cus) break;
     }
     // fewer items than three quarters of the CUs: the ring kernel (32 x 434 frames at n_fft 1024 = 128 items: 30.8 vs 31.5 us)
-    if (opt(OPT_ISTFT_PATH) == 0 && n_sig * segs * 4 < 3LL * cus) return 0;
-    IstftPwPlan pl;
+    if (opt(OPT_ISTFT_PATH) == 0 && n_sig * segs * 4 < 3LL * cus) return false;
+    IstftPwPlan& pl = r->pw;
     pl.t_out = t_out; pl.F = (int)F; pl.win = win; pl.hop = hop; pl.segs = segs; pl.nitems = (int)(n_sig * segs);
     pl.seg_q = (int)(F / segs); pl.seg_r = (int)(F % segs);
     pl.n_stash = 0;
@@ -692,55 +717,64 @@ static int launch_istft_pw(const float2* spec, const kpr_stft_geom* s, long long
     // (kpr_stft_geom: in_layout = the WAVEFORM's layout, out_layout = the SPECTROGRAM's -- for the inverse as well)
     pl.in_cl = (il && s->out_layout == KPR_CHANNELS_LAST) ? 1 : 0;              // the kernel's input: the spectrogram
     pl.out_cl = (il && s->in_layout == KPR_CHANNELS_LAST) ? 1 : 0;              // its output: the waveform
-    const unsigned grid = (unsigned)std::min<long long>(pl.nitems, cus);
-    *launched = true;
-    if (il) return S == 4 ? launch_istft_pw_inst<NC, 4, true>(spec, pl, grid, synth, tw, out, st)
-                          : launch_istft_pw_inst<NC, 8, true>(spec, pl, grid, synth, tw, out, st);
-    switch (S) {
-        case 2:  return launch_istft_pw_inst<NC, 2, false>(spec, pl, grid, synth, tw, out, st);
-        case 4:  return launch_istft_pw_inst<NC, 4, false>(spec, pl, grid, synth, tw, out, st);
-        default: return launch_istft_pw_inst<NC, 8, false>(spec, pl, grid, synth, tw, out, st);
+    r->fam = IST_PW;
+    r->S = S;
+    r->il = il;
+    r->grid = (unsigned)std::min<long long>(pl.nitems, cus);
+    return true;
+}
+
+template <int NC>
+static int launch_istft_pw(const float2* spec, const IstftRoute& r, const float* synth, const float2* tw, float* out,
+                           hipStream_t st) {
+    if (r.il) return r.S == 4 ? launch_istft_pw_inst<NC, 4, true>(spec, r.pw, r.grid, synth, tw, out, st)
+                              : launch_istft_pw_inst<NC, 8, true>(spec, r.pw, r.grid, synth, tw, out, st);
+    switch (r.S) {
+        case 2:  return launch_istft_pw_inst<NC, 2, false>(spec, r.pw, r.grid, synth, tw, out, st);
+        case 4:  return launch_istft_pw_inst<NC, 4, false>(spec, r.pw, r.grid, synth, tw, out, st);
+        default: return launch_istft_pw_inst<NC, 8, false>(spec, r.pw, r.grid, synth, tw, out, st);
     }
 }
 
-template <int NC, int MODE, bool OUT_CL>
-static int launch_stft_inst(const float* x, const Geom& g, const float* window, const float2* tw,
-                            void* out, hipStream_t st) {
-    constexpr int L = NC / kPts, G = 64 / L;
+// k_stft3_cl / k_stft3 / k_stft at a power-of-two n_fft (g as launched: frame numbering g.cfast, output layout g.out_cl)
+static int stft_pow2_kernel(const Geom& g, int mode, int cus) {
+    const int NC = g.n_fft / 2, G = 64 / (NC / kPts);
     const long long ngroups = (g.total_frames + G - 1) / G;          // wave-loads of G frames
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
-    const size_t lds = stft_lds_bytes(NC);
     // channels_last output with several channels (round 4): k_stft3 writes the G channel-frames of a wave as neighbours
     // (n_fft 1024, complex output, even channel count); everything else of that layout stays on k_stft
-    const bool cl_ok = OUT_CL && MODE != KPR_OUT_PHASE && NC >= 512 && g.cfast && (g.C % G) == 0;
-    if constexpr (MODE != KPR_OUT_PHASE && NC >= 512) if (!OUT_CL || cl_ok) {      // (the n_fft 256 / 512 instances spill at 128 VGPRs)
-        // k_stft3: one sixteen-wave workgroup per CU drawing frame groups from an LDS counter (stft_variant 0 = automatic, from
-        // 8 groups per CU up -- tools/sweep_dispatch.py stft: 13.5 groups per CU 12.2 vs 14.0 us, 2.6 per CU 10.3 vs 7.0 us
-        // against k_stft; 3 = always; 1 = k_stft).  The round-3 kernel with static runs per wave (k_stft2) lost to one of the
-        // two on every shape of the sweep (profiles/r05_sweep_before_prune.log) and was removed in round 5.
-        if (opt(OPT_STFT_VARIANT) == 3 || (opt(OPT_STFT_VARIANT) == 0 && ngroups >= 8LL * cus)) {
-            const size_t lds3 = stft3_lds_bytes(NC);
-            static LdsOptIn lds_opt_in3;
-            const unsigned grid3 = (unsigned)std::max<long long>(1, std::min<long long>((ngroups + kStft3Waves - 1) / kStft3Waves, cus));
-            {
-                // the CL instance (channel-pair fetch at n_fft 1024; channels_last store) whenever a side is interleaved and
-                // the G frames of a wave are channels of one (item, frame) -- also for interleaved input with
-                // channels_first output (per-row stores there); n_fft 2048 (one frame per wave): channels_last output only
-                if (g.cfast && (g.C % G) == 0 && (NC == 512 || OUT_CL)) {
-                    static LdsOptIn lds_opt_in3c;
-                    if (int e = allow_big_lds(lds_opt_in3c, reinterpret_cast<const void*>(&k_stft3<NC, MODE, true>))) return e;
-                    hipLaunchKernelGGL((k_stft3<NC, MODE, true>), dim3(grid3), dim3(64 * kStft3Waves), lds3, st, x, g, window, tw, out,
-                                       (int)(ngroups / grid3), (int)(ngroups % grid3));
-                    return launch_check("k_stft3_cl", NC, MODE == KPR_OUT_COMPLEX ? "complex" : "magnitude");
-                }
-            }
-            if (int e = allow_big_lds(lds_opt_in3, reinterpret_cast<const void*>(&k_stft3<NC, MODE, false>))) return e;
-            hipLaunchKernelGGL((k_stft3<NC, MODE, false>), dim3(grid3), dim3(64 * kStft3Waves), lds3, st, x, g, window, tw, out,
-                               (int)(ngroups / grid3), (int)(ngroups % grid3));
-            return launch_check("k_stft3", NC, MODE == KPR_OUT_COMPLEX ? "complex" : "magnitude");
-        }
-    }
+    const bool cl_ok = g.cfast && (g.C % G) == 0;
+    if (mode == KPR_OUT_PHASE || NC < 512 || (g.out_cl && !cl_ok)) return STFT_K;   // (the n_fft 256 / 512 instances spill at 128 VGPRs)
+    // k_stft3: one sixteen-wave workgroup per CU drawing frame groups from an LDS counter (stft_variant 0 = automatic, from
+    // 8 groups per CU up -- tools/sweep_dispatch.py stft: 13.5 groups per CU 12.2 vs 14.0 us, 2.6 per CU 10.3 vs 7.0 us
+    // against k_stft; 3 = always; 1 = k_stft).  The round-3 kernel with static runs per wave (k_stft2) lost to one of the
+    // two on every shape of the sweep (profiles/r05_sweep_before_prune.log) and was removed in round 5.
+    if (!(opt(OPT_STFT_VARIANT) == 3 || (opt(OPT_STFT_VARIANT) == 0 && ngroups >= 8LL * cus))) return STFT_K;
+    // the CL instance (channel-pair fetch at n_fft 1024; channels_last store) whenever a side is interleaved and
+    // the G frames of a wave are channels of one (item, frame) -- also for interleaved input with
+    // channels_first output (per-row stores there); n_fft 2048 (one frame per wave): channels_last output only
+    return cl_ok && (NC == 512 || g.out_cl) ? STFT_K3_CL : STFT_K3;
+}
+
+template <int NC, int MODE, bool CL>
+static int launch_stft3(const float* x, const Geom& g, const float* window, const float2* tw, void* out, int cus,
+                        hipStream_t st) {
+    constexpr int G = 64 / (NC / kPts);
+    const long long ngroups = (g.total_frames + G - 1) / G;
+    const size_t lds3 = stft3_lds_bytes(NC);
+    static LdsOptIn lds_opt_in;
+    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_stft3<NC, MODE, CL>))) return e;
+    const unsigned grid3 = (unsigned)std::max<long long>(1, std::min<long long>((ngroups + kStft3Waves - 1) / kStft3Waves, cus));
+    hipLaunchKernelGGL((k_stft3<NC, MODE, CL>), dim3(grid3), dim3(64 * kStft3Waves), lds3, st, x, g, window, tw, out,
+                       (int)(ngroups / grid3), (int)(ngroups % grid3));
+    return launch_check(CL ? "k_stft3_cl" : "k_stft3", NC, MODE == KPR_OUT_COMPLEX ? "complex" : "magnitude");
+}
+
+template <int NC, int MODE, bool OUT_CL>
+static int launch_stft_inst(const float* x, const Geom& g, const float* window, const float2* tw, void* out, int cus,
+                            hipStream_t st) {
+    constexpr int G = 64 / (NC / kPts);
+    const long long ngroups = (g.total_frames + G - 1) / G;          // wave-loads of G frames
+    const size_t lds = stft_lds_bytes(NC);
     // workgroups the hardware can keep resident per CU (registers + LDS), asked from the runtime
     static int resident_dev[64] = {0};
     int dev = 0;
@@ -766,20 +800,23 @@ static int launch_stft_inst(const float* x, const Geom& g, const float* window, 
                                              : (MODE == KPR_OUT_COMPLEX ? "complex" : MODE == KPR_OUT_MAGNITUDE ? "magnitude" : "phase"));
 }
 
+// kernel: stft_pow2_kernel's choice
 template <int NC>
-static int launch_stft_fast(const float* x, const Geom& g, const float* window, const float2* tw,
-                            int mode, void* out, hipStream_t st) {
-    const bool cl = g.out_cl != 0;
+static int launch_stft_pow2(int kernel, const float* x, const Geom& g, const float* window, const float2* tw, int mode,
+                            void* out, int cus, hipStream_t st) {
+    auto run = [&](auto mode_c) -> int {
+        constexpr int MODE = decltype(mode_c)::value;
+        if constexpr (MODE != KPR_OUT_PHASE && NC >= 512) {
+            if (kernel == STFT_K3_CL) return launch_stft3<NC, MODE, true>(x, g, window, tw, out, cus, st);
+            if (kernel == STFT_K3) return launch_stft3<NC, MODE, false>(x, g, window, tw, out, cus, st);
+        }
+        return g.out_cl ? launch_stft_inst<NC, MODE, true>(x, g, window, tw, out, cus, st)
+                        : launch_stft_inst<NC, MODE, false>(x, g, window, tw, out, cus, st);
+    };
     switch (mode) {
-        case KPR_OUT_COMPLEX:
-            return cl ? launch_stft_inst<NC, KPR_OUT_COMPLEX, true>(x, g, window, tw, out, st)
-                      : launch_stft_inst<NC, KPR_OUT_COMPLEX, false>(x, g, window, tw, out, st);
-        case KPR_OUT_MAGNITUDE:
-            return cl ? launch_stft_inst<NC, KPR_OUT_MAGNITUDE, true>(x, g, window, tw, out, st)
-                      : launch_stft_inst<NC, KPR_OUT_MAGNITUDE, false>(x, g, window, tw, out, st);
-        default:
-            return cl ? launch_stft_inst<NC, KPR_OUT_PHASE, true>(x, g, window, tw, out, st)
-                      : launch_stft_inst<NC, KPR_OUT_PHASE, false>(x, g, window, tw, out, st);
+        case KPR_OUT_COMPLEX:   return run(std::integral_constant<int, KPR_OUT_COMPLEX>{});
+        case KPR_OUT_MAGNITUDE: return run(std::integral_constant<int, KPR_OUT_MAGNITUDE>{});
+        default:                return run(std::integral_constant<int, KPR_OUT_PHASE>{});
     }
 }
 
@@ -862,27 +899,31 @@ typedef TwoPassFft<16, 24> Fft768;  typedef TwoPassFft<20, 24> Fft960;
 // (the smaller factor first where it matters: N1 values per lane are prefetched one ticket ahead, twice
 //  over in the inverse kernels, and <24, .> spilled there)
 
-// 1: MrFft plan (forward, inverse and ring-ISTFT kernels), 2: TwoPassFft plan (forward and inverse), 0: none
-static int mixed_radix_plan(int n_fft) {
+// n_fft -> f(FftTag<plan>) for every size with a mixed-radix plan, none() for the others
+template <class FF> struct FftTag { using type = FF; };
+template <class Fn, class None>
+static int with_mr(int n_fft, Fn&& f, None&& none) {
     switch (n_fft) {
-        case 160: case 200: case 320: case 400: case 640: case 800: case 1000: return 1;
-        case 96: case 120: case 192: case 240: case 360: case 384: case 480: case 600: case 720: case 768:
-        case 960: return 2;
-        default: return 0;
+        case 160: return f(FftTag<Fft160>{});   case 200: return f(FftTag<Fft200>{});    case 320: return f(FftTag<Fft320>{});
+        case 400: return f(FftTag<Fft400>{});   case 640: return f(FftTag<Fft640>{});    case 800: return f(FftTag<Fft800>{});
+        case 1000: return f(FftTag<Fft1000>{});
+        case 96: return f(FftTag<Fft96>{});     case 120: return f(FftTag<Fft120>{});    case 192: return f(FftTag<Fft192>{});
+        case 240: return f(FftTag<Fft240>{});   case 360: return f(FftTag<Fft360>{});    case 384: return f(FftTag<Fft384>{});
+        case 480: return f(FftTag<Fft480>{});   case 600: return f(FftTag<Fft600>{});    case 720: return f(FftTag<Fft720>{});
+        case 768: return f(FftTag<Fft768>{});   case 960: return f(FftTag<Fft960>{});
+        default: return none();
     }
 }
-#define KPR_MR_CASES(FN, ...)                                                                      \
-    case 160: return FN<Fft160>(__VA_ARGS__);   case 200: return FN<Fft200>(__VA_ARGS__);          \
-    case 320: return FN<Fft320>(__VA_ARGS__);   case 400: return FN<Fft400>(__VA_ARGS__);          \
-    case 640: return FN<Fft640>(__VA_ARGS__);   case 800: return FN<Fft800>(__VA_ARGS__);          \
-    case 1000: return FN<Fft1000>(__VA_ARGS__);
-#define KPR_2P_CASES(FN, ...)                                                                      \
-    case 96: return FN<Fft96>(__VA_ARGS__);     case 120: return FN<Fft120>(__VA_ARGS__);          \
-    case 192: return FN<Fft192>(__VA_ARGS__);   case 240: return FN<Fft240>(__VA_ARGS__);          \
-    case 360: return FN<Fft360>(__VA_ARGS__);   case 384: return FN<Fft384>(__VA_ARGS__);          \
-    case 480: return FN<Fft480>(__VA_ARGS__);   case 600: return FN<Fft600>(__VA_ARGS__);          \
-    case 720: return FN<Fft720>(__VA_ARGS__);   case 768: return FN<Fft768>(__VA_ARGS__);          \
-    case 960: return FN<Fft960>(__VA_ARGS__);
+template <class Fn>
+static int with_mr(int n_fft, Fn&& f) {
+    return with_mr(n_fft, f, [&] { return fail(KPR_E_UNSUPPORTED, "no mixed-radix plan for n_fft %d", n_fft); });
+}
+template <class FF> struct IsTwoPass : std::false_type {};
+template <int N1, int N2> struct IsTwoPass<TwoPassFft<N1, N2>> : std::true_type {};
+// 1: MrFft plan (forward, inverse and ring-ISTFT kernels), 2: TwoPassFft plan (forward and inverse), 0: none
+static int mixed_radix_plan(int n_fft) {
+    return with_mr(n_fft, [](auto ff) { return IsTwoPass<typename decltype(ff)::type>::value ? 2 : 1; }, [] { return 0; });
+}
 
 template <class FF>
 static size_t mr_lds_bytes() {
@@ -909,27 +950,18 @@ static int launch_stft_mr_inst(const float* x, const Geom& g, const float* windo
 static int launch_stft_mr(const float* x, const Geom& g, const float* window, int mode, void* out, hipStream_t st) {
     const float2* tw = nullptr;
     if (int e = get_twiddles(g.n_fft, &tw)) return e;
-    switch (g.n_fft) {
-        KPR_MR_CASES(launch_stft_mr_inst, x, g, window, tw, mode, out, st)
-        KPR_2P_CASES(launch_stft_mr_inst, x, g, window, tw, mode, out, st)
-        default: return fail(KPR_E_UNSUPPORTED, "no mixed-radix plan for n_fft %d", g.n_fft);
-    }
+    return with_mr(g.n_fft, [&](auto ff) {
+        return launch_stft_mr_inst<typename decltype(ff)::type>(x, g, window, tw, mode, out, st);
+    });
 }
 
 static int launch_stft_bs(const float* x, const Geom& g, const float* window, int mode, void* out,
                           hipStream_t st) {
-    // sizes with a mixed-radix plan: one N-point FFT per frame instead of two chirp-z FFTs
-    if (mixed_radix_plan(g.n_fft) && opt(OPT_MIXED_RADIX)) return launch_stft_mr(x, g, window, mode, out, st);
     const int m = bluestein_m(g.n_fft);
     const float2 *tw = nullptr, *bs = nullptr;
     if (int e = get_twiddles(2 * m, &tw)) return e;
     if (int e = get_bluestein(g.n_fft, &bs)) return e;
-    switch (m) {
-        case 128:  return launch_stft_bs_m<128>(x, g, window, tw, bs, mode, out, st);
-        case 256:  return launch_stft_bs_m<256>(x, g, window, tw, bs, mode, out, st);
-        case 512:  return launch_stft_bs_m<512>(x, g, window, tw, bs, mode, out, st);
-        default:   return launch_stft_bs_m<1024>(x, g, window, tw, bs, mode, out, st);
-    }
+    return with_pow2(m, [&](auto m_c) { return launch_stft_bs_m<m_c>(x, g, window, tw, bs, mode, out, st); });
 }
 
 template <int M>
@@ -966,11 +998,9 @@ static int launch_irfft_mr_inst(const float2* spec, const Geom& g, const float* 
 static int launch_irfft_mr(const float2* spec, const Geom& g, const float* synth, float* frames, hipStream_t st) {
     const float2* tw = nullptr;
     if (int e = get_twiddles(g.n_fft, &tw)) return e;
-    switch (g.n_fft) {
-        KPR_MR_CASES(launch_irfft_mr_inst, spec, g, synth, tw, frames, st)
-        KPR_2P_CASES(launch_irfft_mr_inst, spec, g, synth, tw, frames, st)
-        default: return fail(KPR_E_UNSUPPORTED, "no mixed-radix plan for n_fft %d", g.n_fft);
-    }
+    return with_mr(g.n_fft, [&](auto ff) {
+        return launch_irfft_mr_inst<typename decltype(ff)::type>(spec, g, synth, tw, frames, st);
+    });
 }
 
 template <class FF, int RJ, int VEC>
@@ -985,59 +1015,46 @@ static int launch_istft_ws_mr_inst(const float2* spec, const IstftWsPlan& pl, si
                                                                                    : (VEC == 4 ? "rj8,v4" : "rj8,v2"));
 }
 
-template <class FF>
-static int launch_istft_ws_mr_plan(const float2* spec, const kpr_stft_geom* s, long long F, const float* synth,
-                                   const float2* tw, float* out, hipStream_t st, bool* launched) {
-    constexpr int G = 64 / FF::L;
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
-    IstftWsPlan pl;
-    size_t lds;
-    int RJ, VEC;
-    long long nitems;
-    // rows double as exchange rows (ROW complex words); window pairs and the twiddle table behind the counters
-    if (!istft_ws_plan(s, F, out, 2 * FF::ROW, G, 0, sizeof(float) * 2 * 3 * (size_t)FF::N, cus, 2, &pl, &lds, &RJ, &VEC,
-                       &nitems))
+// the ring kernel with mixed-radix producers (n_fft with a mixed-radix plan)
+static bool istft_ws_mr_plan(const kpr_stft_geom* s, long long F, const float* out, int cus, IstftRoute* r) {
+    if (!mixed_radix_plan(s->n_fft) || !opt(OPT_MIXED_RADIX) || s->win_length > s->n_fft) return false;
+    int vec = 0;
+    bool ok = false;
+    with_mr(s->n_fft, [&](auto ff) {
+        using FF = typename decltype(ff)::type;
+        // rows double as exchange rows (ROW complex words); window pairs and the twiddle table behind the counters
+        ok = istft_ws_plan(s, F, out, 2 * FF::ROW, 64 / FF::L, 0, sizeof(float) * 2 * 3 * (size_t)FF::N, cus, 2, &r->ws, &r->lds,
+                           &r->rj, &vec, &r->nitems);
         return 0;
-    if (RJ > 4) return 0;                                       // more than four overlapping frames: two-kernel path
+    });
+    if (!ok || r->rj > 4) return false;                         // more than four overlapping frames: two-kernel path
     // hop or win_length not a multiple of four: the consumer would sum and store 8 bytes per lane.  Those 18 instances
     // (k_istft_ws_mr<FF, 4, 2>) were removed in round 6: on 64 x 10 s @ 16 kHz they beat irFFT + overlap-add as two kernels by at
     // most 1.4x (n_fft 200 / hop 50: 156 vs 214 us, 1000 / 250: 154 vs 189, 120 / 30: 156 vs 187) and LOST at 360 / 90 (205 vs
     // 138) and 600 / 150 (245 vs 199) -- profiles/r06_sweep_before_prune.log; VERDICT r05 item 7 asked for > 1.5x.
-    if (VEC == 2) return 0;
-    const unsigned grid = (unsigned)std::min<long long>(nitems, cus);
-    *launched = true;
-    if (RJ == 2) return launch_istft_ws_mr_inst<FF, 2, 4>(spec, pl, lds, grid, synth, tw, out, (int)nitems, st);
-    return launch_istft_ws_mr_inst<FF, 4, 4>(spec, pl, lds, grid, synth, tw, out, (int)nitems, st);
+    if (vec == 2) return false;
+    r->fam = IST_WS_MR;
+    r->grid = (unsigned)std::min<long long>(r->nitems, cus);
+    return true;
 }
 
-// ring kernel for the mixed-radix transform sizes; *launched stays false when it does not apply
-static int launch_istft_ws_mr(const float2* spec, const kpr_stft_geom* s, long long F, const float* synth,
-                              float* out, hipStream_t st, bool* launched) {
-    *launched = false;
-    if (!mixed_radix_plan(s->n_fft) || !opt(OPT_MIXED_RADIX) || s->win_length > s->n_fft) return 0;
+static int launch_istft_ws_mr(const float2* spec, const IstftRoute& r, int n_fft, const float* synth, float* out, hipStream_t st) {
     const float2* tw = nullptr;
-    if (int e = get_twiddles(s->n_fft, &tw)) return e;
-    switch (s->n_fft) {
-        KPR_MR_CASES(launch_istft_ws_mr_plan, spec, s, F, synth, tw, out, st, launched)
-        KPR_2P_CASES(launch_istft_ws_mr_plan, spec, s, F, synth, tw, out, st, launched)
-        default: return 0;
-    }
+    if (int e = get_twiddles(n_fft, &tw)) return e;
+    return with_mr(n_fft, [&](auto ff) {
+        using FF = typename decltype(ff)::type;
+        return r.rj == 2 ? launch_istft_ws_mr_inst<FF, 2, 4>(spec, r.ws, r.lds, r.grid, synth, tw, out, (int)r.nitems, st)
+                         : launch_istft_ws_mr_inst<FF, 4, 4>(spec, r.ws, r.lds, r.grid, synth, tw, out, (int)r.nitems, st);
+    });
 }
 
 static int launch_irfft_bs(const float2* spec, const Geom& g, const float* synth, float* frames,
                            hipStream_t st) {
-    if (mixed_radix_plan(g.n_fft) && opt(OPT_MIXED_RADIX)) return launch_irfft_mr(spec, g, synth, frames, st);
     const int m = bluestein_m(g.n_fft);
     const float2 *tw = nullptr, *bs = nullptr;
     if (int e = get_twiddles(2 * m, &tw)) return e;
     if (int e = get_bluestein(g.n_fft, &bs)) return e;
-    switch (m) {
-        case 128:  return launch_irfft_bs_m<128>(spec, g, synth, tw, bs, frames, st);
-        case 256:  return launch_irfft_bs_m<256>(spec, g, synth, tw, bs, frames, st);
-        case 512:  return launch_irfft_bs_m<512>(spec, g, synth, tw, bs, frames, st);
-        default:   return launch_irfft_bs_m<1024>(spec, g, synth, tw, bs, frames, st);
-    }
+    return with_pow2(m, [&](auto m_c) { return launch_irfft_bs_m<m_c>(spec, g, synth, tw, bs, frames, st); });
 }
 
 template <int NC>
@@ -1348,20 +1365,29 @@ static int launch_mel_ws_inst(const float* x, const Geom& g, const float* window
     return launch_check("k_mel_ws", NC);
 }
 
-// fbp: the fragment section of the packed blob (behind its header)
+// the longest filterbank slice (chunks) of the four consumer waves of k_mel_ws
+static int slice_max(const MelSched& sch) {
+    int m = 0;
+    for (int i = 0; i < 4; ++i) m = std::max(m, (int)sch.wave_nchunks[i]);
+    return m;
+}
+
+enum { WS_PLAIN, WS_RES, WS_LD8 };                               // k_mel_ws instances (mel_ws_form)
+static int mel_ws_form(const MelSched& sch, bool from_mag, int K) {
+    // every consumer wave's slice fits the register-resident form (mel banks: 37 chunks at 1025 x 128)?
+    if (!from_mag) return slice_max(sch) <= kWsResident && opt(OPT_MEL_VARIANT) != 2 ? WS_RES : WS_PLAIN;
+    return K > 512 ? WS_LD8 : WS_PLAIN;                            // wide rows: 8 loaders
+}
+
+// fbp: the fragment section of the packed blob (behind its header); form: mel_ws_form
 template <int NC, bool FROM_MAG = false>
-static int launch_mel_ws(const float* x, const Geom& g, const float* window, const float2* tw,
+static int launch_mel_ws(int form, const float* x, const Geom& g, const float* window, const float2* tw,
                          const float* fbp, const MelSched& sch, const DbDev& db, unsigned* stats,
                          float* out, hipStream_t st) {
-    if constexpr (!FROM_MAG) {
-        // every consumer wave's slice fits the register-resident form (mel banks: 37 chunks at 1025 x 128)?
-        int slice_max = 0;
-        for (int i = 0; i < 4; ++i) slice_max = std::max(slice_max, (int)sch.wave_nchunks[i]);
-        if (slice_max <= kWsResident && opt(OPT_MEL_VARIANT) != 2)
-            return launch_mel_ws_inst<NC, false, true>(x, g, window, tw, fbp, sch, db, stats, out, st);
-    }
     if constexpr (FROM_MAG) {
-        if (g.K > 512) return launch_mel_ws_inst<NC, true, false, true>(x, g, window, tw, fbp, sch, db, stats, out, st);   // wide rows: 8 loaders
+        if (form == WS_LD8) return launch_mel_ws_inst<NC, true, false, true>(x, g, window, tw, fbp, sch, db, stats, out, st);
+    } else {
+        if (form == WS_RES) return launch_mel_ws_inst<NC, false, true>(x, g, window, tw, fbp, sch, db, stats, out, st);
     }
     return launch_mel_ws_inst<NC, FROM_MAG, false>(x, g, window, tw, fbp, sch, db, stats, out, st);
 }
@@ -1533,13 +1559,10 @@ static int launch_mel_pw(const float* x, const Geom& g, const float* window, con
                        (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
     return launch_check("k_mel_pw", NC, W == 4 ? "w4" : W == 8 ? "w8" : "w16");
 }
-// the PAIR form (interleaved waveforms, even channel count: two channel-frames per fetch; three waves per SIMD)
-template <int NC>
-static int launch_mel_pw_pair(const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
-                              const PackInfo& pi, int M, const DbDev& db, unsigned* stats, float* out, hipStream_t st) {
-    constexpr int L = NC / kPts, G = 64 / L, W = 12;
-    PwPlan pl{(int)pi.L, (int)pi.NR, (int)pi.CMQ, (int)pi.nlist, M, reinterpret_cast<const unsigned*>(blob) + pi.band_off,
-              reinterpret_cast<const unsigned*>(blob), pi.band_off, 0, 0};
+constexpr int kPwPairWaves = 12;                                 // waves per workgroup of the PAIR form
+// the PAIR form's channels_last staging: output slots (0: 8-byte stores) of M x C floats each
+static int mel_pw_pair_slots(const Geom& g, const PackInfo& pi, int M, const float* out) {
+    const int NC = g.n_fft / 2, G = 64 / (NC / kPts), W = kPwPairWaves;
     // channels_last output with C >= 4: the M x C block of an (item, frame) through a ring of LDS slots, stored as one contiguous
     // run by the last of its C / 2 pair-waves (kpr_mel_pw_kernels.h; n_fft 2048 only).  A power of two, whatever fits the CU's LDS, and
     // at least the blocks the W waves can hold pairs of (need / 2: progress is guaranteed by the ticket order with any ring of one
@@ -1551,9 +1574,20 @@ static int launch_mel_pw_pair(const float* x, const Geom& g, const float* window
         const int blk = M * g.C;
         const int need = 2 * ((W * G + CP - 1) / CP) + 2;
         int slots = 32;
-        while (slots >= 4 && pw_lds_bytes(NC, W, pl.NR, pl.CMQ, true, slots, blk) > 160 * 1024) slots >>= 1;
-        if (slots >= 4 && slots >= need / 2) { pl.cl_slots = slots; pl.cl_blk = blk; }
+        while (slots >= 4 && pw_lds_bytes(NC, W, (int)pi.NR, (int)pi.CMQ, true, slots, blk) > 160 * 1024) slots >>= 1;
+        if (slots >= 4 && slots >= need / 2) return slots;
     }
+    return 0;
+}
+
+// the PAIR form (interleaved waveforms, even channel count: two channel-frames per fetch; three waves per SIMD)
+template <int NC>
+static int launch_mel_pw_pair(const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
+                              const PackInfo& pi, int M, int cl_slots, const DbDev& db, unsigned* stats, float* out, hipStream_t st) {
+    constexpr int L = NC / kPts, G = 64 / L, W = kPwPairWaves;
+    PwPlan pl{(int)pi.L, (int)pi.NR, (int)pi.CMQ, (int)pi.nlist, M, reinterpret_cast<const unsigned*>(blob) + pi.band_off,
+              reinterpret_cast<const unsigned*>(blob), pi.band_off, cl_slots, cl_slots ? M * g.C : 0};
+    const int CP = g.C / 2;
     const size_t lds = pw_lds_bytes(NC, W, pl.NR, pl.CMQ, true, pl.cl_slots, pl.cl_blk);
     static LdsOptIn lds_opt_in;
     if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_mel_pw<NC, W, true>))) return e;
@@ -1606,30 +1640,14 @@ static int launch_fb_pw(const float* x, long long rows, int K, const float* blob
                        (int)(tickets % grid));
     return ST ? launch_check("k_fb_pw", NC, "st") : launch_check("k_fb_pw", NC);
 }
-template <bool ST>
-static int launch_fb_pw_l(int lanes, const float* x, long long rows, int K, const float* blob, const PackInfo& pi, int M, const float* fb,
-                          float* out, hipStream_t st) {
-    switch (lanes) {
-        case 8:  return launch_fb_pw<128, ST>(x, rows, K, blob, pi, M, fb, out, st);
-        case 16: return launch_fb_pw<256, ST>(x, rows, K, blob, pi, M, fb, out, st);
-        case 32: return launch_fb_pw<512, ST>(x, rows, K, blob, pi, M, fb, out, st);
-        default: return launch_fb_pw<1024, ST>(x, rows, K, blob, pi, M, fb, out, st);
-    }
-}
 
 // ---- k_mel_mr: the same schedule for the mixed-radix sizes (four-wave workgroups, up to three per CU) ---------------
 static bool mel_mr_nfft(int n_fft) { return mixed_radix_plan(n_fft) != 0; }
 template <class FF>
 static int launch_mel_mr_inst(const float* x, const Geom& g, const float* window, const float2* tw, const float* fbp,
-                              const int32_t* kr_host, int M, const DbDev& db, unsigned* stats, float* out,
-                              hipStream_t st, bool* taken) {
+                              const MelSchedTs& sch, const DbDev& db, unsigned* stats, float* out, hipStream_t st) {
     constexpr int G = 64 / FF::L, RF = mel_mr_rf<FF>();
-    *taken = false;
-    MelSchedTs sch;
-    if (get_sched_ts(FF::N + 1, M, kr_host, mel_mr_nt<FF>(), 0, kMrWaves, &sch)) return 0;   // no schedule: the caller's other path
     const size_t lds = mel_mr_lds_bytes<FF>(sch.nslots);
-    if (lds > 160 * 1024) return 0;
-    *taken = true;
     static LdsOptIn lds_opt_in;
     if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_mel_mr<FF>))) return e;
     int cus = 256;
@@ -1641,24 +1659,6 @@ static int launch_mel_mr_inst(const float* x, const Geom& g, const float* window
     hipLaunchKernelGGL((k_mel_mr<FF>), dim3(grid), dim3(kMrWaves * 64), lds, st, x, g, window, tw, fbp, sch, db, stats, out,
                        (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
     return launch_check("k_mel_mr", FF::N);
-}
-static int launch_mel_mr(const float* x, const Geom& g, const float* window, const float* fbp, const int32_t* kr_host,
-                         int M, const DbDev& db, unsigned* stats, float* out, hipStream_t st, bool* taken) {
-    *taken = false;
-    if ((M + 15) / 16 > kTsMaxTiles || g.total_frames >= 0x7fffff00LL) return 0;
-    const float2* tw = nullptr;
-    if (int e = get_twiddles(g.n_fft, &tw)) return e;
-    switch (g.n_fft) {
-        case 160:  return launch_mel_mr_inst<Fft160>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 200:  return launch_mel_mr_inst<Fft200>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 320:  return launch_mel_mr_inst<Fft320>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 400:  return launch_mel_mr_inst<Fft400>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 640:  return launch_mel_mr_inst<Fft640>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 800:  return launch_mel_mr_inst<Fft800>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        case 1000: return launch_mel_mr_inst<Fft1000>(x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken);
-        KPR_2P_CASES(launch_mel_mr_inst, x, g, window, tw, fbp, kr_host, M, db, stats, out, st, taken)
-        default:   return 0;
-    }
 }
 
 // blocks per item of the decibel passes: enough blocks to fill the GPU (about 2048), at least 4096
@@ -1682,17 +1682,16 @@ static int db_clamp(float* out, long long n_items, long long item_size, float dy
     return launch_check("k_db_clamp");
 }
 
-// banded filterbank product on contiguous |X| rows (k_band_mel) + the decibel clamp pass
+// banded filterbank product on contiguous |X| rows (k_band_mel)
 static int run_band_mel(const float* mag, const Geom& g, const float* fb, const MelSched& sch, const DbDev& dbd,
-                        unsigned* stats, float* out, long long batch, long long item_size, hipStream_t st) {
+                        unsigned* stats, float* out, hipStream_t st) {
     // (k_band_mel's own atomics use slot 0; the other slots keep their initial values and drop out of the reduction)
     const size_t lds = sizeof(float) * (size_t)kBandRows * g.K;
     static LdsOptIn lds_opt_in;
     if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_band_mel))) return e;
     const long long nsteps = (g.total_frames + kBandRows - 1) / kBandRows;
     hipLaunchKernelGGL(k_band_mel, dim3(grid_1d(nsteps, 1, 256 * 8)), dim3(256), lds, st, mag, g, fb, sch, dbd, stats, out);
-    if (int e = launch_check("k_band_mel")) return e;
-    return dbd.enabled ? db_clamp(out, batch, item_size, dbd.dyn, stats, st, dbd.slot_mask + 1) : 0;
+    return launch_check("k_band_mel");
 }
 
 }  // namespace kpr
@@ -1935,16 +1934,64 @@ int64_t kpr_num_frames(const kpr_stft_geom* s) {
     return frames_of(s);
 }
 
+// the FFT family of a transform size, in dispatch order (forward transforms: the cropped geometry of forward_geom)
+static int fft_family(const kpr_stft_geom* s) {
+    if (fast_nfft(s->n_fft)) return FAM_POW2;
+    // even n_fft that is not a power of two: sizes with a mixed-radix plan take one N-point FFT per frame instead of two chirp-z FFTs
+    if (bluestein_ok(s)) return mixed_radix_plan(s->n_fft) && opt(OPT_MIXED_RADIX) ? FAM_MR : FAM_BS;
+    if (big_nfft(s->n_fft)) return FAM_BIG;
+    // every other size with small prime factors (odd sizes, 1200, 1536, 2000 ...): run-time mixed-radix FFT
+    if (gen_ok_f32(s)) return FAM_GEN;
+    return FAM_GEMM;
+}
+
+struct StftRoute {
+    int fam;                   // FAM_*
+    int kernel;                // FAM_POW2: stft_pow2_kernel
+    int cfast;                 // Geom::cfast of the launch
+    int64_t workspace;         // bytes the call needs
+};
+
+// s: the cropped geometry (forward_geom), g: its Geom
+static StftRoute stft_route(const kpr_stft_geom* s, const Geom& g, int mode, int cus) {
+    StftRoute r{fft_family(s), STFT_K, 0, 0};
+    if (r.fam == FAM_POW2) {
+        // channel-fastest frame numbering whenever either side is interleaved: the frames that share the waveform's cache
+        // lines / the spectrogram's channel runs sit in one wave
+        Geom gk = g;
+        gk.cfast = r.cfast = ((g.in_cl || g.out_cl) && g.C > 1) ? 1 : 0;
+        r.kernel = stft_pow2_kernel(gk, mode, cus);
+    }
+    // every FFT family writes |X| / phase itself; the DFT-GEMM path with a real-valued epilogue stages the complex spectrum in
+    // the workspace
+    if (r.fam == FAM_GEMM && mode != KPR_OUT_COMPLEX) r.workspace = (int64_t)sizeof(float) * 2 * g.total_frames * g.K;
+    return r;
+}
+
+// the forward transform of route `r` into `out` (the DFT-GEMM family: complex output only)
+static int launch_stft(const StftRoute& r, const float* x, const Geom& g, const float* window, int mode, void* out, int cus,
+                       hipStream_t st) {
+    switch (r.fam) {
+        case FAM_POW2: {
+            const float2* tw = nullptr;
+            if (int e = get_twiddles(g.n_fft, &tw)) return e;
+            return with_pow2(g.n_fft / 2, [&](auto nc) {
+                return launch_stft_pow2<decltype(nc)::value>(r.kernel, x, g, window, tw, mode, out, cus, st);
+            });
+        }
+        case FAM_MR:  return launch_stft_mr(x, g, window, mode, out, st);
+        case FAM_BS:  return launch_stft_bs(x, g, window, mode, out, st);
+        case FAM_BIG: return launch_stft_big(x, g, window, mode, out, st);
+        case FAM_GEN: return launch_stft_gen_f32(x, g, window, mode, out, st);
+        default:      return stft_gemm(x, g, window, (float*)out, st);
+    }
+}
+
 int64_t kpr_stft_workspace_bytes(const kpr_stft_geom* s, int mode) {
     if (check_geom(s)) return -1;
-    const long long F = frames_of(s);
     const kpr_stft_geom se = forward_geom(s);
-    s = &se;
-    if (fast_nfft(s->n_fft) || bluestein_ok(s) || mode == KPR_OUT_COMPLEX) return 0;
-    if (big_nfft(s->n_fft) && s->win_length <= s->n_fft) return 0;     // k_stft_big writes |X| / phase itself
-    if (gen_ok_f32(s)) return 0;                                        // so does the size-generic FFT kernel
-    // DFT-GEMM path with a real-valued epilogue: complex spectrum staged in the workspace
-    return (int64_t)sizeof(float) * 2 * s->batch * s->channels * F * (s->n_fft / 2 + 1);
+    // (no device query: the CU count only picks among kernels that need no workspace)
+    return stft_route(&se, make_geom(&se, frames_of(s)), mode, 256).workspace;
 }
 
 int kpr_stft_f32(const float* x, const kpr_stft_geom* s, const float* window, void* out, int mode,
@@ -1953,35 +2000,20 @@ int kpr_stft_f32(const float* x, const kpr_stft_geom* s, const float* window, vo
     if (int e = check_geom(s)) return e;
     if (mode < 0 || mode > 2) return fail(KPR_E_BADARG, "bad output mode %d", mode);
     const long long F = frames_of(s);
-    const kpr_stft_geom* s_call = s;
     const kpr_stft_geom se = forward_geom(s);                    // win_length > n_fft: cropped frames (see forward_geom)
     s = &se;
     Geom g = make_geom(s, F);
     if (g.total_frames == 0) return 0;
     if (!x || !window || !out) return fail(KPR_E_BADARG, "x / window / out must not be NULL");
     hipStream_t st = (hipStream_t)stream;
-    if (fast_nfft(s->n_fft)) {
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        // channel-fastest frame numbering whenever either side is interleaved: the frames that share the waveform's cache
-        // lines / the spectrogram's channel runs sit in one wave
-        g.cfast = ((g.in_cl || g.out_cl) && g.C > 1) ? 1 : 0;
-        switch (s->n_fft) {
-            case 256:  return launch_stft_fast<128>(x, g, window, tw, mode, out, st);
-            case 512:  return launch_stft_fast<256>(x, g, window, tw, mode, out, st);
-            case 1024: return launch_stft_fast<512>(x, g, window, tw, mode, out, st);
-            default:   return launch_stft_fast<1024>(x, g, window, tw, mode, out, st);
-        }
-    }
-    if (bluestein_ok(s)) return launch_stft_bs(x, g, window, mode, out, st);
-    if (big_nfft(s->n_fft) && s->win_length <= s->n_fft) return launch_stft_big(x, g, window, mode, out, st);
-    // every other size with small prime factors (odd sizes, 1200, 1536, 2000 ...): run-time mixed-radix FFT
-    if (gen_ok_f32(s)) return launch_stft_gen_f32(x, g, window, mode, out, st);
-    if (mode == KPR_OUT_COMPLEX) return stft_gemm(x, s, g, window, (float*)out, false, st);
-    const int64_t need = kpr_stft_workspace_bytes(s_call, mode);
-    if (!workspace || workspace_bytes < need)
-        return fail(KPR_E_WORKSPACE, "stft workspace: need %lld bytes", (long long)need);
-    if (int e = stft_gemm(x, s, g, window, (float*)workspace, false, st)) return e;
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const StftRoute r = stft_route(s, g, mode, cus);
+    g.cfast = r.cfast;
+    if (r.fam != FAM_GEMM || mode == KPR_OUT_COMPLEX) return launch_stft(r, x, g, window, mode, out, cus, st);
+    if (!workspace || workspace_bytes < r.workspace)
+        return fail(KPR_E_WORKSPACE, "stft workspace: need %lld bytes", (long long)r.workspace);
+    if (int e = stft_gemm(x, g, window, (float*)workspace, st)) return e;
     const long long n = g.total_frames * g.K;
     hipLaunchKernelGGL(k_cplx_to_real, dim3(grid_1d(n, 256)), dim3(256), 0, st,
                        (const float2*)workspace, n, mode == KPR_OUT_PHASE ? 1 : 0, (float*)out);
@@ -2068,6 +2100,140 @@ int64_t kpr_mel_workspace_bytes_unpacked(const kpr_stft_geom* s, int n_filt) {
            (int64_t)sizeof(float) * 2 * s->batch * s->channels * frames_of(s) * (s->n_fft / 2 + 1);
 }
 
+enum { MEL_PW, MEL_PW_PAIR, MEL_TS, MEL_WS, MEL_MR, MEL_STAGED };     // MEL_STAGED: an STFT into the workspace, then a product
+enum { PROD_GEMM, PROD_WS, PROD_BAND };                                 // the product of MEL_STAGED
+
+struct MelRoute {
+    int fam;
+    int cfast;                 // Geom::cfast of the launch
+    int w;                     // MEL_PW: waves per workgroup
+    int cl_slots;              // MEL_PW_PAIR: mel_pw_pair_slots
+    int rf64;                  // MEL_TS: the 64-frame-round instance (n_fft 512)
+    int ws_form;               // MEL_WS, PROD_WS: mel_ws_form
+    MelSchedTs ts;             // MEL_TS, MEL_MR
+    StftRoute stage;           // MEL_STAGED: the STFT that stages the frame-contiguous spectrum
+    int stage_mode;            //   complex, or |X| for PROD_WS / PROD_BAND
+    int product;
+    int64_t workspace;         // bytes the call needs
+};
+
+// s: the cropped geometry, g: its Geom; packed: a verified packed filterbank (pi: its band plan), kr: k-ranges (NULL: dense)
+static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool packed, const PackInfo& pi, const MelSched& sch,
+                          const int32_t* kr, const float* out, int cus) {
+    MelRoute r{};
+    const int n_fft = s->n_fft, mv = opt(OPT_MEL_VARIANT);
+    const bool fits = g.total_frames < 0x7fffff00LL;
+    // channel-fastest frame numbering: the C frames that share cache lines sit in one wave
+    const int cfast = (g.in_cl && g.C > 1) ? 1 : 0;
+    // k_mel_pw (round 4): n_fft 256 ... 2048 with a band plan in the packed filterbank (mel / triangular banks) -- the
+    // default since round 4 (same-box sweeps against k_mel_ws / k_mel_ts / the ring kernel: tools/sweep_dispatch.py mel).
+    // mel_variant 5 / 6 / 7 = k_mel_pw with 8 / 4 / 16 waves per workgroup, 8 = its PAIR form where it applies (A/B runs, tests).
+    if (packed && pi.band_off && (fused_nfft(n_fft) || n_fft == 256) && s->win_length <= n_fft && (int)pi.L * kPts == g.K - 1 &&
+        fits && (mv >= 5 || mv == 0)) {
+        r.cfast = cfast;
+        // waves per workgroup: sixteen (one workgroup per CU, one copy of the tables, tickets shared by the whole CU) once
+        // there are sixteen tickets per CU; smaller launches are spread over more, smaller workgroups
+        const long long tickets_w = (g.total_frames + (64 / (n_fft / 32)) - 1) / (64 / (n_fft / 32));
+        // (tools/sweep_dispatch.py mel, gpurun_out/r04i: 8-wave workgroups win from ~4 tickets per CU up -- 8.2 vs 9.1 us at
+        //  1328 tickets -- and 16-wave ones from 16 per CU: 14.8 vs 15.9 vs 17.6 us at 5312)
+        const int w_auto = tickets_w >= 16LL * cus ? 16 : tickets_w >= 4LL * cus ? 8 : 4;
+        r.w = mv == 6 ? 4 : mv == 7 ? 16 : mv == 5 ? 8 : w_auto;
+        // interleaved waveforms with an even channel count, launches that fill the chip: the PAIR form (kpr_mel_pw_kernels.h).
+        // n_fft 1024 stereo stays on the plain kernel (its stereo pair fetch does the same at four waves per SIMD).
+        // mel_variant 8 forces it wherever it applies (tests), 5 / 6 / 7 never take it.
+        const bool pair_ok = cfast && (g.C % 2) == 0 && (n_fft == 2048 || n_fft == 1024);
+        const bool pair_auto = pair_ok && (n_fft == 2048 || g.C >= 4) && tickets_w >= 24LL * cus;
+        r.fam = MEL_PW;
+        if (pair_ok && (mv == 8 || (mv == 0 && pair_auto))) {
+            Geom gk = g;
+            gk.cfast = cfast;
+            r.fam = MEL_PW_PAIR;
+            r.cl_slots = mel_pw_pair_slots(gk, pi, M, out);
+        }
+        return r;
+    }
+    // k_mel_ts when its schedule holds the bank (fills r.ts)
+    auto ts = [&]() {
+        // n_fft 512, long runs (>= 64 k frames, two 64-frame rounds per workgroup): 64-frame rounds, two tickets per wave
+        // (256 x 2 x 1 s @22 kHz, dB: 61 vs 65 us; 43 k frames mono: 29.7 vs 27.6, hence the threshold)
+        r.rf64 = n_fft == 512 && g.total_frames >= 65536 && mel_ts_ok(n_fft, g.K, M, kr, g, &r.ts, 64);
+        if (!r.rf64 && !mel_ts_ok(n_fft, g.K, M, kr, g, &r.ts)) return false;
+        r.fam = MEL_TS;
+        r.cfast = cfast;
+        return true;
+    };
+    if (fused_nfft(n_fft) && packed) {
+        // Banks WITHOUT a band plan (log-frequency banks, dense matrices) or a forced variant: the MFMA kernels.
+        // mel_variant: 0 = automatic, 2 = k_mel_ws with a streamed filterbank slice, 3 = k_mel_ws wherever it applies,
+        // 4 = the tile-synchronous kernel k_mel_ts wherever it applies (A/B runs, tests).  The round-1 4-wave ring kernel
+        // (k_mel_fused, mel_variant 1) lost on every shape of tools/sweep_dispatch.py (profiles/r05_sweep_before_prune.log:
+        // within 4 % of k_mel_ts on launches of a few thousand frames at n_fft 512, 25-95 % behind elsewhere) and was
+        // removed in round 5.
+        // k_mel_ts: n_fft 512 (sweep, log-frequency bank: 38.6 vs 58.8 us on 256 x 1 s @22 kHz; 14.0 vs 13.4 on 16 clips),
+        // interleaved stereo at n_fft 1024 (pair fetch: 126 vs 180 us on 64 x 2 x 10 s @16 kHz), n_fft 1024 from ~12 k frames
+        // up (32-frame rounds: 6-9 % faster than k_mel_ws on 256 x 10 s @16 kHz); k_mel_ws for the rest of n_fft 1024 / 2048
+        const bool stereo_cl = g.in_cl && g.C == 2 && n_fft == 1024;
+        const bool long_1024 = n_fft == 1024 && g.total_frames >= 12288;
+        if ((mv == 4 || (mv == 0 && (n_fft == 512 || stereo_cl || long_1024))) && ts()) return r;
+        // (the consumers keep one lane of schedule per chunk of their slice)
+        if ((n_fft == 2048 || n_fft == 1024) && slice_max(sch) <= 64 && fits && mel_ws_lds_bytes(n_fft / 2, sch.nseg) <= 160 * 1024) {
+            r.fam = MEL_WS;
+            r.cfast = cfast;
+            r.ws_form = mel_ws_form(sch, false, g.K);
+            return r;
+        }
+        // what k_mel_ws cannot take (very wide banks): k_mel_ts if its schedule holds the bank, else the two-launch path below
+        if (ts()) return r;
+    }
+    // n_fft 256 (round 3): the tile-synchronous kernel takes it too (eight lanes per frame, 64-frame rounds); mel_variant 3
+    // keeps the two-launch path
+    if (packed && n_fft == 256 && s->win_length <= n_fft && mv != 3 && ts()) return r;
+    // mixed-radix sizes (n_fft 400, 320, 640 ...: speech front ends): one launch as well (k_mel_mr);
+    // kpr_set_option("mel_variant", 3) keeps the two-launch path of round 2 (A/B runs, tests)
+    if (packed && mel_mr_nfft(n_fft) && opt(OPT_MIXED_RADIX) && s->win_length <= n_fft && mv != 3 &&
+        (M + 15) / 16 <= kTsMaxTiles && fits) {
+        bool ok = false;
+        with_mr(n_fft, [&](auto ff) {
+            using FF = typename decltype(ff)::type;
+            // no schedule, or more LDS than a CU has: the two-launch path
+            ok = get_sched_ts(FF::N + 1, M, kr, mel_mr_nt<FF>(), 0, kMrWaves, &r.ts) == 0 && mel_mr_lds_bytes<FF>(r.ts.nslots) <= 160 * 1024;
+            return 0;
+        });
+        if (ok) {
+            r.fam = MEL_MR;
+            r.cfast = cfast;
+            return r;
+        }
+    }
+    // two-kernel path: STFT (frame-contiguous) -> (|.| x filterbank) product [+ dB]
+    r.fam = MEL_STAGED;
+    r.workspace = stats_region_bytes(s->batch) + (int64_t)sizeof(float) * 2 * g.total_frames * g.K;
+    r.stage = StftRoute{fft_family(s), STFT_K, 0, 0};
+    r.stage_mode = KPR_OUT_COMPLEX;
+    r.product = PROD_GEMM;
+    if (r.stage.fam == FAM_POW2) {             // Stockham STFT (n_fft = 256, or no packed filterbank given)
+        Geom gc = g;
+        gc.out_cl = 0;
+        r.stage.kernel = stft_pow2_kernel(gc, KPR_OUT_COMPLEX, cus);
+    } else if (r.stage.fam == FAM_MR || r.stage.fam == FAM_BS) {
+        // even non-power-of-two n_fft: wide packed filterbank: |X| rows straight into the fused kernel's MFMA consumers
+        // (loader producers, FROM_MAG) instead of the complex spectrum + generic GEMM
+        if (packed && g.K <= 1025 && slice_max(sch) <= 64 && !g.out_cl && fits && mel_ws_lds_bytes(1024, sch.nseg, 2) <= 160 * 1024) {
+            r.stage_mode = KPR_OUT_MAGNITUDE;
+            r.product = PROD_WS;
+            r.ws_form = mel_ws_form(sch, true, g.K);
+        } else if (kr) {                       // e.g. channels_last output with several channels: |X| rows + banded product
+            r.stage_mode = KPR_OUT_MAGNITUDE;
+            r.product = PROD_BAND;
+        }
+    } else if (r.stage.fam == FAM_BIG && kr) {
+        // n_fft 4096 / 8192: |X| rows, then the banded product (a mel / log bank has ~2 K non-zeros: bandwidth work)
+        r.stage_mode = KPR_OUT_MAGNITUDE;
+        r.product = PROD_BAND;
+    }
+    return r;
+}
+
 int kpr_mel_f32(const float* x, const kpr_stft_geom* s, const float* window, const float* fb,
                 const float* fb_packed, int n_filt, const int32_t* fb_kranges_host,
                 const kpr_db_params* db, float* out, void* workspace, int64_t workspace_bytes,
@@ -2087,16 +2253,6 @@ int kpr_mel_f32(const float* x, const kpr_stft_geom* s, const float* window, con
     if (!workspace || workspace_bytes < need)
         return fail(KPR_E_WORKSPACE, "mel workspace: need %lld bytes", (long long)need);
     hipStream_t st = (hipStream_t)stream;
-    DbDev dbd = make_db(db);
-    unsigned* stats = reinterpret_cast<unsigned*>(workspace);
-    const int slots = dbd.enabled ? db_slots(s->batch) : 1;       // statistics slots per item (small batches, see DbDev)
-    if (dbd.enabled) {
-        dbd.slot_mask = slots - 1;
-        dbd.slot_stride = (int)(2 * s->batch);
-        hipLaunchKernelGGL(k_stats_init, dim3(grid_1d(s->batch * slots, 256)), dim3(256), 0, st, stats,
-                           (long long)s->batch * slots);
-        if (int e = launch_check("k_stats_init")) return e;
-    }
     MelSched sch{};
     const int sched_rc = get_sched(g.K, n_filt, fb_kranges_host, &sch);
     if (sched_rc != 0 && sched_rc != KPR_E_UNSUPPORTED) return sched_rc;          // malformed k-ranges etc.: report
@@ -2108,195 +2264,70 @@ int kpr_mel_f32(const float* x, const kpr_stft_geom* s, const float* window, con
         if (int e = verify_packed(fb_packed, g.K, n_filt, fb_kranges_host, sch, st, &pinfo)) return e;
         fb_packed += kPackHeaderFloats;
     }
-    const long long item_size = (long long)s->channels * F * n_filt;
-    // k_mel_pw (round 4): n_fft 256 ... 2048 with a band plan in the packed filterbank (mel / triangular banks) -- the
-    // default since round 4 (same-box sweeps against k_mel_ws / k_mel_ts / the ring kernel: tools/sweep_dispatch.py mel).
-    // mel_variant 5 / 6 / 7 = k_mel_pw with 8 / 4 / 16 waves per workgroup, 8 = its PAIR form where it applies (A/B runs, tests).
-    if (fb_packed && pinfo.band_off && (fused_nfft(s->n_fft) || s->n_fft == 256) && s->win_length <= s->n_fft &&
-        (int)pinfo.L * kPts == g.K - 1 &&
-        g.total_frames < 0x7fffff00LL && (opt(OPT_MEL_VARIANT) >= 5 || opt(OPT_MEL_VARIANT) == 0)) {
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        g.cfast = (g.in_cl && g.C > 1) ? 1 : 0;
-        // waves per workgroup: sixteen (one workgroup per CU, one copy of the tables, tickets shared by the whole CU) once
-        // there are sixteen tickets per CU; smaller launches are spread over more, smaller workgroups
-        int cus_w = 256;
-        if (int e = device_cus(&cus_w)) return e;
-        const long long tickets_w = (g.total_frames + (64 / (s->n_fft / 32)) - 1) / (64 / (s->n_fft / 32));
-        // (tools/sweep_dispatch.py mel, gpurun_out/r04i: 8-wave workgroups win from ~4 tickets per CU up -- 8.2 vs 9.1 us at
-        //  1328 tickets -- and 16-wave ones from 16 per CU: 14.8 vs 15.9 vs 17.6 us at 5312)
-        const int w_auto = tickets_w >= 16LL * cus_w ? 16 : tickets_w >= 4LL * cus_w ? 8 : 4;
-        const int w = opt(OPT_MEL_VARIANT) == 6 ? 4 : opt(OPT_MEL_VARIANT) == 7 ? 16 : opt(OPT_MEL_VARIANT) == 5 ? 8 : w_auto;
-        int rc;
-        // interleaved waveforms with an even channel count, launches that fill the chip: the PAIR form (kpr_mel_pw_kernels.h).
-        // n_fft 1024 stereo stays on the plain kernel (its stereo pair fetch does the same at four waves per SIMD).
-        // mel_variant 8 forces it wherever it applies (tests), 5 / 6 / 7 never take it.
-        const bool pair_ok = g.cfast && (g.C % 2) == 0 && (s->n_fft == 2048 || s->n_fft == 1024);
-        const bool pair_auto = pair_ok && (s->n_fft == 2048 || g.C >= 4) && tickets_w >= 24LL * cus_w;
-        if (pair_ok && (opt(OPT_MEL_VARIANT) == 8 || (opt(OPT_MEL_VARIANT) == 0 && pair_auto))) {
-            rc = s->n_fft == 2048 ? launch_mel_pw_pair<1024>(x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st)
-                                  : launch_mel_pw_pair<512>(x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st);
-            if (rc) return rc;
-            return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        }
-        switch (s->n_fft) {
-            case 256:  rc = launch_mel_pw_w<128>(w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st); break;
-            case 512:  rc = launch_mel_pw_w<256>(w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st); break;
-            case 1024: rc = launch_mel_pw_w<512>(w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st); break;
-            default:   rc = launch_mel_pw_w<1024>(w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st); break;
-        }
-        if (rc) return rc;
-        return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-    }
-    if (fused_nfft(s->n_fft) && fb_packed) {
-        // Banks WITHOUT a band plan (log-frequency banks, dense matrices) or a forced variant: the MFMA kernels.
-        // mel_variant: 0 = automatic, 2 = k_mel_ws with a streamed filterbank slice, 3 = k_mel_ws wherever it applies,
-        // 4 = the tile-synchronous kernel k_mel_ts wherever it applies (A/B runs, tests).  The round-1 4-wave ring kernel
-        // (k_mel_fused, mel_variant 1) lost on every shape of tools/sweep_dispatch.py (profiles/r05_sweep_before_prune.log:
-        // within 4 % of k_mel_ts on launches of a few thousand frames at n_fft 512, 25-95 % behind elsewhere) and was
-        // removed in round 5.
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        int rc;
-        const int cfast_in = g.cfast;
-        g.cfast = (g.in_cl && g.C > 1) ? 1 : 0;
-        // k_mel_ts: n_fft 512 (sweep, log-frequency bank: 38.6 vs 58.8 us on 256 x 1 s @22 kHz; 14.0 vs 13.4 on 16 clips),
-        // interleaved stereo at n_fft 1024 (pair fetch: 126 vs 180 us on 64 x 2 x 10 s @16 kHz), n_fft 1024 from ~12 k frames
-        // up (32-frame rounds: 6-9 % faster than k_mel_ws on 256 x 10 s @16 kHz); k_mel_ws for the rest of n_fft 1024 / 2048
-        const bool stereo_cl = g.in_cl && g.C == 2 && s->n_fft == 1024;
-        const bool long_1024 = s->n_fft == 1024 && g.total_frames >= 12288;
-        auto run_ts = [&](bool* taken) -> int {
-            *taken = false;
-            MelSchedTs sts;
-            // n_fft 512, long runs (>= 64 k frames, two 64-frame rounds per workgroup): 64-frame rounds, two tickets per wave
-            // (256 x 2 x 1 s @22 kHz, dB: 61 vs 65 us; 43 k frames mono: 29.7 vs 27.6, hence the threshold)
-            if (s->n_fft == 512 && g.total_frames >= 65536 && mel_ts_ok(s->n_fft, g.K, n_filt, fb_kranges_host, g, &sts, 64)) {
-                *taken = true;
-                return launch_mel_ts<256, 64>(x, g, window, tw, fb_packed, sts, dbd, stats, out, st);
-            }
-            if (!mel_ts_ok(s->n_fft, g.K, n_filt, fb_kranges_host, g, &sts)) return 0;
-            *taken = true;
-            switch (s->n_fft) {
-                case 512:  return launch_mel_ts<256>(x, g, window, tw, fb_packed, sts, dbd, stats, out, st);
-                case 1024: return launch_mel_ts<512>(x, g, window, tw, fb_packed, sts, dbd, stats, out, st);
-                default:   return launch_mel_ts<1024>(x, g, window, tw, fb_packed, sts, dbd, stats, out, st);
-            }
-        };
-        bool taken = false;
-        if (opt(OPT_MEL_VARIANT) == 4 || (opt(OPT_MEL_VARIANT) == 0 && (s->n_fft == 512 || stereo_cl || long_1024))) {
-            if ((rc = run_ts(&taken))) return rc;
-            if (taken) return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        }
-        int slice_max = 0;      // the consumers keep one lane of schedule per chunk of their slice
-        for (int i = 0; i < 4; ++i) slice_max = std::max(slice_max, (int)sch.wave_nchunks[i]);
-        if ((s->n_fft == 2048 || s->n_fft == 1024) && slice_max <= 64 &&
-            g.total_frames < 0x7fffff00LL && mel_ws_lds_bytes(s->n_fft / 2, sch.nseg) <= 160 * 1024) {
-            rc = (s->n_fft == 2048)
-                     ? launch_mel_ws<1024>(x, g, window, tw, fb_packed, sch, dbd, stats, out, st)
-                     : launch_mel_ws<512>(x, g, window, tw, fb_packed, sch, dbd, stats, out, st);
-            if (rc) return rc;
-            return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        }
-        // what k_mel_ws cannot take (very wide banks): k_mel_ts if its schedule holds the bank, else the two-launch path below
-        if ((rc = run_ts(&taken))) return rc;
-        if (taken) return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        g.cfast = cfast_in;
-    }
-    // n_fft 256 (round 3): the tile-synchronous kernel takes it too (eight lanes per frame, 64-frame rounds); mel_variant 3
-    // keeps the two-launch path
-    if (fb_packed && s->n_fft == 256 && s->win_length <= s->n_fft && opt(OPT_MEL_VARIANT) != 3) {
-        MelSchedTs sts;
-        Geom gt = g;
-        gt.cfast = (g.in_cl && g.C > 1) ? 1 : 0;
-        if (mel_ts_ok(s->n_fft, g.K, n_filt, fb_kranges_host, gt, &sts)) {
-            const float2* tw = nullptr;
-            if (int e = get_twiddles(s->n_fft, &tw)) return e;
-            if (int e = launch_mel_ts<128>(x, gt, window, tw, fb_packed, sts, dbd, stats, out, st)) return e;
-            return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        }
-    }
-    // mixed-radix sizes (n_fft 400, 320, 640 ...: speech front ends): one launch as well (k_mel_mr);
-    // kpr_set_option("mel_variant", 3) keeps the two-launch path of round 2 (A/B runs, tests)
-    if (fb_packed && mel_mr_nfft(s->n_fft) && opt(OPT_MIXED_RADIX) && s->win_length <= s->n_fft &&
-        opt(OPT_MEL_VARIANT) != 3) {
-        bool taken = false;
-        Geom gm = g;
-        gm.cfast = (g.in_cl && g.C > 1) ? 1 : 0;  // channel-fastest frame numbering: the C frames that share cache lines sit in one wave
-        if (int e = launch_mel_mr(x, gm, window, fb_packed, fb_kranges_host, n_filt, dbd, stats, out, st, &taken)) return e;
-        if (taken) return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-    }
-    // two-kernel path: STFT (complex, frame-contiguous) -> (|.| x filterbank) GEMM [+ dB]
-    {
-        const int64_t need2 = stats_region_bytes(s->batch) +
-                              (int64_t)sizeof(float) * 2 * g.total_frames * g.K;
-        if (workspace_bytes < need2)
-            return fail(KPR_E_WORKSPACE, "mel workspace (unpacked filterbank path): need %lld bytes",
-                        (long long)need2);
-    }
-    float* spec = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) +
-                                           stats_region_bytes(s->batch));
-    if (fast_nfft(s->n_fft)) {   // Stockham STFT (n_fft = 256, or no packed filterbank given)
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        Geom gc = g;
-        gc.out_cl = 0;
-        int rc;
-        switch (s->n_fft) {
-            case 256:  rc = launch_stft_fast<128>(x, gc, window, tw, KPR_OUT_COMPLEX, spec, st); break;
-            case 512:  rc = launch_stft_fast<256>(x, gc, window, tw, KPR_OUT_COMPLEX, spec, st); break;
-            case 1024: rc = launch_stft_fast<512>(x, gc, window, tw, KPR_OUT_COMPLEX, spec, st); break;
-            default:   rc = launch_stft_fast<1024>(x, gc, window, tw, KPR_OUT_COMPLEX, spec, st); break;
-        }
-        if (rc) return rc;
-    } else if (bluestein_ok(s)) {   // even non-power-of-two n_fft: chirp-z STFT, frame-contiguous
-        Geom gc = g;
-        gc.out_cl = 0;
-        // wide packed filterbank: |X| rows straight into the fused kernel's MFMA consumers
-        // (loader producers, FROM_MAG) instead of the complex spectrum + generic GEMM
-        int slice_max = 0;
-        for (int i = 0; i < 4; ++i) slice_max = std::max(slice_max, (int)sch.wave_nchunks[i]);
-        if (fb_packed && g.K <= 1025 && slice_max <= 64 && !g.out_cl &&
-            g.total_frames < 0x7fffff00LL && mel_ws_lds_bytes(1024, sch.nseg, 2) <= 160 * 1024) {
-            if (int e = launch_stft_bs(x, gc, window, KPR_OUT_MAGNITUDE, spec, st)) return e;
-            if (int e = launch_mel_ws<1024, true>(spec, g, nullptr, nullptr, fb_packed, sch, dbd, stats, out, st))
-                return e;
-            return dbd.enabled ? db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots) : 0;
-        }
-        if (fb_kranges_host) {           // e.g. channels_last output with several channels: |X| rows + banded product
-            if (int e = launch_stft_bs(x, gc, window, KPR_OUT_MAGNITUDE, spec, st)) return e;
-            return run_band_mel(spec, g, fb, sch, dbd, stats, out, s->batch, item_size, st);
-        }
-        if (int e = launch_stft_bs(x, gc, window, KPR_OUT_COMPLEX, spec, st)) return e;
-    } else if (big_nfft(s->n_fft) && s->win_length <= s->n_fft) {   // n_fft 4096 / 8192: FFT kernel, frame-contiguous
-        Geom gc = g;
-        gc.out_cl = 0;
-        if (fb_kranges_host) {
-            // |X| rows, then the banded product (a mel / log bank has ~2 K non-zeros: bandwidth work)
-            if (int e = launch_stft_big(x, gc, window, KPR_OUT_MAGNITUDE, spec, st)) return e;
-            return run_band_mel(spec, g, fb, sch, dbd, stats, out, s->batch, item_size, st);
-        }
-        if (int e = launch_stft_big(x, gc, window, KPR_OUT_COMPLEX, spec, st)) return e;
-    } else if (gen_ok_f32(s)) {
-        Geom gc = g;
-        gc.out_cl = 0;
-        if (int e = launch_stft_gen_f32(x, gc, window, KPR_OUT_COMPLEX, spec, st)) return e;
-    } else {
-        if (int e = stft_gemm(x, s, g, window, spec, true, st)) return e;
-    }
-    GemmArgs ga{};
-    ga.in = frames_contig_map(g, g.K);
-    ga.out = frames_out_map(g, n_filt);
-    ga.Kdim = g.K; ga.N = n_filt; ga.ldb = n_filt;
-    ga.db = dbd; ga.stats = stats;
-    if (fb_kranges_host) {
-        ga.has_kr = 1;
-        for (int t = 0; t < sch.ntiles; ++t) { ga.klo[t] = sch.klo[t]; ga.khi[t] = sch.khi[t]; }
-    }
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const MelRoute r = mel_route(s, g, n_filt, blob != nullptr, pinfo, sch, fb_kranges_host, out, cus);
+    if (workspace_bytes < r.workspace)
+        return fail(KPR_E_WORKSPACE, "mel workspace (unpacked filterbank path): need %lld bytes", (long long)r.workspace);
+    DbDev dbd = make_db(db);
+    unsigned* stats = reinterpret_cast<unsigned*>(workspace);
+    const int slots = dbd.enabled ? db_slots(s->batch) : 1;       // statistics slots per item (small batches, see DbDev)
     if (dbd.enabled) {
-        if (int e = run_gemm<A_CABS, E_DB>(spec, fb, ga, out, st)) return e;
-        return db_clamp(out, s->batch, item_size, dbd.dyn, stats, st, slots);
+        dbd.slot_mask = slots - 1;
+        dbd.slot_stride = (int)(2 * s->batch);
+        hipLaunchKernelGGL(k_stats_init, dim3(grid_1d(s->batch * slots, 256)), dim3(256), 0, st, stats,
+                           (long long)s->batch * slots);
+        if (int e = launch_check("k_stats_init")) return e;
     }
-    return run_gemm<A_CABS, E_PLAIN>(spec, fb, ga, out, st);
+    g.cfast = r.cfast;
+    const float2* tw = nullptr;
+    if (r.fam != MEL_STAGED)
+        if (int e = get_twiddles(s->n_fft, &tw)) return e;
+    auto run = [&]() -> int {
+        switch (r.fam) {
+            case MEL_PW:
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    return launch_mel_pw_w<nc>(r.w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st);
+                });
+            case MEL_PW_PAIR:
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    if constexpr (nc >= 512) return launch_mel_pw_pair<nc>(x, g, window, tw, blob, pinfo, n_filt, r.cl_slots, dbd, stats, out, st);
+                    else return no_instance("k_mel_pw_pair");
+                });
+            case MEL_TS:
+                if (r.rf64) return launch_mel_ts<256, 64>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    return launch_mel_ts<nc>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                });
+            case MEL_WS:
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    if constexpr (nc >= 512) return launch_mel_ws<nc>(r.ws_form, x, g, window, tw, fb_packed, sch, dbd, stats, out, st);
+                    else return no_instance("k_mel_ws");
+                });
+            case MEL_MR:
+                return with_mr(s->n_fft, [&](auto ff) {
+                    return launch_mel_mr_inst<typename decltype(ff)::type>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                });
+        }
+        float* spec = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + stats_region_bytes(s->batch));
+        Geom gc = g;
+        gc.out_cl = 0;
+        if (int e = launch_stft(r.stage, x, gc, window, r.stage_mode, spec, cus, st)) return e;
+        if (r.product == PROD_WS) return launch_mel_ws<1024, true>(r.ws_form, spec, g, nullptr, nullptr, fb_packed, sch, dbd, stats, out, st);
+        if (r.product == PROD_BAND) return run_band_mel(spec, g, fb, sch, dbd, stats, out, st);
+        GemmArgs ga{};
+        ga.in = frames_contig_map(g, g.K);
+        ga.out = frames_out_map(g, n_filt);
+        ga.Kdim = g.K; ga.N = n_filt; ga.ldb = n_filt;
+        ga.db = dbd; ga.stats = stats;
+        if (fb_kranges_host) {
+            ga.has_kr = 1;
+            for (int t = 0; t < sch.ntiles; ++t) { ga.klo[t] = sch.klo[t]; ga.khi[t] = sch.khi[t]; }
+        }
+        return dbd.enabled ? run_gemm<A_CABS, E_DB>(spec, fb, ga, out, st) : run_gemm<A_CABS, E_PLAIN>(spec, fb, ga, out, st);
+    };
+    if (int e = run()) return e;
+    return dbd.enabled ? db_clamp(out, s->batch, (long long)s->channels * F * n_filt, dbd.dyn, stats, st, slots) : 0;
 }
 
 int kpr_filterbank_kranges(const float* fb_host, int n_freq, int n_filt, int32_t* out_host) {
@@ -2337,6 +2368,9 @@ int kpr_angle_c64(const void* x, int64_t n, float* out, kpr_stream_t stream) {
     return launch_check("k_cplx_to_real");
 }
 
+// narrow matrices (LogmelToMFCC's DCT, small filterbanks) on contiguous rows of a multiple of four floats: the thin GEMM
+static bool thin_gemm_shape(int n_freq, int n_filt) { return (n_filt + 15) / 16 <= 4 && n_freq <= 512 && (n_freq & 3) == 0; }
+
 int kpr_apply_filterbank_f32(const float* x, int64_t batch, int channels, int64_t frames,
                              int n_freq, int layout, const float* fb, int n_filt,
                              const int32_t* fb_kranges_host, float* out, kpr_stream_t stream) {
@@ -2349,9 +2383,8 @@ int kpr_apply_filterbank_f32(const float* x, int64_t batch, int channels, int64_
     if (!x || !fb || !out) return fail(KPR_E_BADARG, "x / fb / out must not be NULL");
     const int ntiles = (n_filt + 15) / 16;
     if (ntiles > kMaxTiles || n_freq > 32000) fb_kranges_host = nullptr;   // GemmArgs holds 16-bit k-ranges for 64 tiles: dense product
-    // narrow matrices on contiguous rows (LogmelToMFCC's DCT, small filterbanks): the thin GEMM
     const bool contiguous = layout == KPR_CHANNELS_FIRST || channels == 1;
-    if (contiguous && ntiles <= 4 && n_freq <= 512 && (n_freq & 3) == 0 && (((uintptr_t)x) & 15) == 0) {
+    if (contiguous && thin_gemm_shape(n_freq, n_filt) && (((uintptr_t)x) & 15) == 0) {
         const size_t lds = sizeof(float) * 4 * 64 * (size_t)ntiles * ((n_freq + 15) / 16);
         const unsigned grid = (unsigned)std::min<long long>((rows + 63) / 64, 256 * 8);
         hipStream_t st = (hipStream_t)stream;
@@ -2388,6 +2421,43 @@ int kpr_apply_filterbank_f32(const float* x, int64_t batch, int channels, int64_
     return run_gemm<A_PLAIN, E_PLAIN>(x, fb, ga, out, (hipStream_t)stream);
 }
 
+// the Geom of a row product: `rows` rows of n_freq bins, interleaved = channel-fastest rows (channels_last, C > 1)
+static Geom rows_geom(long long rows, long long frames, int channels, int n_freq, bool interleaved) {
+    Geom g{};
+    g.total_frames = rows; g.T = 0; g.F = (int)frames; g.C = channels;
+    g.n_fft = 2 * (n_freq - 1); g.win = 0; g.hop = 0; g.pad_left = 0; g.K = n_freq;
+    g.in_cl = 0; g.out_cl = interleaved ? 1 : 0; g.cfast = interleaved ? 1 : 0;
+    geom_set_magic(g);
+    return g;
+}
+
+enum { FB_PW, FB_WS, FB_BAND, FB_UNPACKED };      // FB_UNPACKED: kpr_apply_filterbank_f32 (thin GEMM or generic GEMM)
+
+// calls whose packed filterbank is verified (get_sched + verify_packed) ahead of fb_route
+static bool fb_packed_candidate(const float* x, const float* fb_packed, const float* out, long long rows, int n_freq, int n_filt) {
+    return fb_packed && x && out && rows > 0 && rows < 0x7fffff00LL && n_freq <= 1025 && !thin_gemm_shape(n_freq, n_filt);
+}
+// verified: the packed header was verified (pi, sch); band_sch: the schedule FB_BAND runs with
+static int fb_route(bool verified, const PackInfo& pi, const MelSched& sch, const float* x, const float* fb, const float* out,
+                    long long rows, int channels, int n_freq, int n_filt, bool contiguous, const int32_t* kr, MelSched* band_sch) {
+    if (verified) {
+        // a bank with a band plan (mel / triangular banks; n_freq - 1 a multiple of four up to 1024: every even n_fft / 4): the banded
+        // row kernel (round 6; 21 248 x 1025 -> 128: k_mel_ws 35 / 41 us, this one 19 / 25 -- same buffers / rotating) on contiguous rows
+        // and on rows of TWO interleaved channels (channels_last stereo: the ST instances; 10 624 blocks of 1025 bins: 38 / 44 ->
+        // 25 / 30 us, a single-block launch 8.1 -> 6.9).  More channels stay on the MFMA kernels (kpr_fb_pw_kernels.h).
+        // fb_variant 1 = never (A/B runs, tests).
+        if (pi.band_off && fb && (contiguous || channels == 2) && opt(OPT_FB_VARIANT) != 1 && pi.L >= 8 && pi.L <= 64) return FB_PW;
+        // (channels_last with C > 1: the loader waves read rows strided by C, channel-fastest row order)
+        if (slice_max(sch) <= 64 && mel_ws_lds_bytes(1024, sch.nseg, 2) <= 160 * 1024) return FB_WS;
+    }
+    // long contiguous rows of a banded matrix (K = 2049 / 4097 bins after an n_fft 4096 / 8192 STFT: beyond the
+    // MFMA consumers' tile): the banded product instead of the generic GEMM
+    if (x && out && fb && contiguous && rows > 0 && rows < 0x7fffff00LL && n_freq > 1025 && kr &&
+        sizeof(float) * (size_t)kBandRows * n_freq <= 160 * 1024 && get_sched(n_freq, n_filt, kr, band_sch) == 0)
+        return FB_BAND;
+    return FB_UNPACKED;
+}
+
 int kpr_apply_filterbank_packed_f32(const float* x, int64_t batch, int channels, int64_t frames,
                                     int n_freq, int layout, const float* fb, const float* fb_packed,
                                     int n_filt, const int32_t* fb_kranges_host, float* out,
@@ -2398,50 +2468,27 @@ int kpr_apply_filterbank_packed_f32(const float* x, int64_t batch, int channels,
     if ((unsigned)layout > 1u) return fail(KPR_E_BADARG, "bad layout enum");
     const long long rows = batch * channels * frames;
     const bool contiguous = layout == KPR_CHANNELS_FIRST || channels == 1;
+    hipStream_t st = (hipStream_t)stream;
     MelSched sch{};
-    // (channels_last with C > 1: the loader waves read rows strided by C, channel-fastest row order)
-    if (fb_packed && x && out && rows > 0 && rows < 0x7fffff00LL && n_freq <= 1025 &&
-        // (narrow matrices on rows of a multiple of four floats: the thin GEMM of kpr_apply_filterbank_f32)
-        (n_filt > 64 || n_freq > 512 || (n_freq & 3)) && get_sched(n_freq, n_filt, fb_kranges_host, &sch) == 0) {
-        PackInfo pinfo{0, 0, 0, 0, 0};
-        if (int e = verify_packed(fb_packed, n_freq, n_filt, fb_kranges_host, sch, (hipStream_t)stream, &pinfo)) return e;
-        // a bank with a band plan (mel / triangular banks; n_freq - 1 a multiple of four up to 1024: every even n_fft / 4): the banded
-        // row kernel (round 6; 21 248 x 1025 -> 128: k_mel_ws 35 / 41 us, this one 19 / 25 -- same buffers / rotating) on contiguous rows
-        // and on rows of TWO interleaved channels (channels_last stereo: the ST instances; 10 624 blocks of 1025 bins: 38 / 44 ->
-        // 25 / 30 us, a single-block launch 8.1 -> 6.9).  More channels stay on the MFMA kernels (kpr_fb_pw_kernels.h).
-        // fb_variant 1 = never (A/B runs, tests).
-        if (pinfo.band_off && fb && (contiguous || channels == 2) && opt(OPT_FB_VARIANT) != 1 && pinfo.L >= 8 && pinfo.L <= 64) {
-            hipStream_t st = (hipStream_t)stream;
-            if (contiguous) return launch_fb_pw_l<false>((int)pinfo.L, x, rows, n_freq, fb_packed, pinfo, n_filt, fb, out, st);
-            return launch_fb_pw_l<true>((int)pinfo.L, x, rows / 2, n_freq, fb_packed, pinfo, n_filt, fb, out, st);
-        }
-        fb_packed += kPackHeaderFloats;
-        int slice_max = 0;
-        for (int i = 0; i < 4; ++i) slice_max = std::max(slice_max, (int)sch.wave_nchunks[i]);
-        if (slice_max <= 64 && mel_ws_lds_bytes(1024, sch.nseg, 2) <= 160 * 1024) {
-            Geom g{};
-            g.total_frames = rows; g.T = 0; g.F = (int)frames; g.C = channels;
-            g.n_fft = 2 * (n_freq - 1); g.win = 0; g.hop = 0; g.pad_left = 0; g.K = n_freq;
-            g.in_cl = 0; g.out_cl = contiguous ? 0 : 1; g.cfast = contiguous ? 0 : 1;
-            geom_set_magic(g);
-            DbDev dbd = make_db(nullptr);
-            return launch_mel_ws<1024, true>(x, g, nullptr, nullptr, fb_packed, sch, dbd, nullptr, out,
-                                             (hipStream_t)stream);
-        }
+    PackInfo pinfo{0, 0, 0, 0, 0};
+    const bool verified = fb_packed_candidate(x, fb_packed, out, rows, n_freq, n_filt) &&
+                          get_sched(n_freq, n_filt, fb_kranges_host, &sch) == 0;
+    if (verified)
+        if (int e = verify_packed(fb_packed, n_freq, n_filt, fb_kranges_host, sch, st, &pinfo)) return e;
+    switch (fb_route(verified, pinfo, sch, x, fb, out, rows, channels, n_freq, n_filt, contiguous, fb_kranges_host, &sch)) {
+        case FB_PW:
+            return with_pow2((int)pinfo.L * kPts, [&](auto nc) {
+                return contiguous ? launch_fb_pw<nc, false>(x, rows, n_freq, fb_packed, pinfo, n_filt, fb, out, st)
+                                  : launch_fb_pw<nc, true>(x, rows / 2, n_freq, fb_packed, pinfo, n_filt, fb, out, st);
+            });
+        case FB_WS:
+            return launch_mel_ws<1024, true>(mel_ws_form(sch, true, n_freq), x, rows_geom(rows, frames, channels, n_freq, !contiguous),
+                                             nullptr, nullptr, fb_packed + kPackHeaderFloats, sch, make_db(nullptr), nullptr, out, st);
+        case FB_BAND:
+            return run_band_mel(x, rows_geom(rows, frames, channels, n_freq, false), fb, sch, make_db(nullptr), nullptr, out, st);
+        default:
+            return kpr_apply_filterbank_f32(x, batch, channels, frames, n_freq, layout, fb, n_filt, fb_kranges_host, out, stream);
     }
-    // long contiguous rows of a banded matrix (K = 2049 / 4097 bins after an n_fft 4096 / 8192 STFT: beyond the
-    // MFMA consumers' tile): the banded product instead of the generic GEMM
-    if (x && out && fb && contiguous && rows > 0 && rows < 0x7fffff00LL && n_freq > 1025 && fb_kranges_host &&
-        sizeof(float) * (size_t)kBandRows * n_freq <= 160 * 1024 && get_sched(n_freq, n_filt, fb_kranges_host, &sch) == 0) {
-        Geom g{};
-        g.total_frames = rows; g.T = 0; g.F = (int)frames; g.C = channels;
-        g.n_fft = 2 * (n_freq - 1); g.win = 0; g.hop = 0; g.pad_left = 0; g.K = n_freq;
-        g.in_cl = 0; g.out_cl = 0; g.cfast = 0;
-        geom_set_magic(g);
-        return run_band_mel(x, g, fb, sch, make_db(nullptr), nullptr, out, batch, 0, (hipStream_t)stream);
-    }
-    return kpr_apply_filterbank_f32(x, batch, channels, frames, n_freq, layout, fb, n_filt, fb_kranges_host,
-                                    out, stream);
 }
 
 int64_t kpr_db_workspace_bytes(int64_t n_items) {
@@ -2485,6 +2532,31 @@ int64_t kpr_istft_workspace_bytes(const kpr_stft_geom* s, int64_t n_frames) {
     return 256 + (int64_t)sizeof(float) * s->batch * s->channels * n_frames * s->win_length;
 }
 
+// F: frames per signal, g: the call's Geom, out: the waveform (alignment of the overlap-add stores)
+static IstftRoute istft_route(const kpr_stft_geom* s, long long F, const Geom& g, const float* out, int cus) {
+    IstftRoute r{};
+    const int path = opt(OPT_ISTFT_PATH);
+    if (fast_nfft(s->n_fft) && path != 2) {
+        // fused irFFT + window + overlap-add (no workspace traffic) whenever the frames overlap.
+        // Launches of a few thousand frames -- batch 1 ... 8 of clips, the serving case -- are latency bound and the
+        // barrier kernel (many small workgroups, one barrier) beats the ring kernel's serial walk over short segments:
+        // 4 x 434 frames at n_fft 1024 12.0 vs 15.2 us, 16 x 83 at n_fft 2048 16.0 vs 20.3, 16 x 61 at n_fft 512 8.0 vs
+        // 9.1; from ~3.5 k frames up the ring kernel wins (16 x 434: 20.0 vs 24.4; cfg4: 77 vs 122)
+        // (tools/kbench_istft_variants.py; kpr_set_option("istft_path", 3) = the ring kernel whatever the size).
+        const bool small = path == 0 && g.total_frames <= 3072;
+        // k_istft_pw (round 4): hop = n_fft / 8, / 4, / 2, launches that fill the chip (istft_path 4 = wherever it applies)
+        if (((path == 0 && !small) || path == 4) && s->n_fft >= 512 && istft_pw_plan(s, F, cus, &r)) return r;
+        // the wave-specialised ring kernel when its preconditions hold, then the barrier kernel
+        if (!small && istft_ring_plan(s, F, out, cus, &r)) return r;
+        if (istft_fused_plan(s, F, out, cus, &r)) return r;
+        if (small && istft_ring_plan(s, F, out, cus, &r)) return r;   // the barrier kernel did not apply (no overlap ...): the ring kernel may
+    }
+    // n_fft = 2^a 5^b ...: the ring kernel with mixed-radix producers
+    if (!fast_nfft(s->n_fft) && path != 2 && istft_ws_mr_plan(s, F, out, cus, &r)) return r;
+    r.fam = fft_family(s);
+    return r;
+}
+
 int kpr_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_frames,
                   const float* synth_window, float* out, void* workspace, int64_t workspace_bytes,
                   kpr_stream_t stream) {
@@ -2500,79 +2572,36 @@ int kpr_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_frames,
         return fail(KPR_E_WORKSPACE, "istft workspace: need %lld bytes", (long long)need);
     hipStream_t st = (hipStream_t)stream;
     float* frames = reinterpret_cast<float*>(workspace);
-    if (fast_nfft(s->n_fft) && opt(OPT_ISTFT_PATH) != 2) {
-        // fused irFFT + window + overlap-add (no workspace traffic) whenever the frames overlap
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const IstftRoute r = istft_route(s, n_frames, g, out, cus);
+    const float2* sp = (const float2*)spec;
+    if (r.fam >= IST_PW) {
+        if (r.fam == IST_WS_MR) return launch_istft_ws_mr(sp, r, s->n_fft, synth_window, out, st);
         const float2* tw = nullptr;
         if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        bool launched = false;
-        int rc = 0;
-        // Launches of a few thousand frames -- batch 1 ... 8 of clips, the serving case -- are latency bound and the
-        // barrier kernel (many small workgroups, one barrier) beats the ring kernel's serial walk over short segments:
-        // 4 x 434 frames at n_fft 1024 12.0 vs 15.2 us, 16 x 83 at n_fft 2048 16.0 vs 20.3, 16 x 61 at n_fft 512 8.0 vs
-        // 9.1; from ~3.5 k frames up the ring kernel wins (16 x 434: 20.0 vs 24.4; cfg4: 77 vs 122)
-        // (tools/kbench_istft_variants.py; kpr_set_option("istft_path", 3) = the ring kernel whatever the size).
-        const bool small = opt(OPT_ISTFT_PATH) == 0 && g.total_frames <= 3072;
-        auto ring = [&]() {      // wave-specialised ring kernel when its preconditions hold
-            switch (s->n_fft) {
-                case 256:  return launch_istft_ws<128>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched);
-                case 512:  return launch_istft_ws<256>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched);
-                case 1024: return launch_istft_ws<512>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched);
-                default:   return launch_istft_ws<1024>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched);
-            }
-        };
-        // k_istft_pw (round 4): hop = n_fft / 8, / 4, / 2, launches that fill the chip (istft_path 4 = wherever it applies)
-        if ((opt(OPT_ISTFT_PATH) == 0 && !small) || opt(OPT_ISTFT_PATH) == 4) {
-            switch (s->n_fft) {
-                case 512:  rc = launch_istft_pw<256>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-                case 1024: rc = launch_istft_pw<512>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-                case 2048: rc = launch_istft_pw<1024>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-                default:   rc = 0; break;
-            }
-            if (rc) return rc;
-            if (launched) return 0;
-        }
-        if (!small) {
-            rc = ring();
-            if (rc) return rc;
-            if (launched) return 0;
-        }
-        switch (s->n_fft) {
-            case 256:  rc = launch_istft_fused<128, 4>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-            case 512:  rc = launch_istft_fused<256, 4>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-            case 1024: rc = launch_istft_fused<512, 4>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-            default:   rc = launch_istft_fused<1024, 8>((const float2*)spec, s, n_frames, synth_window, tw, out, st, &launched); break;
-        }
-        if (rc) return rc;
-        if (launched) return 0;
-        if (small) {             // the barrier kernel did not apply (no overlap ...): the ring kernel may
-            rc = ring();
-            if (rc) return rc;
-            if (launched) return 0;
-        }
+        return with_pow2(s->n_fft / 2, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            if (r.fam == IST_WS) return launch_istft_ws<NC>(sp, r, synth_window, tw, out, st);
+            if (r.fam == IST_FUSED) return launch_istft_fused<NC, NC == 1024 ? 8 : 4>(sp, r, synth_window, tw, out, st);
+            if constexpr (NC >= 256) return launch_istft_pw<NC>(sp, r, synth_window, tw, out, st);
+            else return no_instance("k_istft_pw");
+        });
     }
-    if (!fast_nfft(s->n_fft) && opt(OPT_ISTFT_PATH) != 2) {
-        // n_fft = 2^a 5^b: the ring kernel with mixed-radix producers
-        bool launched = false;
-        if (int e = launch_istft_ws_mr((const float2*)spec, s, n_frames, synth_window, out, st, &launched)) return e;
-        if (launched) return 0;
-    }
-    if (fast_nfft(s->n_fft)) {
+    // two-kernel path: irFFT + synthesis window into the workspace, then the overlap-add
+    if (r.fam == FAM_POW2) {
         const float2* tw = nullptr;
         if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        int rc;
-        switch (s->n_fft) {
-            case 256:  rc = launch_irfft_fast<128>((const float2*)spec, g, synth_window, tw, frames, st); break;
-            case 512:  rc = launch_irfft_fast<256>((const float2*)spec, g, synth_window, tw, frames, st); break;
-            case 1024: rc = launch_irfft_fast<512>((const float2*)spec, g, synth_window, tw, frames, st); break;
-            default:   rc = launch_irfft_fast<1024>((const float2*)spec, g, synth_window, tw, frames, st); break;
-        }
-        if (rc) return rc;
-    } else if (bluestein_ok(s)) {     // even non-power-of-two n_fft: inverse chirp-z, then the gather
-        if (int e = launch_irfft_bs((const float2*)spec, g, synth_window, frames, st)) return e;
-    } else if (big_nfft(s->n_fft)) {  // 4096 / 8192: sub-FFT kernel, then the gather
-        if (int e = launch_irfft_big((const float2*)spec, g, synth_window, frames, st)) return e;
-    } else if (gen_ok_f32(s)) {       // small prime factors: run-time mixed-radix inverse FFT, then the gather
-        if (int e = launch_irfft_gen_f32((const float2*)spec, g, synth_window, frames, st)) return e;
+        if (int e = with_pow2(s->n_fft / 2, [&](auto nc) { return launch_irfft_fast<nc>(sp, g, synth_window, tw, frames, st); }))
+            return e;
+    } else if (r.fam == FAM_MR) {     // n_fft with a mixed-radix plan: one N-point inverse FFT per frame
+        if (int e = launch_irfft_mr(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_BS) {     // even non-power-of-two n_fft: inverse chirp-z, then the gather
+        if (int e = launch_irfft_bs(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_BIG) {    // 4096 / 8192: sub-FFT kernel, then the gather
+        if (int e = launch_irfft_big(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_GEN) {    // small prime factors: run-time mixed-radix inverse FFT, then the gather
+        if (int e = launch_irfft_gen_f32(sp, g, synth_window, frames, st)) return e;
     } else {
         const float* idft = nullptr;
         if (int e = get_dft_inv(s->n_fft, &idft)) return e;
