@@ -312,12 +312,17 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
 #define PW_STAMP() do { (void)dbg; } while (0)
 #endif
     PW_STAMP();
-    // the header words of the blob, requested first (scalar loads; compared before the first table access, below)
+    // the header words of the blob, requested first (scalar loads; compared before the first table access, below) -- except in
+    // the one-frame-per-ticket instance (HDR_LATE), which requests them after its first samples: requested first, the first
+    // sample request waited for this dependent round trip (kernel arguments -> header) as well.  (The other instances keep the
+    // early request: measured 0.5 % slower on cfg5 / n_fft 512 with the late one, and PAIR spilled two more SGPRs.)
+    constexpr bool HDR_LATE = !PAIR && G == 1;
     typedef const unsigned __attribute__((address_space(4)))* ConstU32;
     unsigned long long hdra = (unsigned long long)pl.hdr;
     asm volatile("" : "+s"(hdra));
-    const unsigned h6 = ((ConstU32)hdra)[6], h7 = ((ConstU32)hdra)[7], h8 = ((ConstU32)hdra)[8], h9 = ((ConstU32)hdra)[9],
-                   h10 = ((ConstU32)hdra)[10];
+    const unsigned h6 = HDR_LATE ? 0u : ((ConstU32)hdra)[6], h7 = HDR_LATE ? 0u : ((ConstU32)hdra)[7],
+                   h8 = HDR_LATE ? 0u : ((ConstU32)hdra)[8], h9 = HDR_LATE ? 0u : ((ConstU32)hdra)[9],
+                   h10 = HDR_LATE ? 0u : ((ConstU32)hdra)[10];
 
     float* rows = smem;                                                   // [W * G][RWD]
     float* tab = smem + W * G * RWD;                                      // P | WN | T2 (as in the section, after T1)
@@ -344,6 +349,34 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
     // ---- prologue: everything is REQUESTED before anything is used (one cold memory latency, not four in a row) ------
     auto fetch_ticket = [&](int tk, int lane_, f2 (&dst)[kPts]) -> bool {   // tk = ticket of this workgroup, wave-uniform
         bool sw = false;
+        if constexpr (G == 1) {
+            // One frame per ticket on contiguous rows, frames numbered (b C + c) F + f (one channel, or channels_first input with
+            // that numbering): frame gf starts at element (gf / F) T + (gf % F) hop - pad_left.  Its whole geometry is
+            // wave-uniform -- 32-bit scalar arithmetic (the launcher keeps total_frames below 2^31, check_geom T below 2^30), no
+            // 64-bit vector compares -- and each request is an SGPR base (one per 4 KiB half of the frame), the lane's offset and
+            // an immediate.  Edge frames and the other layouts take the general path below.  (The layout test is a few scalar
+            // compares of kernel arguments; a host-side flags word in PwPlan moved the kernel arguments of every k_mel_pw
+            // instance and cost the n_fft 1024 ones three SGPR spills and ~1 % on cfg5.)
+            if (tk < n_wg && (g.C == 1 || (!g.in_cl && !g.cfast))) {
+                const unsigned gf = (unsigned)(t_wg0 + tk);
+                const unsigned bc = magic_div(gf, g.mF, g.sF);
+                const int s0 = (int)(gf - bc * (unsigned)g.F) * g.hop - g.pad_left;
+                if (gf < (unsigned)g.total_frames && s0 >= 0 && s0 + 2 * NC <= (int)g.T) {
+                    typedef const char __attribute__((address_space(1)))* GlobalB;
+                    typedef const float __attribute__((address_space(1)))* GlobalF;
+                    unsigned long long b0 = (unsigned long long)(x + ((long long)bc * g.T + s0));
+                    unsigned long long b1 = b0 + 8 * (kPts / 2) * L;
+                    asm volatile("" : "+s"(b0), "+s"(b1));           // (two scalar bases: the offsets stay immediates)
+                    const unsigned lo = 8u * (unsigned)(lane_ & (L - 1));
+#pragma unroll
+                    for (int m = 0; m < kPts; ++m) {
+                        const GlobalB p = (GlobalB)(m < kPts / 2 ? b0 : b1) + lo + 8 * L * (m % (kPts / 2));
+                        dst[m] = f2{((GlobalF)p)[0], ((GlobalF)p)[1]};   // (one dwordx2)
+                    }
+                    return false;
+                }
+            }
+        }
         if (tk < n_wg) {
             const int fl_ = lane_ & (L - 1), grp_ = (G == 1) ? 0 : lane_ / L;
             const long long gf = (long long)(t_wg0 + tk) * G;
@@ -352,8 +385,12 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
             if constexpr (L == 16 || L == 32) fetch_frame_z<NC>(x, g, p, v, fl_, dst, lane_, &sw);
             else fetch_frame_z<NC>(x, g, p, v, fl_, dst);
         } else {
+            // (G = 1: zeros written in this branch only -- as plain constants hipcc hoisted 32 v_mov into the path of every request)
 #pragma unroll
-            for (int m = 0; m < kPts; ++m) dst[m] = f2{0.0f, 0.0f};
+            for (int m = 0; m < kPts; ++m) {
+                if constexpr (G == 1) asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(dst[m].x), "=v"(dst[m].y));
+                else dst[m] = f2{0.0f, 0.0f};
+            }
         }
         return sw;
     };
@@ -401,6 +438,11 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
     bool nsw = false;
     if constexpr (PAIR) fetch_pair(cur, lane0, nz, nz2);
     else nsw = fetch_ticket(cur, lane0, nz);
+    unsigned l6 = h6, l7 = h7, l8 = h8, l9 = h9, l10 = h10;
+    if constexpr (HDR_LATE) {
+        asm volatile("" : "+s"(hdra) :: "memory");                       // (behind the sample requests)
+        l6 = ((ConstU32)hdra)[6]; l7 = ((ConstU32)hdra)[7]; l8 = ((ConstU32)hdra)[8]; l9 = ((ConstU32)hdra)[9]; l10 = ((ConstU32)hdra)[10];
+    }
     PW_STAMP();
     constexpr int WPT = (NC + THREADS - 1) / THREADS;
     float wa[WPT], wb[WPT];
@@ -433,7 +475,7 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
     PW_STAMP();
     // (compared BEFORE the first access through pl.sec -- ADVICE r05: a replaced blob of another layout must not be read at the
     //  old offsets; the scalar loads were requested at kernel entry and have arrived while the samples were being requested)
-    if (h6 != pl.band_off || h7 != (unsigned)pl.L || h8 != (unsigned)pl.NR || h9 != (unsigned)pl.CMQ || h10 != (unsigned)pl.nlist) {
+    if (l6 != pl.band_off || l7 != (unsigned)pl.L || l8 != (unsigned)pl.NR || l9 != (unsigned)pl.CMQ || l10 != (unsigned)pl.nlist) {
         // not the plan this launch was sized for (workgroup-uniform): nothing is computed, the next API call fails (KPR_E_DEVICE)
         if (tid == 0) status_raise(kStStalePlan);
         return;

@@ -2,6 +2,7 @@
 """Static instruction mix of the hot loop of every kernel in a gfx950 assembly file (hipcc -save-temps .s).
 
     python tools/probes/isa_count.py file.s [kernel-name-substring]
+    python tools/probes/isa_count.py --prologue file.s [kernel-name-substring]    (spans of k_mel_pw: see prologue())
 
 The hot loop of a kernel = the span of its LAST backward branch target .. that branch with the most instructions (the
 frame loop of the probes and of the product kernels is by far the largest loop).  Prints per kernel: VGPRs / spills /
@@ -69,7 +70,63 @@ def kernels(text):
         yield cur, body
 
 
+ADDR64 = re.compile(r"v_(lshl_add_u64|mad_u64_u32|mad_i64_i32|add_co_u32|addc_co_u32|sub_co_u32|subb_co_u32|mov_b64|"
+                    r"cmp\w*_[iu]64|lshlrev_b64|ashrrev_i64)")
+
+
+def span_counts(instrs):
+    """VALU / SALU / 64-bit VALU address / magic-division multiply / SGPR spill (lane) instructions of a list of (op, rest)"""
+    c = dict(n=len(instrs), valu=0, salu=0, addr64=0, mulhi=0, spill=0, vmem=0, lds=0)
+    for op, rest in instrs:
+        k = classify(op)
+        if op.startswith(("v_writelane", "v_readlane")):
+            c["spill"] += 1
+        if k in ("valu", "pk", "trans", "permlane"):
+            c["valu"] += 1
+            if ADDR64.match(op):
+                c["addr64"] += 1
+        elif k == "salu" and not op.startswith(("s_cbranch", "s_branch")):
+            c["salu"] += 1
+        elif k in ("vmem", "lds"):
+            c[k] += 1
+        if op in ("s_mul_hi_u32", "v_mul_hi_u32"):
+            c["mulhi"] += 1
+    return c
+
+
+def prologue(text, want):
+    """Static spans (layout order) of the fused mel kernel k_mel_pw: (a) entry .. first sample request, (b) .. the prologue
+    s_barrier, (c) the ticket draw (ds_add_rtn_u32) .. the last sample request after it, and the whole kernel."""
+    print("| kernel | span | instrs | VALU | SALU | 64-bit VALU addr | mul_hi | writelane/readlane | VMEM | LDS |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for name, body in kernels(text):
+        if want not in name:
+            continue
+        ins = []
+        for line in body:
+            st = line.strip()
+            if not st or st.startswith((";", ".", "//")) or st.endswith(":") or re.match(r"^\.LBB", st):
+                continue
+            parts = st.split(None, 1)
+            ins.append((parts[0], parts[1] if len(parts) > 1 else ""))
+            if parts[0] == "s_endpgm" and ins and len(ins) > 4000:
+                break
+        first = next(i for i, (op, _) in enumerate(ins) if op.startswith("global_load"))
+        bar = next(i for i, (op, _) in enumerate(ins) if op == "s_barrier")
+        draw = next(i for i, (op, _) in enumerate(ins) if op == "ds_add_rtn_u32")
+        last = max(i for i, (op, _) in enumerate(ins[draw:draw + 600]) if op.startswith("global_load")) + draw
+        short = re.sub(r"^_Z\d+", "", name)[:40]
+        for lab, sp in (("(a) entry .. first sample request", ins[:first + 1]), ("(b) .. prologue barrier", ins[first + 1:bar + 1]),
+                        ("(c) ticket draw .. last sample request", ins[draw:last + 1]), ("whole kernel", ins)):
+            c = span_counts(sp)
+            print("| %s | %s | %d | %d | %d | %d | %d | %d | %d | %d |" % (short, lab, c["n"], c["valu"], c["salu"], c["addr64"],
+                                                                        c["mulhi"], c["spill"], c["vmem"], c["lds"]))
+
+
 def main():
+    if sys.argv[1] == "--prologue":
+        prologue(open(sys.argv[2]).read(), sys.argv[3] if len(sys.argv) > 3 else "k_mel_pw")
+        return
     path = sys.argv[1]
     want = sys.argv[2] if len(sys.argv) > 2 else ""
     text = open(path).read()
