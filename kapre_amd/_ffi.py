@@ -233,11 +233,10 @@ def require_gpu():
                            "False); the MI355X kernels have no CPU fallback")
 
 
-def as_device_f32(x, device=None):
-    """numpy / torch (any device, any float dtype) -> contiguous float32 torch tensor on the GPU."""
+def as_device(x, dtype):
+    """numpy / torch (any device, any dtype) -> contiguous torch tensor of ``dtype`` on the current GPU."""
     import torch
-    if (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
-            and x.is_contiguous()):
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous():
         return x                                   # steady-state fast path
     require_gpu()
     if isinstance(x, np.ndarray):
@@ -245,22 +244,7 @@ def as_device_f32(x, device=None):
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(x)
     if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    if x.dtype != torch.float32:
-        x = x.to(torch.float32)
-    return x.contiguous()
-
-
-def as_device_dtype(x, dtype, device=None):
-    """numpy / torch -> contiguous torch tensor of ``dtype`` on the GPU (float64 / complex128 path)."""
-    import torch
-    require_gpu()
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, torch.Tensor):
-        x = torch.as_tensor(x)
-    if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        x = x.to(torch.device("cuda", torch.cuda.current_device()))
     if x.dtype != dtype:
         x = x.to(dtype)
     return x.contiguous()
@@ -272,18 +256,6 @@ def is_f64(x) -> bool:
     if isinstance(x, np.ndarray):
         return x.dtype in (np.float64, np.complex128)
     return isinstance(x, torch.Tensor) and x.dtype in (torch.float64, torch.complex128)
-
-
-def as_device_c64(x, device=None):
-    import torch
-    require_gpu()
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    if x.dtype != torch.complex64:
-        x = x.to(torch.complex64)
-    return x.contiguous()
 
 
 def ptr(t):
@@ -304,6 +276,11 @@ def filterbank_pack(fb_host: np.ndarray, kranges: np.ndarray) -> np.ndarray:
     return out
 
 
+def filterbank_forget(addr: int):
+    """Drop what the library cached about the packed filterbank at device address ``addr`` (it is being freed)."""
+    lib().kpr_filterbank_forget(ctypes.c_void_p(addr))
+
+
 def filterbank_kranges(fb_host: np.ndarray) -> np.ndarray:
     """Per 16-filter tile [lo, hi) row range outside of which the (n_freq, n_filt) matrix is 0."""
     fb_host = np.ascontiguousarray(fb_host, dtype=np.float32)
@@ -312,4 +289,238 @@ def filterbank_kranges(fb_host: np.ndarray) -> np.ndarray:
     check(lib().kpr_filterbank_kranges(fb_host.ctypes.data_as(ctypes.c_void_p), n_freq, n_filt,
                                        out.ctypes.data_as(ctypes.c_void_p)),
           "kpr_filterbank_kranges")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# native operations: one launcher per entry point family, shared by the layers and their backward passes.  Each picks
+# the float32 / float64 entry point from the dtype of the (contiguous, device) tensor it is given, allocates the output
+# and the workspace, and runs the call with the tensor's device current on torch's current stream there.
+# ---------------------------------------------------------------------------------------------
+def dims_of(shape, fmt):
+    """(b, *inner, c) for channels_last, (b, c, *inner) for channels_first -> (b, c, *inner).  ``fmt`` is a data-format
+    string or a layout enum."""
+    if fmt in ("channels_last", CHANNELS_LAST):
+        return (shape[0], shape[-1], *shape[1:-1])
+    return tuple(shape)
+
+
+def shape_of(fmt, b, c, *inner):
+    """The inverse of ``dims_of``."""
+    return (b, *inner, c) if fmt in ("channels_last", CHANNELS_LAST) else (b, c, *inner)
+
+
+def workspace(nbytes: int, device):
+    import torch
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _call(name: str, device, *args):
+    """``name``(*args, stream) with ``device`` current; raises naming ``name`` when it fails."""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args, current_stream_ptr()), name)
+
+
+def mel_workspace_bytes(g_ref, n_filt: int, db_ref, packed: bool) -> int:
+    """kpr_mel_f32's scratch: without a packed filterbank it takes its two-kernel path, which stages the spectrum."""
+    L = lib()
+    n = int(L.kpr_mel_workspace_bytes(g_ref, n_filt, db_ref) if packed
+            else L.kpr_mel_workspace_bytes_unpacked(g_ref, n_filt))
+    if n < 0:
+        check(-1, "kpr_mel_workspace_bytes")
+    return n
+
+
+def num_frames(geom: StftGeom) -> int:
+    n = int(lib().kpr_num_frames(ctypes.byref(geom)))
+    if n < 0:
+        check(-1, "kpr_num_frames")
+    return n
+
+
+def stft(x, geom: StftGeom, n_frames: int, window, mode: int):
+    """STFT of the float32 / float64 waveform ``x`` (``geom``; ``n_frames = num_frames(geom)``) with ``window`` of x's
+    dtype: complex spectrogram for OUT_COMPLEX, else real, laid out as geom.out_layout."""
+    import torch
+    f64 = x.dtype == torch.float64
+    dtype = ((torch.complex128 if f64 else torch.complex64) if mode == OUT_COMPLEX else x.dtype)
+    out = torch.empty(shape_of(geom.out_layout, geom.batch, geom.channels, n_frames, geom.n_fft // 2 + 1),
+                      dtype=dtype, device=x.device)
+    if f64:
+        _call("kpr_stft_f64", x.device, ptr(x), ctypes.byref(geom), ptr(window), ptr(out), mode)
+    else:
+        ws_bytes = int(lib().kpr_stft_workspace_bytes(ctypes.byref(geom), mode))
+        ws = workspace(ws_bytes, x.device)
+        _call("kpr_stft_f32", x.device, ptr(x), ctypes.byref(geom), ptr(window), ptr(out), mode, ptr(ws), ws_bytes)
+    return out
+
+
+def istft(spec, window, n_fft: int, win_length: int, hop_length: int, wave_fmt, spec_fmt):
+    """Inverse STFT of the complex64 / complex128 spectrogram ``spec`` (n_fft // 2 + 1 bins) with the synthesis
+    ``window``: (n_frames - 1) hop + win samples per signal (untrimmed), float32 / float64."""
+    import torch
+    f64 = spec.dtype == torch.complex128
+    b, c, f, _ = dims_of(spec.shape, spec_fmt)
+    # StftGeom: in_layout = waveform layout, out_layout = spectrogram layout
+    g = StftGeom(b, c, 0, int(n_fft), int(win_length), int(hop_length), 0, 0, layout(wave_fmt), layout(spec_fmt))
+    t_out = (f - 1) * int(hop_length) + int(win_length) if f > 0 else 0
+    out = torch.empty(shape_of(wave_fmt, b, c, t_out), dtype=torch.float64 if f64 else torch.float32,
+                      device=spec.device)
+    L = lib()
+    ws_bytes = int((L.kpr_istft_f64_workspace_bytes if f64 else L.kpr_istft_workspace_bytes)(ctypes.byref(g), f))
+    ws = workspace(ws_bytes, spec.device)
+    _call("kpr_istft_f64" if f64 else "kpr_istft_f32", spec.device, ptr(spec), ctypes.byref(g), f, ptr(window),
+          ptr(out), ptr(ws), ws_bytes)
+    return out
+
+
+def edge_scale(spec, n_fft: int, fmt, s_edge: float, s_mid: float, out=None):
+    """``spec`` (complex) times s_edge on the DC / Nyquist bins, s_mid elsewhere."""
+    import torch
+    if out is None:
+        out = torch.empty_like(spec)
+    b, c, f, k = dims_of(spec.shape, fmt)
+    inner = c if fmt in ("channels_last", CHANNELS_LAST) else 1
+    _call("kpr_spec_edge_scale_c128" if spec.dtype == torch.complex128 else "kpr_spec_edge_scale_c64", spec.device,
+          ptr(spec), spec.numel(), int(k), int(inner), int(n_fft), float(s_edge), float(s_mid), ptr(out))
+    return out
+
+
+def _cplx_to_real_name(x, phase: bool) -> str:
+    import torch
+    if x.dtype == torch.complex128:
+        return "kpr_angle_c128" if phase else "kpr_abs_c128"
+    return "kpr_angle_c64" if phase else "kpr_abs_c64"
+
+
+def cplx_to_real(x, phase: bool):
+    """|x|, or angle(x) with ``phase``, of a complex64 / complex128 tensor: float32 / float64."""
+    import torch
+    out = torch.empty(x.shape, dtype=torch.float64 if x.dtype == torch.complex128 else torch.float32, device=x.device)
+    _call(_cplx_to_real_name(x, phase), x.device, ptr(x), x.numel(), ptr(out))
+    return out
+
+
+def cplx_to_real_bwd(x, g, phase: bool):
+    """Cotangent of ``x`` from the cotangent ``g`` of ``cplx_to_real(x, phase)``."""
+    import torch
+    g = g.contiguous().to(torch.float64 if x.dtype == torch.complex128 else torch.float32)
+    gx = torch.empty_like(x)
+    _call(_cplx_to_real_name(x, phase) + "_bwd", x.device, ptr(x), ptr(g), x.numel(), ptr(gx))
+    return gx
+
+
+def freq_matmul(x, fmt, mat, packed=None, kranges=None):
+    """x . mat over the frequency axis of the rank-4 float32 / float64 tensor ``x`` (``mat``: (n_in, n_out), x's dtype).
+    ``kranges`` (host int32 row ranges of a banded filterbank) selects the filterbank entry point, which also takes the
+    optional MFMA-ordered copy ``packed``; without it float32 runs the plain GEMM."""
+    import torch
+    b, c, f, n_in = dims_of(x.shape, fmt)
+    n_out = int(mat.shape[1])
+    out = torch.empty(shape_of(fmt, b, c, f, n_out), dtype=x.dtype, device=x.device)
+    args = (ptr(x), b, c, f, n_in, layout(fmt), ptr(mat))
+    if x.dtype == torch.float64:
+        _call("kpr_apply_filterbank_f64", x.device, *args, n_out, ptr(out))
+    elif kranges is not None:
+        _call("kpr_apply_filterbank_packed_f32", x.device, *args, ptr(packed), n_out,
+              kranges.ctypes.data_as(ctypes.c_void_p), ptr(out))
+    else:
+        _call("kpr_apply_filterbank_f32", x.device, *args, n_out, ctypes.c_void_p(0), ptr(out))
+    return out
+
+
+def _db_items(x):
+    """(items, item size) of the decibel entry points: the leading axis holds the items; a rank-1 tensor is one."""
+    if x.dim() > 1:
+        return x.shape[0], x.numel() // max(x.shape[0], 1)
+    return 1, x.numel()
+
+
+def mag_to_db(x, ref_value: float, amin: float, dynamic_range: float):
+    """backend.magnitude_to_decibel of a float32 / float64 tensor."""
+    import torch
+    out = torch.empty_like(x)
+    n_items, item = _db_items(x)
+    if x.dtype == torch.float64:
+        _call("kpr_mag_to_db_f64", x.device, ptr(x), n_items, item, float(ref_value), float(amin),
+              float(dynamic_range), ptr(out))
+    else:
+        ws_bytes = int(lib().kpr_db_workspace_bytes(n_items))
+        ws = workspace(ws_bytes, x.device)
+        db = DbParams(1, float(ref_value), float(amin), float(dynamic_range))
+        _call("kpr_mag_to_db_f32", x.device, ptr(x), n_items, item, ctypes.byref(db), ptr(out), ptr(ws), ws_bytes)
+    return out
+
+
+def mag_to_db_bwd(x, g, ref_value: float, amin: float, dynamic_range: float):
+    """Cotangent of ``x`` from the cotangent ``g`` of ``mag_to_db(x, ...)``."""
+    import torch
+    g = g.contiguous().to(x.dtype)
+    gx = torch.empty_like(x)
+    n_items, item = _db_items(x)
+    if x.dtype == torch.float64:
+        _call("kpr_mag_to_db_bwd_f64", x.device, ptr(x), ptr(g), n_items, item, ref_value, amin, dynamic_range,
+              ptr(gx))
+    else:
+        db = DbParams(1, ref_value, amin, dynamic_range)
+        _call("kpr_mag_to_db_bwd_f32", x.device, ptr(x), ptr(g), n_items, item, ctypes.byref(db), ptr(gx))
+    return gx
+
+
+# float32-only signal operations (kapre_amd/signal.py, Delta)
+def _frame_count(t, frame_length, hop_length, pad_end) -> int:
+    n = int(lib().kpr_frame_count(t, frame_length, hop_length, int(bool(pad_end))))
+    if n < 0:
+        check(-1, "kpr_frame_count")
+    return n
+
+
+def frame(x, fmt, frame_length, hop_length, pad_end, pad_value):
+    """tf.signal.frame of the waveform ``x``: (b, frames, frame_length, c) / (b, c, frames, frame_length)."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    f = _frame_count(t, frame_length, hop_length, pad_end)
+    out = torch.empty(shape_of(fmt, b, c, f, frame_length), dtype=torch.float32, device=x.device)
+    _call("kpr_frame_f32", x.device, ptr(x), b, c, t, layout(fmt), frame_length, hop_length, int(bool(pad_end)),
+          float(pad_value), ptr(out))
+    return out
+
+
+def frame_bwd(g, x_shape, fmt, frame_length, hop_length, pad_end):
+    import torch
+    b, c, t = dims_of(x_shape, fmt)
+    gx = torch.empty(x_shape, dtype=torch.float32, device=g.device)
+    _call("kpr_frame_bwd_f32", g.device, ptr(g), b, c, t, layout(fmt), frame_length, hop_length, int(bool(pad_end)),
+          ptr(gx))
+    return gx
+
+
+def energy(x, fmt, frame_length, hop_length, pad_end, pad_value, scale):
+    """``scale`` times the sum of squares of each frame of the waveform ``x``: (b, frames, c) / (b, c, frames)."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    f = _frame_count(t, frame_length, hop_length, pad_end)
+    out = torch.empty(shape_of(fmt, b, c, f), dtype=torch.float32, device=x.device)
+    _call("kpr_energy_f32", x.device, ptr(x), b, c, t, layout(fmt), frame_length, hop_length, int(bool(pad_end)),
+          float(pad_value), float(scale), ptr(out))
+    return out
+
+
+def energy_bwd(x, g, fmt, frame_length, hop_length, pad_end, scale):
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    gx = torch.empty(x.shape, dtype=torch.float32, device=g.device)
+    _call("kpr_energy_bwd_f32", g.device, ptr(x), ptr(g), b, c, t, layout(fmt), frame_length, hop_length,
+          int(bool(pad_end)), float(scale), ptr(gx))
+    return gx
+
+
+def delta(x, fmt, win_length, mode: str, backward: bool = False):
+    """Delta of the rank-4 ``x`` along its time axis, or with ``backward`` its adjoint (x is then the cotangent)."""
+    import torch
+    b, c, t, f = dims_of(x.shape, fmt)
+    out = torch.empty_like(x)
+    _call("kpr_delta_bwd_f32" if backward else "kpr_delta_f32", x.device, ptr(x), b, c, t, f, layout(fmt), win_length,
+          PAD_MODES[mode.lower()], ptr(out))
     return out

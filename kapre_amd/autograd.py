@@ -18,8 +18,6 @@ torch.autograd is the tape; every arithmetic step is a HIP launch of this packag
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
 from . import _ffi
@@ -38,7 +36,7 @@ def needs_grad(x) -> bool:
 
 def prep(x, dtype_name: str):
     """Device / dtype / layout normalisation of a tensor that carries gradient, done with torch ops so that it is
-    recorded (the forward-only path does the same through _ffi.as_device_* outside the tape)."""
+    recorded (the forward-only path does the same through _ffi.as_device outside the tape)."""
     import torch
 
     _ffi.require_gpu()
@@ -48,87 +46,6 @@ def prep(x, dtype_name: str):
     if x.dtype != dtype:
         x = x.to(dtype)
     return x.contiguous()
-
-
-def _stream():
-    return _ffi.current_stream_ptr()
-
-
-def _edge_scale(spec, n_fft: int, channels_last: bool, s_edge: float, s_mid: float, out=None):
-    """``spec`` (complex, frequency axis 2 for channels_last, 3 otherwise) times s_edge on DC / Nyquist, s_mid elsewhere."""
-    import torch
-
-    f64 = spec.dtype == torch.complex128
-    if out is None:
-        out = torch.empty_like(spec)
-    k = spec.shape[2] if channels_last else spec.shape[3]
-    inner = spec.shape[3] if channels_last else 1
-    fn = _ffi.lib().kpr_spec_edge_scale_c128 if f64 else _ffi.lib().kpr_spec_edge_scale_c64
-    with torch.cuda.device(spec.device):
-        _ffi.check(fn(_ffi.ptr(spec), spec.numel(), int(k), int(inner), int(n_fft), float(s_edge), float(s_mid),
-                      _ffi.ptr(out), _stream()), 'kpr_spec_edge_scale')
-    return out
-
-
-def _run_istft(spec, n_fft, win_length, hop, window, wave_fmt, spec_fmt):
-    """kpr_istft_f32 / f64 on a contiguous complex spectrogram with an arbitrary 'synthesis' window tensor."""
-    import torch
-
-    f64 = spec.dtype == torch.complex128
-    if spec_fmt == _CH_LAST_STR:
-        b, f, k, c = spec.shape
-    else:
-        b, c, f, k = spec.shape
-    g = _ffi.StftGeom(b, c, 0, int(n_fft), int(win_length), int(hop), 0, 0, _ffi.layout(wave_fmt), _ffi.layout(spec_fmt))
-    t_out = (f - 1) * int(hop) + int(win_length) if f > 0 else 0
-    shape = (b, t_out, c) if wave_fmt == _CH_LAST_STR else (b, c, t_out)
-    out = torch.empty(shape, dtype=torch.float64 if f64 else torch.float32, device=spec.device)
-    if out.numel() == 0:
-        return out
-    L = _ffi.lib()
-    with torch.cuda.device(spec.device):
-        if f64:
-            ws_bytes = int(L.kpr_istft_f64_workspace_bytes(ctypes.byref(g), f))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=spec.device)
-            _ffi.check(L.kpr_istft_f64(_ffi.ptr(spec), ctypes.byref(g), f, _ffi.ptr(window), _ffi.ptr(out),
-                                       _ffi.ptr(ws), ws_bytes, _stream()), 'kpr_istft_f64')
-        else:
-            ws_bytes = int(L.kpr_istft_workspace_bytes(ctypes.byref(g), f))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=spec.device)
-            _ffi.check(L.kpr_istft_f32(_ffi.ptr(spec), ctypes.byref(g), f, _ffi.ptr(window), _ffi.ptr(out),
-                                       _ffi.ptr(ws), ws_bytes, _stream()), 'kpr_istft_f32')
-    return out
-
-
-def _run_stft(wave, n_fft, win_length, hop, window, wave_fmt, spec_fmt):
-    """kpr_stft_f32 / f64 (complex output, no padding) on a contiguous waveform with an arbitrary window tensor."""
-    import torch
-
-    f64 = wave.dtype == torch.float64
-    if wave_fmt == _CH_LAST_STR:
-        b, t, c = wave.shape
-    else:
-        b, c, t = wave.shape
-    g = _ffi.StftGeom(b, c, t, int(n_fft), int(win_length), int(hop), 0, 0, _ffi.layout(wave_fmt), _ffi.layout(spec_fmt))
-    L = _ffi.lib()
-    n_frames = int(L.kpr_num_frames(ctypes.byref(g)))
-    if n_frames < 0:
-        _ffi.check(-1, 'kpr_num_frames')
-    k = int(n_fft) // 2 + 1
-    shape = (b, n_frames, k, c) if spec_fmt == _CH_LAST_STR else (b, c, n_frames, k)
-    out = torch.empty(shape, dtype=torch.complex128 if f64 else torch.complex64, device=wave.device)
-    if out.numel() == 0:
-        return out
-    with torch.cuda.device(wave.device):
-        if f64:
-            _ffi.check(L.kpr_stft_f64(_ffi.ptr(wave), ctypes.byref(g), _ffi.ptr(window), _ffi.ptr(out),
-                                      _ffi.OUT_COMPLEX, _stream()), 'kpr_stft_f64')
-        else:
-            ws_bytes = int(L.kpr_stft_workspace_bytes(ctypes.byref(g), _ffi.OUT_COMPLEX))
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=wave.device)
-            _ffi.check(L.kpr_stft_f32(_ffi.ptr(wave), ctypes.byref(g), _ffi.ptr(window), _ffi.ptr(out),
-                                      _ffi.OUT_COMPLEX, _ffi.ptr(ws), ws_bytes, _stream()), 'kpr_stft_f32')
-    return out
 
 
 def _scaled_window(layer, key, device, f64: bool, scale: float):
@@ -154,12 +71,11 @@ def stft_vjp(layer, gspec, x_shape):
     import torch
 
     n_fft, win, hop = int(layer.n_fft), int(layer.win_length), int(layer.hop_length)
-    ch_last_spec = layer.output_data_format == _CH_LAST_STR
     f64 = gspec.dtype == torch.complex128
     gspec = gspec.contiguous()
-    half = _edge_scale(gspec, n_fft, ch_last_spec, 1.0, 0.5)
+    half = _ffi.edge_scale(gspec, n_fft, layer.output_data_format, 1.0, 0.5)
     window = _scaled_window(layer, 'vjp_window', gspec.device, f64, float(n_fft))
-    ola = _run_istft(half, n_fft, win, hop, window, layer.input_data_format, layer.output_data_format)
+    ola = _ffi.istft(half, window, n_fft, win, hop, layer.input_data_format, layer.output_data_format)
     gx = torch.zeros(x_shape, dtype=ola.dtype, device=ola.device)
     pad_left = n_fft - hop if layer.pad_begin else 0
     t_axis = 1 if layer.input_data_format == _CH_LAST_STR else 2
@@ -182,11 +98,14 @@ def istft_vjp(layer, gwave, n_frames):
     f64 = gwave.dtype == torch.float64
     gwave = gwave.contiguous()
     window = _scaled_window(layer, 'vjp_window', gwave.device, f64, 2.0 / n_fft)
-    spec = _run_stft(gwave, n_fft, win, hop, window, layer.output_data_format, layer.input_data_format)
-    f_axis = 1 if layer.input_data_format == _CH_LAST_STR else 2
-    if spec.shape[f_axis] != n_frames:     # cannot happen: (F - 1) hop + win samples frame into exactly F frames
-        raise RuntimeError('InverseSTFT backward: %d frames, expected %d' % (spec.shape[f_axis], n_frames))
-    return _edge_scale(spec, n_fft, layer.input_data_format == _CH_LAST_STR, 0.5, 1.0, out=spec)
+    b, c, t = _ffi.dims_of(gwave.shape, layer.output_data_format)
+    g = _ffi.StftGeom(b, c, t, n_fft, win, hop, 0, 0, _ffi.layout(layer.output_data_format),
+                      _ffi.layout(layer.input_data_format))
+    f = _ffi.num_frames(g)
+    if f != n_frames:     # cannot happen: (F - 1) hop + win samples frame into exactly F frames
+        raise RuntimeError('InverseSTFT backward: %d frames, expected %d' % (f, n_frames))
+    spec = _ffi.stft(gwave, g, f, window, _ffi.OUT_COMPLEX)
+    return _ffi.edge_scale(spec, n_fft, layer.input_data_format, 0.5, 1.0, out=spec)
 
 
 def _functions():
@@ -240,16 +159,7 @@ def _functions():
         @staticmethod
         def backward(ctx, g):
             (x,) = ctx.saved_tensors
-            f64 = x.dtype == torch.complex128
-            x = x.contiguous()
-            g = g.contiguous().to(torch.float64 if f64 else torch.float32)
-            gx = torch.empty_like(x)
-            L = _ffi.lib()
-            fn = ((L.kpr_angle_c128_bwd if f64 else L.kpr_angle_c64_bwd) if ctx.phase
-                  else (L.kpr_abs_c128_bwd if f64 else L.kpr_abs_c64_bwd))
-            with torch.cuda.device(x.device):
-                _ffi.check(fn(_ffi.ptr(x), _ffi.ptr(g), x.numel(), _ffi.ptr(gx), _stream()), 'kpr_abs/angle_bwd')
-            return gx, None, None
+            return _ffi.cplx_to_real_bwd(x.contiguous(), g, ctx.phase), None, None
 
     class MatrixFn(torch.autograd.Function):
         """y = x . M over the frequency axis (ApplyFilterbank, LogmelToMFCC); backward = the same GEMM with M^T."""
@@ -262,26 +172,7 @@ def _functions():
         @staticmethod
         def backward(ctx, g):
             mt = ctx.matrix_t                         # (n_out, n_in) on the device, dtype of the layer
-            f64 = mt.dtype == torch.float64
-            g = g.contiguous().to(mt.dtype)
-            if ctx.data_format == _CH_LAST_STR:
-                b, f, m, c = g.shape
-            else:
-                b, c, f, m = g.shape
-            n_in = int(mt.shape[1])
-            shape = (b, f, n_in, c) if ctx.data_format == _CH_LAST_STR else (b, c, f, n_in)
-            gx = torch.empty(shape, dtype=mt.dtype, device=g.device)
-            L = _ffi.lib()
-            with torch.cuda.device(g.device):
-                if f64:
-                    _ffi.check(L.kpr_apply_filterbank_f64(_ffi.ptr(g), b, c, f, m, _ffi.layout(ctx.data_format),
-                                                          _ffi.ptr(mt), n_in, _ffi.ptr(gx), _stream()),
-                               'kpr_apply_filterbank_f64 (backward)')
-                else:
-                    _ffi.check(L.kpr_apply_filterbank_f32(_ffi.ptr(g), b, c, f, m, _ffi.layout(ctx.data_format),
-                                                          _ffi.ptr(mt), n_in, ctypes.c_void_p(0), _ffi.ptr(gx),
-                                                          _stream()), 'kpr_apply_filterbank_f32 (backward)')
-            return gx, None, None, None
+            return _ffi.freq_matmul(g.contiguous().to(mt.dtype), ctx.data_format, mt), None, None, None
 
     class DbFn(torch.autograd.Function):
         @staticmethod
@@ -294,24 +185,7 @@ def _functions():
         @staticmethod
         def backward(ctx, g):
             (x,) = ctx.saved_tensors
-            ref, amin, dyn = ctx.params
-            g = g.contiguous().to(x.dtype)
-            gx = torch.empty_like(x)
-            if x.dim() > 1:
-                n_items = x.shape[0]
-                item = x.numel() // max(n_items, 1)
-            else:
-                n_items, item = 1, x.numel()
-            L = _ffi.lib()
-            with torch.cuda.device(x.device):
-                if x.dtype == torch.float64:
-                    _ffi.check(L.kpr_mag_to_db_bwd_f64(_ffi.ptr(x), _ffi.ptr(g), n_items, item, ref, amin, dyn,
-                                                       _ffi.ptr(gx), _stream()), 'kpr_mag_to_db_bwd_f64')
-                else:
-                    db = _ffi.DbParams(1, ref, amin, dyn)
-                    _ffi.check(L.kpr_mag_to_db_bwd_f32(_ffi.ptr(x), _ffi.ptr(g), n_items, item, ctypes.byref(db),
-                                                       _ffi.ptr(gx), _stream()), 'kpr_mag_to_db_bwd_f32')
-            return gx, None
+            return _ffi.mag_to_db_bwd(x, g, *ctx.params), None
 
     class ChainFn(torch.autograd.Function):
         """A fused run of layers (one forward launch); backward recomputes the chain layer by layer with the
@@ -373,28 +247,11 @@ def _functions():
         def backward(ctx, g):
             layer = ctx.layer
             g = g.contiguous().to(torch.float32)
-            fmt = layer.data_format
-            L = _ffi.lib()
+            args = (layer.data_format, int(layer.frame_length), int(layer.hop_length), layer.pad_end)
             if ctx.energy:
                 (x,) = ctx.saved_tensors
-            shape = tuple(x.shape) if ctx.energy else ctx.x_shape
-            if fmt == _CH_LAST_STR:
-                b, t, c = shape
-            else:
-                b, c, t = shape
-            gx = torch.empty(shape, dtype=torch.float32, device=g.device)
-            with torch.cuda.device(g.device):
-                if ctx.energy:
-                    scale = layer.ref_duration / (layer.frame_length / layer.sample_rate)
-                    _ffi.check(L.kpr_energy_bwd_f32(_ffi.ptr(x), _ffi.ptr(g), b, c, t, _ffi.layout(fmt),
-                                                    int(layer.frame_length), int(layer.hop_length),
-                                                    int(bool(layer.pad_end)), float(scale), _ffi.ptr(gx), _stream()),
-                               'kpr_energy_bwd_f32')
-                else:
-                    _ffi.check(L.kpr_frame_bwd_f32(_ffi.ptr(g), b, c, t, _ffi.layout(fmt), int(layer.frame_length),
-                                                   int(layer.hop_length), int(bool(layer.pad_end)), _ffi.ptr(gx),
-                                                   _stream()), 'kpr_frame_bwd_f32')
-            return gx, None, None
+                return _ffi.energy_bwd(x, g, *args, layer._scale()), None, None
+            return _ffi.frame_bwd(g, ctx.x_shape, *args), None, None
 
     class DeltaFn(torch.autograd.Function):
         @staticmethod
@@ -406,16 +263,7 @@ def _functions():
         def backward(ctx, g):
             layer = ctx.layer
             g = g.contiguous().to(torch.float32)
-            if layer.data_format == _CH_LAST_STR:
-                b, t, f, c = g.shape
-            else:
-                b, c, t, f = g.shape
-            gx = torch.empty_like(g)
-            with torch.cuda.device(g.device):
-                _ffi.check(_ffi.lib().kpr_delta_bwd_f32(_ffi.ptr(g), b, c, t, f, _ffi.layout(layer.data_format),
-                                                        int(layer.win_length), _ffi.PAD_MODES[layer.mode.lower()],
-                                                        _ffi.ptr(gx), _stream()), 'kpr_delta_bwd_f32')
-            return gx, None
+            return _ffi.delta(g, layer.data_format, int(layer.win_length), layer.mode, backward=True), None
 
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn)

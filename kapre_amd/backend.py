@@ -11,7 +11,6 @@ signal itself runs in the HIP kernels behind ``kapre_amd._ffi``.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Callable, Optional, Union
 
 import numpy as np
@@ -181,28 +180,8 @@ def magnitude_to_decibel(x, ref_value: float = 1.0, amin: float = 1e-5,
     import torch
 
     f64 = _ffi.is_f64(x)            # tf ops compute in the dtype of their input (float64 layers hand in float64)
-    xt = _ffi.as_device_dtype(x, torch.float64) if f64 else _ffi.as_device_f32(x)
-    out = torch.empty_like(xt)
-    if xt.dim() > 1:
-        n_items = xt.shape[0]
-        item_size = xt.numel() // max(n_items, 1)
-    else:
-        n_items, item_size = 1, xt.numel()
-    L = _ffi.lib()
-    if f64:
-        with torch.cuda.device(xt.device):
-            _ffi.check(L.kpr_mag_to_db_f64(_ffi.ptr(xt), n_items, item_size, float(ref_value), float(amin),
-                                           float(dynamic_range), _ffi.ptr(out), _ffi.current_stream_ptr()),
-                       'kpr_mag_to_db_f64')
-        return out
-    ws_bytes = int(L.kpr_db_workspace_bytes(n_items))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xt.device)
-    db = _ffi.DbParams(1, float(ref_value), float(amin), float(dynamic_range))
-    with torch.cuda.device(xt.device):
-        _ffi.check(L.kpr_mag_to_db_f32(_ffi.ptr(xt), n_items, item_size, ctypes.byref(db),
-                                       _ffi.ptr(out), _ffi.ptr(ws), ws_bytes,
-                                       _ffi.current_stream_ptr()), 'kpr_mag_to_db_f32')
-    return out
+    xt = _ffi.as_device(x, torch.float64 if f64 else torch.float32)
+    return _ffi.mag_to_db(xt, ref_value, amin, dynamic_range)
 
 
 # --------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@
 constructor signatures, validation, get_config() keys and output shapes; the arithmetic runs in
 libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with a DCT-II matrix).
 MuLawEncoding / MuLawDecoding are out of scope."""
-import ctypes
 import math
 
 import numpy as np
@@ -19,14 +18,13 @@ def _resolve_format(fmt):
     return backend.image_data_format() if fmt == _CH_DEFAULT_STR else fmt
 
 
-def _waveform_dims(x, data_format):
+def _as_waveform(x):
+    import torch
+
+    x = _ffi.as_device(x, torch.float32)
     if x.dim() != 3:
         raise ValueError('expected a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-    if data_format == _CH_FIRST_STR:
-        b, c, t = x.shape
-    else:
-        b, t, c = x.shape
-    return int(b), int(c), int(t)
+    return x
 
 
 @register_keras_serializable(package='Kapre')
@@ -56,14 +54,12 @@ class Frame(Layer):
 
     def compute_output_shape(self, input_shape):
         """(b, t, ch) -> (b, frame, frame_length, ch); (b, ch, t) -> (b, ch, frame, frame_length) (tf.signal.frame)"""
-        t = input_shape[self.time_axis]
+        b, c, t = _ffi.dims_of(input_shape, self.data_format)
         n = None
         if t is not None:
             t, fl, hop = int(t), int(self.frame_length), int(self.hop_length)
             n = -(-t // hop) if self.pad_end else max(0, 1 + (t - fl) // hop)
-        if self.data_format == _CH_FIRST_STR:
-            return (input_shape[0], input_shape[1], n, int(self.frame_length))
-        return (input_shape[0], n, int(self.frame_length), input_shape[2])
+        return _ffi.shape_of(self.data_format, b, c, n, int(self.frame_length))
 
     def call(self, x):
         if autograd.needs_grad(x):
@@ -71,21 +67,8 @@ class Frame(Layer):
         return self._forward(x)
 
     def _forward(self, x):
-        import torch
-
-        x = _ffi.as_device_f32(x)
-        b, c, t = _waveform_dims(x, self.data_format)
-        L = _ffi.lib()
-        f = int(L.kpr_frame_count(t, self.frame_length, self.hop_length, int(bool(self.pad_end))))
-        shape = ((b, f, self.frame_length, c) if self.data_format == _CH_LAST_STR
-                 else (b, c, f, self.frame_length))
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _ffi.check(L.kpr_frame_f32(_ffi.ptr(x), b, c, t, _ffi.layout(self.data_format),
-                                       self.frame_length, self.hop_length, int(bool(self.pad_end)),
-                                       float(self.pad_value), _ffi.ptr(out), _ffi.current_stream_ptr()),
-                       'kpr_frame_f32')
-        return out
+        return _ffi.frame(_as_waveform(x), self.data_format, self.frame_length, self.hop_length, self.pad_end,
+                          self.pad_value)
 
     def get_config(self):
         config = super(Frame, self).get_config()
@@ -118,37 +101,24 @@ class Energy(Layer):
 
     def compute_output_shape(self, input_shape):
         """(b, t, ch) -> (b, frame, ch); (b, ch, t) -> (b, ch, frame)"""
-        t = input_shape[self.time_axis]
+        b, c, t = _ffi.dims_of(input_shape, self.data_format)
         n = None
         if t is not None:
             t, fl, hop = int(t), int(self.frame_length), int(self.hop_length)
             n = -(-t // hop) if self.pad_end else max(0, 1 + (t - fl) // hop)
-        if self.data_format == _CH_FIRST_STR:
-            return (input_shape[0], input_shape[1], n)
-        return (input_shape[0], n, input_shape[2])
+        return _ffi.shape_of(self.data_format, b, c, n)
 
     def call(self, x):
         if autograd.needs_grad(x):
             return autograd.energy(self, autograd.prep(x, 'float32'))
         return self._forward(x)
 
-    def _forward(self, x):
-        import torch
+    def _scale(self):
+        return self.ref_duration / (self.frame_length / self.sample_rate)
 
-        x = _ffi.as_device_f32(x)
-        b, c, t = _waveform_dims(x, self.data_format)
-        L = _ffi.lib()
-        f = int(L.kpr_frame_count(t, self.frame_length, self.hop_length, int(bool(self.pad_end))))
-        _ffi.check(0 if f >= 0 else -1, 'kpr_frame_count')
-        shape = (b, f, c) if self.data_format == _CH_LAST_STR else (b, c, f)
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        nor_coeff = self.ref_duration / (self.frame_length / self.sample_rate)
-        with torch.cuda.device(x.device):
-            _ffi.check(L.kpr_energy_f32(_ffi.ptr(x), b, c, t, _ffi.layout(self.data_format),
-                                        self.frame_length, self.hop_length, int(bool(self.pad_end)),
-                                        float(self.pad_value), float(nor_coeff), _ffi.ptr(out),
-                                        _ffi.current_stream_ptr()), 'kpr_energy_f32')
-        return out
+    def _forward(self, x):
+        return _ffi.energy(_as_waveform(x), self.data_format, self.frame_length, self.hop_length, self.pad_end,
+                           self.pad_value, self._scale())
 
     def get_config(self):
         config = super(Energy, self).get_config()
@@ -202,7 +172,7 @@ class LogmelToMFCC(Layer):
     def call(self, log_melgrams):
         if autograd.needs_grad(log_melgrams):
             x = autograd.prep(log_melgrams, 'float32')
-            n_mels = int(x.shape[2] if self.data_format == _CH_LAST_STR else x.shape[3]) if x.dim() == 4 else 0
+            n_mels = int(_ffi.dims_of(x.shape, self.data_format)[3]) if x.dim() == 4 else 0
             if n_mels:
                 mat_t = self._matrix(n_mels, x.device).t().contiguous()      # (n_mfccs, n_mels): the backward GEMM
                 return autograd.matrix(self, x, mat_t, self.data_format)
@@ -211,23 +181,12 @@ class LogmelToMFCC(Layer):
     def _forward(self, log_melgrams):
         import torch
 
-        x = _ffi.as_device_f32(log_melgrams)
+        x = _ffi.as_device(log_melgrams, torch.float32)
         if x.dim() != 4:
             raise ValueError('LogmelToMFCC expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-        if self.data_format == _CH_LAST_STR:
-            b, f, m, c = x.shape
-        else:
-            b, c, f, m = x.shape
-        mat = self._matrix(int(m), x.device)
-        n_out = int(mat.shape[1])                      # min(n_mfccs, n_mels), as the slice upstream
-        shape = (b, f, n_out, c) if self.data_format == _CH_LAST_STR else (b, c, f, n_out)
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().kpr_apply_filterbank_f32(
-                _ffi.ptr(x), b, c, f, m, _ffi.layout(self.data_format), _ffi.ptr(mat), n_out,
-                ctypes.c_void_p(0), _ffi.ptr(out), _ffi.current_stream_ptr()),
-                'kpr_apply_filterbank_f32 (mfcc)')
-        return out
+        n_mels = int(_ffi.dims_of(x.shape, self.data_format)[3])
+        # (n_mels, min(n_mfccs, n_mels)): the first n_mfccs coefficients, as the slice upstream
+        return _ffi.freq_matmul(x, self.data_format, self._matrix(n_mels, x.device))
 
     def get_config(self):
         config = super(LogmelToMFCC, self).get_config()

@@ -39,7 +39,7 @@ def _resolve_format(fmt):
 
 def _forget_packed(ptr):
     try:
-        _ffi.lib().kpr_filterbank_forget(ctypes.c_void_p(ptr))
+        _ffi.filterbank_forget(ptr)
     except Exception:        # interpreter shutdown: the library may be gone already
         pass
 
@@ -61,12 +61,6 @@ class _DeviceConstants:
         return t
 
 
-def _workspace(nbytes: int, device):
-    import torch
-
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
 class _WorkspacePool:
     """Scratch buffers of the cached (plan-based) calls: one per (device, stream), grown
     geometrically and NEVER freed -- a captured hipGraph keeps replaying the pointer it recorded, so
@@ -85,7 +79,7 @@ class _WorkspacePool:
             if buf is not None:
                 self._retired.append(buf)
             grow = 0 if buf is None else 2 * buf.numel()
-            buf = self._live[key] = _workspace(max(int(nbytes), grow, 4096), device)
+            buf = self._live[key] = _ffi.workspace(max(int(nbytes), grow, 4096), device)
         return buf
 
 
@@ -150,16 +144,17 @@ class STFT(Layer):
         if x.dim() != 3:
             raise ValueError('STFT expects a rank-3 input (batch, time, ch) / (batch, ch, time), '
                              'got shape %s' % (tuple(x.shape),))
-        if self.input_data_format == _CH_LAST_STR:
-            b, t, c = x.shape
-        else:
-            b, c, t = x.shape
+        b, c, t = _ffi.dims_of(x.shape, self.input_data_format)
         return _ffi.StftGeom(b, c, t, int(self.n_fft), int(self.win_length), int(self.hop_length),
                              int(bool(self.pad_begin)), int(bool(self.pad_end)),
                              _ffi.layout(self.input_data_format),
                              _ffi.layout(self.output_data_format))
 
-    def _window(self, device):
+    def _window(self, device, f64=False):
+        # float32 uses window_fn's own values; float64 recomputes them in float64 (backend.window_values)
+        if f64:
+            return self._consts.get(('window64', int(self.win_length), id(self.window_fn)), device,
+                                    lambda: backend.window_values(self.window_fn, int(self.win_length), np.float64))
         return self._consts.get(('window', int(self.win_length), id(self.window_fn)), device,
                                 lambda: self.window_fn(int(self.win_length)))
 
@@ -170,64 +165,24 @@ class STFT(Layer):
                 bool(self.pad_end), self.input_data_format, self.output_data_format,
                 id(self.window_fn))
 
-    def _out_shape(self, g: _ffi.StftGeom, n_frames: int, q: int):
-        if self.output_data_format == _CH_LAST_STR:
-            return (g.batch, n_frames, q, g.channels)
-        return (g.batch, g.channels, n_frames, q)
-
     def _run(self, x, mode: int):
+        """float32 STFT, or float64 for a dtype='float64' layer (reference :155): complex or real output by ``mode``."""
         import torch
 
-        if self._f64:
-            return self._run_f64(x, mode)
-        x = _ffi.as_device_f32(x)
-        L = _ffi.lib()
+        x = _ffi.as_device(x, torch.float64 if self._f64 else torch.float32)
         g = self._geom(x)
-        n_frames = int(L.kpr_num_frames(ctypes.byref(g)))
-        if n_frames < 0:
-            _ffi.check(-1, 'kpr_num_frames')
-        k = int(self.n_fft) // 2 + 1
-        dtype = torch.complex64 if mode == _ffi.OUT_COMPLEX else torch.float32
-        out = torch.empty(self._out_shape(g, n_frames, k), dtype=dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            ws_bytes = int(L.kpr_stft_workspace_bytes(ctypes.byref(g), mode))
-            ws = _workspace(ws_bytes, x.device)
-            _ffi.check(L.kpr_stft_f32(_ffi.ptr(x), ctypes.byref(g), _ffi.ptr(self._window(x.device)),
-                                      _ffi.ptr(out), mode, _ffi.ptr(ws), ws_bytes,
-                                      _ffi.current_stream_ptr()), 'kpr_stft_f32')
-        return out
-
-    def _run_f64(self, x, mode: int):
-        """dtype='float64' layer: float64 in, complex128 / float64 out (reference :155)."""
-        import torch
-
-        x = _ffi.as_device_dtype(x, torch.float64)
-        L = _ffi.lib()
-        g = self._geom(x)
-        n_frames = int(L.kpr_num_frames(ctypes.byref(g)))
-        if n_frames < 0:
-            _ffi.check(-1, 'kpr_num_frames')
-        k = int(self.n_fft) // 2 + 1
-        dtype = torch.complex128 if mode == _ffi.OUT_COMPLEX else torch.float64
-        out = torch.empty(self._out_shape(g, n_frames, k), dtype=dtype, device=x.device)
-        win = self._consts.get(('window64', int(self.win_length), id(self.window_fn)), x.device,
-                               lambda: backend.window_values(self.window_fn, int(self.win_length), np.float64))
-        with torch.cuda.device(x.device):
-            _ffi.check(L.kpr_stft_f64(_ffi.ptr(x), ctypes.byref(g), _ffi.ptr(win), _ffi.ptr(out), mode,
-                                      _ffi.current_stream_ptr()), 'kpr_stft_f64')
-        return out
+        n_frames = _ffi.num_frames(g)
+        return _ffi.stft(x, g, n_frames, self._window(x.device, self._f64), mode)
 
     def compute_output_shape(self, input_shape):
         """(b, t, ch) / (b, ch, t) -> (b, frame, n_fft // 2 + 1, ch) / (b, ch, frame, n_fft // 2 + 1); frames as tf.signal.stft counts
         them after the left padding of n_fft - hop_length (reference: time_frequency.py:164-185)"""
-        b, t, c = (input_shape[0], input_shape[1], input_shape[2]) if self.input_data_format == _CH_LAST_STR else \
-                  (input_shape[0], input_shape[2], input_shape[1])
+        b, c, t = _ffi.dims_of(input_shape, self.input_data_format)
         frames = None
         if t is not None:
             t = int(t) + (int(self.n_fft) - int(self.hop_length) if self.pad_begin else 0)
             frames = -(-t // int(self.hop_length)) if self.pad_end else max(0, 1 + (t - int(self.win_length)) // int(self.hop_length))
-        k = int(self.n_fft) // 2 + 1
-        return (b, frames, k, c) if self.output_data_format == _CH_LAST_STR else (b, c, frames, k)
+        return _ffi.shape_of(self.output_data_format, b, c, frames, int(self.n_fft) // 2 + 1)
 
     def call(self, x):
         """(batch, time, ch) or (batch, ch, time) float -> complex64 STFT (reference :146-187).
@@ -264,6 +219,12 @@ def _complex_f64(x, layer_f64: bool) -> bool:
     if name == 'complex64':
         return False
     return layer_f64
+
+
+def _as_device_complex(x, layer_f64: bool):
+    import torch
+
+    return _ffi.as_device(x, torch.complex128 if _complex_f64(x, layer_f64) else torch.complex64)
 
 
 @register_keras_serializable(package='Kapre')
@@ -315,10 +276,9 @@ class InverseSTFT(Layer):
 
     def compute_output_shape(self, input_shape):
         """(b, frame, freq, ch) / (b, ch, frame, freq) -> (b, (frame - 1) hop + win, ch) / (b, ch, ...): untrimmed, as upstream"""
-        b, f, c = (input_shape[0], input_shape[1], input_shape[3]) if self.input_data_format == _CH_LAST_STR else \
-                  (input_shape[0], input_shape[2], input_shape[1])
+        b, c, f, _ = _ffi.dims_of(input_shape, self.input_data_format)
         t = None if f is None else ((int(f) - 1) * int(self.hop_length) + int(self.win_length) if int(f) > 0 else 0)
-        return (b, t, c) if self.output_data_format == _CH_LAST_STR else (b, c, t)
+        return _ffi.shape_of(self.output_data_format, b, c, t)
 
     def call(self, x):
         if autograd.needs_grad(x):
@@ -328,14 +288,10 @@ class InverseSTFT(Layer):
     def _forward(self, x):
         import torch
 
-        f64 = _complex_f64(x, self._f64)
-        x = _ffi.as_device_dtype(x, torch.complex128) if f64 else _ffi.as_device_c64(x)
+        x = _as_device_complex(x, self._f64)
         if x.dim() != 4:
             raise ValueError('InverseSTFT expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-        if self.input_data_format == _CH_LAST_STR:
-            b, f, k, c = x.shape
-        else:
-            b, c, f, k = x.shape
+        k = _ffi.dims_of(x.shape, self.input_data_format)[3]
         k_need = int(self.n_fft) // 2 + 1
         if k != k_need:
             # tf.signal.irfft crops / zero-pads the frequency axis to n_fft//2+1
@@ -346,32 +302,14 @@ class InverseSTFT(Layer):
                 pad = [0, 0] * (x.dim() - 1 - axis) + [0, k_need - k]
                 x = torch.nn.functional.pad(torch.view_as_real(x), [0, 0] + pad)
                 x = torch.view_as_complex(x.contiguous())
-        # StftGeom: in_layout = waveform layout, out_layout = spectrogram layout
-        g = _ffi.StftGeom(b, c, 0, int(self.n_fft), int(self.win_length), int(self.hop_length), 0, 0,
-                          _ffi.layout(self.output_data_format), _ffi.layout(self.input_data_format))
-        t_out = (f - 1) * int(self.hop_length) + int(self.win_length) if f > 0 else 0
-        shape = (b, t_out, c) if self.output_data_format == _CH_LAST_STR else (b, c, t_out)
-        L = _ffi.lib()
-        if f64:
-            out = torch.empty(shape, dtype=torch.float64, device=x.device)
+        # float32 uses window_fn's own values; float64 recomputes them in float64 (backend.window_values)
+        if x.dtype == torch.complex128:
             win = self._consts.get('synth64', x.device,
                                    lambda: backend.window_values(self.window_fn, int(self.win_length), np.float64))
-            with torch.cuda.device(x.device):
-                ws_bytes = int(L.kpr_istft_f64_workspace_bytes(ctypes.byref(g), f))
-                ws = _workspace(ws_bytes, x.device)
-                _ffi.check(L.kpr_istft_f64(_ffi.ptr(x), ctypes.byref(g), f, _ffi.ptr(win), _ffi.ptr(out),
-                                           _ffi.ptr(ws), ws_bytes, _ffi.current_stream_ptr()),
-                           'kpr_istft_f64')
-            return out
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        win = self._consts.get('synth', x.device, lambda: self.window_fn(int(self.win_length)))
-        with torch.cuda.device(x.device):
-            ws_bytes = int(L.kpr_istft_workspace_bytes(ctypes.byref(g), f))
-            ws = _workspace(ws_bytes, x.device)
-            _ffi.check(L.kpr_istft_f32(_ffi.ptr(x), ctypes.byref(g), f, _ffi.ptr(win), _ffi.ptr(out),
-                                       _ffi.ptr(ws), ws_bytes, _ffi.current_stream_ptr()),
-                       'kpr_istft_f32')
-        return out
+        else:
+            win = self._consts.get('synth', x.device, lambda: self.window_fn(int(self.win_length)))
+        return _ffi.istft(x, win, self.n_fft, self.win_length, self.hop_length, self.output_data_format,
+                          self.input_data_format)
 
     def get_config(self):
         config = super(InverseSTFT, self).get_config()
@@ -398,21 +336,7 @@ class Magnitude(Layer):
         return self._forward(x)
 
     def _forward(self, x):
-        import torch
-
-        if _complex_f64(x, self._f64):
-            x = _ffi.as_device_dtype(x, torch.complex128)
-            out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
-            with torch.cuda.device(x.device):
-                _ffi.check(_ffi.lib().kpr_abs_c128(_ffi.ptr(x), x.numel(), _ffi.ptr(out),
-                           _ffi.current_stream_ptr()), 'kpr_abs_c128')
-            return out
-        x = _ffi.as_device_c64(x)
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().kpr_abs_c64(_ffi.ptr(x), x.numel(), _ffi.ptr(out),
-                                              _ffi.current_stream_ptr()), 'kpr_abs_c64')
-        return out
+        return _ffi.cplx_to_real(_as_device_complex(x, self._f64), phase=False)
 
 
 @register_keras_serializable(package='Kapre')
@@ -434,21 +358,7 @@ class Phase(Layer):
         return self._forward(x)
 
     def _forward(self, x):
-        import torch
-
-        if _complex_f64(x, self._f64):
-            x = _ffi.as_device_dtype(x, torch.complex128)
-            out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
-            with torch.cuda.device(x.device):
-                _ffi.check(_ffi.lib().kpr_angle_c128(_ffi.ptr(x), x.numel(), _ffi.ptr(out),
-                           _ffi.current_stream_ptr()), 'kpr_angle_c128')
-            return out
-        x = _ffi.as_device_c64(x)
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().kpr_angle_c64(_ffi.ptr(x), x.numel(), _ffi.ptr(out),
-                                                _ffi.current_stream_ptr()), 'kpr_angle_c64')
-        return out
+        return _ffi.cplx_to_real(_as_device_complex(x, self._f64), phase=True)
 
     def get_config(self):
         config = super(Phase, self).get_config()
@@ -477,7 +387,7 @@ class MagnitudeToDecibel(Layer):
         import torch
 
         # Keras autocast: the layer dtype decides the compute dtype, then the backend follows its input
-        x = _ffi.as_device_dtype(x, torch.float64) if self._f64 else _ffi.as_device_f32(x)
+        x = _ffi.as_device(x, torch.float64 if self._f64 else torch.float32)
         return backend.magnitude_to_decibel(
             x, ref_value=self.ref_value, amin=self.amin, dynamic_range=self.dynamic_range
         )
@@ -606,30 +516,19 @@ class ApplyFilterbank(Layer):
     def _forward(self, x):
         import torch
 
-        f64 = self._f64
-        x = _ffi.as_device_dtype(x, torch.float64) if f64 else _ffi.as_device_f32(x)
+        x = _ffi.as_device(x, torch.float64 if self._f64 else torch.float32)
         if x.dim() != 4:
             raise ValueError('ApplyFilterbank expects a rank-4 input, got shape %s'
                              % (tuple(x.shape),))
-        if self.data_format == _CH_LAST_STR:
-            b, f, k, c = x.shape
-        else:
-            b, c, f, k = x.shape
+        k = _ffi.dims_of(x.shape, self.data_format)[3]
         n_freq, n_filt = self.filterbank.shape
         if k != n_freq:
             raise ValueError('frequency axis has %d bins but the filterbank expects %d'
                              % (k, n_freq))
-        shape = (b, f, n_filt, c) if self.data_format == _CH_LAST_STR else (b, c, f, n_filt)
-        if f64:
+        if self._f64:
             # the filterbank itself is floatx (float32) upstream as well (backend.py:231, :296); cast like TF does
-            out = torch.empty(shape, dtype=torch.float64, device=x.device)
             fb64 = self._consts.get('fb64', x.device, lambda: np.asarray(self.filterbank, np.float64))
-            with torch.cuda.device(x.device):
-                _ffi.check(_ffi.lib().kpr_apply_filterbank_f64(
-                    _ffi.ptr(x), b, c, f, n_freq, _ffi.layout(self.data_format), _ffi.ptr(fb64), n_filt,
-                    _ffi.ptr(out), _ffi.current_stream_ptr()), 'kpr_apply_filterbank_f64')
-            return out
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+            return _ffi.freq_matmul(x, self.data_format, fb64)
         kr = self._fb_kranges()
         packed = None
         thin = n_filt <= 64 and n_freq <= 512 and n_freq % 4 == 0          # the thin GEMM takes these
@@ -638,13 +537,7 @@ class ApplyFilterbank(Layer):
                 packed = self._fb_packed_device(x.device)      # wide banded matrix: MFMA consumer path
             except RuntimeError:
                 packed = None                                   # band too wide to pack: generic GEMM
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().kpr_apply_filterbank_packed_f32(
-                _ffi.ptr(x), b, c, f, n_freq, _ffi.layout(self.data_format),
-                _ffi.ptr(self._fb_device(x.device)), _ffi.ptr(packed), n_filt,
-                kr.ctypes.data_as(ctypes.c_void_p), _ffi.ptr(out), _ffi.current_stream_ptr()),
-                'kpr_apply_filterbank_packed_f32')
-        return out
+        return _ffi.freq_matmul(x, self.data_format, self._fb_device(x.device), packed, kr)
 
     def get_config(self):
         config = super(ApplyFilterbank, self).get_config()
@@ -694,20 +587,10 @@ class Delta(Layer):
     def _forward(self, x):
         import torch
 
-        x = _ffi.as_device_f32(x)
+        x = _ffi.as_device(x, torch.float32)
         if x.dim() != 4:
             raise ValueError('Delta expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-        if self.data_format == _CH_LAST_STR:
-            b, t, f, c = x.shape
-        else:
-            b, c, t, f = x.shape
-        out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().kpr_delta_f32(
-                _ffi.ptr(x), b, c, t, f, _ffi.layout(self.data_format), self.win_length,
-                _ffi.PAD_MODES[self.mode.lower()], _ffi.ptr(out), _ffi.current_stream_ptr()),
-                'kpr_delta_f32')
-        return out
+        return _ffi.delta(x, self.data_format, self.win_length, self.mode)
 
     def get_config(self):
         config = super(Delta, self).get_config()
@@ -731,13 +614,10 @@ class _MelPlan:
 def _mel_plan(stft, fb_layer, db_layer, x, stream_ptr):
     import torch
 
-    L = _ffi.lib()
     plan = _MelPlan()
     plan.g = stft._geom(x)
     plan.g_ref = ctypes.byref(plan.g)
-    n_frames = int(L.kpr_num_frames(plan.g_ref))
-    if n_frames < 0:
-        _ffi.check(-1, 'kpr_num_frames')
+    n_frames = _ffi.num_frames(plan.g)
     n_freq, n_filt = fb_layer.filterbank.shape
     if n_freq != int(stft.n_fft) // 2 + 1:
         raise ValueError('filterbank has %d frequency rows but the STFT produces %d bins'
@@ -745,7 +625,7 @@ def _mel_plan(stft, fb_layer, db_layer, x, stream_ptr):
     plan.n_filt = n_filt
     plan.db = db_layer._db_params() if db_layer is not None else _ffi.DbParams(0, 1.0, 1e-5, 80.0)
     plan.db_ref = ctypes.byref(plan.db)
-    plan.out_shape = stft._out_shape(plan.g, n_frames, n_filt)
+    plan.out_shape = _ffi.shape_of(plan.g.out_layout, plan.g.batch, plan.g.channels, n_frames, n_filt)
     plan.fb_layer, plan.db_layer = fb_layer, db_layer       # keep the key's objects alive (no id() reuse)
     plan.win = stft._window(x.device)
     plan.win_ptr = _ffi.ptr(plan.win)
@@ -756,11 +636,7 @@ def _mel_plan(stft, fb_layer, db_layer, x, stream_ptr):
     except RuntimeError:
         plan.fbp = None                 # more filter tiles than the packed schedule holds: generic product
     plan.fbp_ptr = _ffi.ptr(plan.fbp)
-    # without a packed filterbank kpr_mel_f32 takes its two-kernel path, which stages the spectrum in the workspace
-    plan.ws_bytes = int(L.kpr_mel_workspace_bytes(plan.g_ref, n_filt, plan.db_ref) if plan.fbp is not None
-                        else L.kpr_mel_workspace_bytes_unpacked(plan.g_ref, n_filt))
-    if plan.ws_bytes < 0:
-        _ffi.check(-1, 'kpr_mel_workspace_bytes')
+    plan.ws_bytes = _ffi.mel_workspace_bytes(plan.g_ref, n_filt, plan.db_ref, plan.fbp is not None)
     plan.ws = _PLAN_WORKSPACES.get(plan.ws_bytes, x.device, stream_ptr)
     plan.ws_ptr = _ffi.ptr(plan.ws)
     plan.kr = fb_layer._fb_kranges()
@@ -773,7 +649,7 @@ def fused_melspectrogram(stft: STFT, fb_layer: ApplyFilterbank, db_layer, x):
     """STFT -> Magnitude -> ApplyFilterbank [-> MagnitudeToDecibel] in one launch (kpr_mel_f32)."""
     import torch
 
-    x = _ffi.as_device_f32(x)
+    x = _ffi.as_device(x, torch.float32)
     dev = x.device
     stream_ptr = torch.cuda.current_stream(dev).cuda_stream
     db_key = None if db_layer is None else (db_layer.ref_value, db_layer.amin, db_layer.dynamic_range)
@@ -787,27 +663,26 @@ def fused_melspectrogram(stft: STFT, fb_layer: ApplyFilterbank, db_layer, x):
         plan = cache[key] = _mel_plan(stft, fb_layer, db_layer, x, stream_ptr)
     out = torch.empty(plan.out_shape, dtype=torch.float32, device=dev)
     L = _ffi.lib()
+
+    def launch():
+        return L.kpr_mel_f32(x.data_ptr(), plan.g_ref, plan.win_ptr, plan.fb_ptr, plan.fbp_ptr, plan.n_filt,
+                             plan.kr_ptr, plan.db_ref, out.data_ptr(), plan.ws_ptr, plan.ws_bytes, plan.stream)
+
     if torch.cuda.current_device() != dev.index:
         with torch.cuda.device(dev):
-            rc = L.kpr_mel_f32(x.data_ptr(), plan.g_ref, plan.win_ptr, plan.fb_ptr, plan.fbp_ptr,
-                               plan.n_filt, plan.kr_ptr, plan.db_ref, out.data_ptr(), plan.ws_ptr,
-                               plan.ws_bytes, plan.stream)
+            rc = launch()
     else:
-        rc = L.kpr_mel_f32(x.data_ptr(), plan.g_ref, plan.win_ptr, plan.fb_ptr, plan.fbp_ptr,
-                           plan.n_filt, plan.kr_ptr, plan.db_ref, out.data_ptr(), plan.ws_ptr,
-                           plan.ws_bytes, plan.stream)
+        rc = launch()
     if rc == -4 and plan.fbp is not None:
         # KPR_E_WORKSPACE: a bank whose schedule none of the fused kernels holds (dense matrices): the two-launch path stages the
-        # spectrum and needs kpr_mel_workspace_bytes_unpacked() -- the plan is upgraded once and keeps the larger workspace
-        ws_bytes = int(L.kpr_mel_workspace_bytes_unpacked(plan.g_ref, plan.n_filt))
+        # spectrum and needs the unpacked workspace -- the plan is upgraded once and keeps the larger workspace
+        ws_bytes = _ffi.mel_workspace_bytes(plan.g_ref, plan.n_filt, plan.db_ref, False)
         if ws_bytes > plan.ws_bytes:
             plan.ws_bytes = ws_bytes
             plan.ws = _PLAN_WORKSPACES.get(plan.ws_bytes, dev, stream_ptr)
             plan.ws_ptr = _ffi.ptr(plan.ws)
             with torch.cuda.device(dev):
-                rc = L.kpr_mel_f32(x.data_ptr(), plan.g_ref, plan.win_ptr, plan.fb_ptr, plan.fbp_ptr,
-                                   plan.n_filt, plan.kr_ptr, plan.db_ref, out.data_ptr(), plan.ws_ptr,
-                                   plan.ws_bytes, plan.stream)
+                rc = launch()
     if rc:
         _ffi.check(rc, 'kpr_mel_f32')
     return out
