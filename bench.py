@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the Kapre time-frequency hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic waveforms already resident in HBM.
 
@@ -11,6 +11,13 @@ PER GPU (weak scaling: the batch axis shards with no data-path collective; RCCL 
 broadcast the filterbank).  `metric`/`unit` are BASELINE.json's; `value` = frames of all ranks / wall
 time of the K timed steps (barrier + synchronize on both sides, max over ranks).
 
+A plain run measures the headline and nothing else: set-up, the hipGraph replays of the headline step that --full times
+(`--settle` seconds on one buffer pair, then up to 0.5 s on rotating buffers), untimed, so that the K timed steps start from the
+same state (settled clocks), W warm-up + K timed steps, --dump-outputs, the result line.
+
+--full adds everything else: the headline's kernel time and rooflines (`kernel_us`, HBM / compute fractions, rotating-buffer
+figures: the same replays, timed), then, after the headline's timed steps, `sclk_mhz`, the `also` rows, the CPU baseline and
+the sustained rate.
 `also` (same JSON line) carries the other BASELINE.json configs, each timed the same way with its own
 algorithmic-bytes roofline: cfg2 (batch 64), cfg3 channels_last / channels_first (LogMel + dB, 256 x 6ch),
 cfg4 forward (kpr_stft_f32) and inverse (kpr_istft_f32), cfg5 one GPU's share (256 items) -- and cfg5
@@ -20,10 +27,10 @@ that the per-N lines hold both a weak (headline) and a strong (configs[4]) scali
 For N > 1 the driver launches this file with torch.distributed.run (one rank per GPU).
 
 Output.  The LAST stdout line is the result: ONE compact JSON object (< 4 KB; tests/test_bench_line.py holds it to
-that) with the contract's keys + `roofline`, `roofline_compute`, `cpu_baseline`, `gpu_over_cpu`, `sustained` and a
-one-row-per-workload `also` summary.  Everything longer -- per-workload detail, the CPU sweep, the notes on how to read
-the fractions -- goes to gpurun_out/bench_full.json and to earlier stdout lines (one small JSON object per `also`
-workload).  (Round 3 printed all of it on one 22 KB line; the driver keeps 8 KB of stdout and could not parse it.)
+that) with the contract's keys; under --full also `roofline`, `roofline_compute`, `cpu_baseline`, `gpu_over_cpu`,
+`sustained` and a one-row-per-workload `also` summary.  Everything longer -- per-workload detail, the CPU sweep, the notes
+on how to read the fractions -- goes to earlier stdout lines (one small JSON object per `also` workload) and, with
+--detail FILE, to FILE.  (Round 3 printed all of it on one 22 KB line; the driver keeps 8 KB of stdout and could not parse it.)
 
 --dump-outputs DIR: after the timed steps, what the headline workload's last timed step returned to its caller is written as
 DIR/<workload>.npy (DIR/<workload>_rank<r>.npy for N > 1), float32 or float64, complex as a trailing axis of 2.  The inputs are
@@ -259,22 +266,8 @@ def kernel_time_us(model, x, launches=100, settle_s=0.0, rotate=None):
     in the Infinity Cache by the step before -- DRAM bandwidth, not MALL bandwidth)."""
     import torch
 
-    model(x)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
     try:
-        with torch.cuda.stream(side):
-            model(x)                                   # plan + first-use table uploads for this stream
-            side.synchronize()
-            with torch.cuda.graph(graph, stream=side):
-                ring = [None] * (len(rotate) if rotate else 1)
-                for i in range(launches):
-                    ring[i % len(ring)] = model(rotate[i % len(rotate)] if rotate else x)
-                del ring
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
+        graph = step_graph(model, x, launches, rotate)
         t0 = time.perf_counter()
         while settle_s > 0 and time.perf_counter() - t0 < settle_s:
             for _ in range(10):
@@ -301,6 +294,44 @@ def kernel_time_us(model, x, launches=100, settle_s=0.0, rotate=None):
         ev1.record()
         torch.cuda.synchronize()
         return ev0.elapsed_time(ev1) * 1e3 / launches, "back-to-back launches, HIP events (%s)" % type(e).__name__
+
+
+def step_graph(model, x, launches=100, rotate=None):
+    """`launches` steps captured into one hipGraph on a side stream (after the plan and first-use table uploads for that
+    stream), replayed once.  rotate: as in kernel_time_us."""
+    import torch
+
+    model(x)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        model(x)
+        side.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            ring = [None] * (len(rotate) if rotate else 1)
+            for i in range(launches):
+                ring[i % len(ring)] = model(rotate[i % len(rotate)] if rotate else x)
+            del ring
+    torch.cuda.synchronize()
+    graph.replay()
+    torch.cuda.synchronize()
+    return graph
+
+
+def settle_clocks(model, x, seconds, rotate=None):
+    """The replays of kernel_time_us(model, x, settle_s=seconds, rotate=rotate) without the timing: `seconds` of back-to-back
+    replays of a hipGraph of 100 steps.  The part reaches its settled clocks only after tens of milliseconds of continuous
+    work, and the K timed steps of a short run are ~1 ms of it."""
+    import torch
+
+    graph = step_graph(model, x, rotate=rotate)
+    t0 = time.perf_counter()
+    while seconds > 0 and time.perf_counter() - t0 < seconds:
+        for _ in range(10):
+            graph.replay()
+        torch.cuda.synchronize()
+    del graph
 
 
 def cpu_baseline(w, screen_s=1.0, final_s=3.0, top=2, rounds=3):
@@ -515,17 +546,24 @@ def measure(name, w, rank, world, device, steps, warmup, with_kernel=True, settl
     kernel = _ffi.last_launches()                      # what the library dispatched for this shape (not a table here)
     # the kernel-time measurement (a hipGraph of 100 steps replayed for settle_s, then timed) runs FIRST and on every rank:
     # it also brings the GPU to its settled clocks, so that a short timed run (the driver uses K = 20, W = 5: ~1 ms of GPU
-    # work) measures the steady state and not the power-management ramp (45 vs 39.6 us per step on the headline)
+    # work) measures the steady state and not the power-management ramp (45 vs 39.6 us per step on the headline).  Without the
+    # kernel time (with_kernel False) the same replays run untimed: the timed steps start from the state they leave the part in,
+    # and a short run's value depends on it (K = 20: ~3 % faster after the replay of one buffer pair than after both replays).
     k_us, how = kernel_time_us(model, x, settle_s=settle_s) if with_kernel else (None, None)
+    if not with_kernel:
+        settle_clocks(model, x, settle_s)
     k_rot, n_rot = None, 0
-    if with_kernel and rotating:
+    if rotating:
         # as many distinct (input, output) buffer pairs as it takes to pass 2 x 256 MiB (at least 5): DRAM, not MALL, figures
         y0 = model(x)
         pair_bytes = x.numel() * x.element_size() + y0.numel() * y0.element_size()
         del y0
         n_rot = int(min(64, max(5, -(-(2 * 256 * 2 ** 20) // pair_bytes))))
         xs = [x] + [make_input(w, rank + 17 * (i + 1), device, batch) for i in range(n_rot - 1)]
-        k_rot, _ = kernel_time_us(model, x, settle_s=min(settle_s, 0.5), rotate=xs)
+        if with_kernel:
+            k_rot, _ = kernel_time_us(model, x, settle_s=min(settle_s, 0.5), rotate=xs)
+        else:
+            settle_clocks(model, x, min(settle_s, 0.5), rotate=xs)
         del xs
     dt, dev_ms, y = timed_steps(model, x, steps, warmup, world)
     last_output = host_arrays(y) if keep_output else None
@@ -575,19 +613,7 @@ def sustained(name, w, rank, world, device, seconds):
     batch = w["batch"] // world if w.get("strong") else w["batch"]
     model = build_model(w)
     x = make_input(w, rank, device, batch)
-    model(x)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        model(x)
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            for _ in range(100):
-                model(x)
-    torch.cuda.synchronize()
-    graph.replay()
-    torch.cuda.synchronize()
+    graph = step_graph(model, x)
     n, t0 = 0, time.perf_counter()
     while True:
         for _ in range(20):                                   # ~0.1 s of queued work per host round trip
@@ -609,10 +635,10 @@ def _r(v, nd=4):
     return v
 
 
-def compact_line(result, also, cap=4000):
-    """The final stdout line: the contract's keys + roofline / roofline_compute / cpu_baseline / gpu_over_cpu /
-    sustained + one short row per `also` workload, without the explanatory strings; shrinks the `also` rows if the
-    line would pass `cap` bytes."""
+def compact_line(result, also, cap=4000, detail=None):
+    """The final stdout line: the contract's keys + whichever of roofline / roofline_compute / cpu_baseline / gpu_over_cpu /
+    sustained the run measured + one short row per `also` workload, without the explanatory strings, + `detail` (the file
+    that holds the full record) when given; shrinks the `also` rows if the line would pass `cap` bytes."""
     keep = ["metric", "value", "unit", "audio_sec_per_sec", "n_gpus", "steps", "warmup", "ms_per_step", "settle_s",
             "device_ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
             "primary_time", "value_device_time", "rccl_ranks", "dist_backend", "sclk_mhz", "kernel_frames_per_s"]
@@ -660,8 +686,10 @@ def compact_line(result, also, cap=4000):
         if (a.get("roofline_compute") or {}).get("bound") == "mfma":
             row["mfma_frac"] = _r(a["roofline_compute"]["frac"], 3)
         rows.append(row)
-    line["also"] = rows
-    line["detail"] = "gpurun_out/bench_full.json"
+    if rows:
+        line["also"] = rows
+    if detail:
+        line["detail"] = detail
     if len(json.dumps(line)) > cap:
         for r_ in rows:
             r_.pop("kernel", None)
@@ -673,21 +701,74 @@ def compact_line(result, also, cap=4000):
     return line
 
 
+def measure_more(args, w, head, result, rank, world, device):
+    """--full, after the headline's timed steps: sclk_mhz and the headline's kernel time and rooflines into `result` (rank 0),
+    the `also` workloads, the CPU baseline and the sustained rate.  Returns the `also` results."""
+    from kapre_amd import _ffi
+
+    if rank == 0:
+        try:
+            result["sclk_mhz"] = round(_ffi.sclk_mhz(), 1)        # under a dense packed-f32 load (2400 = spec maximum)
+        except Exception:  # noqa: BLE001
+            result["sclk_mhz"] = None
+        result["roofline"] = head.get("roofline")
+        if head.get("roofline_compute"):
+            result["roofline_compute"] = head["roofline_compute"]
+        result["kernel_frames_per_s"] = head["frames_per_step_per_gpu"] / (head["kernel_us"] * 1e-6)
+        if world > 1:
+            result["kernel_us_per_rank"] = head.get("kernel_us_per_rank")     # every rank's own hipGraph figure for the headline step
+
+    also = []
+    if not args.no_also and args.workload == DEFAULT:
+        sub_steps, sub_warm = max(10, min(args.steps, 50)), max(3, min(args.warmup, 10))
+        # configs[4] strong-scaled over the ranks: every rank takes part (2048 / N items each)
+        also.append(measure(STRONG, WORKLOADS[STRONG], rank, world, device, max(5, sub_steps // 5), sub_warm))
+        if world == 1:
+            for name in ALSO_N1:
+                also.append(measure(name, WORKLOADS[name], rank, world, device, sub_steps, sub_warm))
+    if rank == 0:
+        for a in also:                                            # one small line per workload, BEFORE the result line
+            print(json.dumps({"also": a["workload"], "value": _r(a["value"]), "unit": a["unit"],
+                              "kernel_us": _r(a.get("kernel_us")), "ms_per_step": _r(a["ms_per_step"]),
+                              "roofline_frac": _r((a.get("roofline") or {}).get("frac")),
+                              "kernel": (a.get("roofline") or {}).get("kernel")}), flush=True)
+    if rank == 0 and not args.no_cpu_baseline:
+        # at every N (round 5): rank 0's host cores, while the other ranks wait at the barrier below -- outside every timed
+        # region.  gpu_over_cpu stays the ONE-GPU ratio: the N = 1-equivalent rate of this rank over the CPU figure.
+        result["cpu_baseline"] = cpu_baseline(w)
+        one_gpu = result["value"] if world == 1 else head["frames_per_step_per_gpu"] / (head["ms_per_step"] * 1e-3)
+        result["gpu_over_cpu"] = one_gpu / result["cpu_baseline"]["value"]
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    if args.sustain > 0:
+        sv, sec, nsteps = sustained(args.workload, w, rank, world, device, args.sustain)
+        result["sustained"] = {"value": sv, "unit": head["unit"], "seconds": sec, "steps": nsteps,
+                               "us_per_step": sec / nsteps * 1e6}
+    return also
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default=DEFAULT, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true")
-    ap.add_argument("--sustain", type=float, default=10.0, help="seconds of continuous headline replay at the end (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the headline's kernel time and rooflines, the other workloads, the CPU baseline and the sustained rate")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full without the other workloads")
+    ap.add_argument("--sustain", type=float, default=10.0, help="--full: seconds of continuous headline replay at the end (0 = off)")
     ap.add_argument("--settle", type=float, default=1.5, help="seconds of continuous replay before the headline is timed (clock settling)")
+    ap.add_argument("--detail", metavar="FILE", default=None,
+                    help="--full: write the full record (every workload's detail, the CPU sweep, notes) to FILE as JSON")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline's last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MiB)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.detail and not args.full:
+        ap.error("--detail needs --full")
 
     import torch
     from kapre_amd import dist as kdist
@@ -703,7 +784,7 @@ def main():
     torch.cuda.set_device(device)
 
     w = WORKLOADS[args.workload]
-    head = measure(args.workload, w, rank, world, device, args.steps, args.warmup, settle_s=args.settle,
+    head = measure(args.workload, w, rank, world, device, args.steps, args.warmup, with_kernel=args.full, settle_s=args.settle,
                    keep_output=args.dump_outputs is not None)
     dumped = None
     if args.dump_outputs is not None:
@@ -738,55 +819,15 @@ def main():
         result["rccl_ranks"] = dist.get_world_size()
         result["rank_devices"] = names
         result["dist_backend"] = dist.get_backend()
-        result["kernel_us_per_rank"] = head.get("kernel_us_per_rank")     # every rank's own hipGraph figure for the headline step
+    also = measure_more(args, w, head, result, rank, world, device) if args.full else []
     if rank == 0:
-        try:
-            result["sclk_mhz"] = round(_ffi.sclk_mhz(), 1)        # under a dense packed-f32 load (2400 = spec maximum)
-        except Exception:  # noqa: BLE001
-            result["sclk_mhz"] = None
-        result["roofline"] = head.get("roofline")
-        if head.get("roofline_compute"):
-            result["roofline_compute"] = head["roofline_compute"]
-        result["kernel_frames_per_s"] = head["frames_per_step_per_gpu"] / (head["kernel_us"] * 1e-6)
-
-    also = []
-    if not args.no_also and args.workload == DEFAULT:
-        sub_steps, sub_warm = max(10, min(args.steps, 50)), max(3, min(args.warmup, 10))
-        # configs[4] strong-scaled over the ranks: every rank takes part (2048 / N items each)
-        also.append(measure(STRONG, WORKLOADS[STRONG], rank, world, device, max(5, sub_steps // 5), sub_warm))
-        if world == 1:
-            for name in ALSO_N1:
-                also.append(measure(name, WORKLOADS[name], rank, world, device, sub_steps, sub_warm))
-    if rank == 0:
-        for a in also:                                            # one small line per workload, BEFORE the result line
-            print(json.dumps({"also": a["workload"], "value": _r(a["value"]), "unit": a["unit"],
-                              "kernel_us": _r(a.get("kernel_us")), "ms_per_step": _r(a["ms_per_step"]),
-                              "roofline_frac": _r((a.get("roofline") or {}).get("frac")),
-                              "kernel": (a.get("roofline") or {}).get("kernel")}), flush=True)
-    if rank == 0 and not args.no_cpu_baseline:
-        # at every N (round 5): rank 0's host cores, while the other ranks wait at the barrier below -- outside every timed
-        # region.  gpu_over_cpu stays the ONE-GPU ratio: the N = 1-equivalent rate of this rank over the CPU figure.
-        result["cpu_baseline"] = cpu_baseline(w)
-        one_gpu = result["value"] if world == 1 else head["frames_per_step_per_gpu"] / (head["ms_per_step"] * 1e-3)
-        result["gpu_over_cpu"] = one_gpu / result["cpu_baseline"]["value"]
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-    if args.sustain > 0:
-        sv, sec, nsteps = sustained(args.workload, w, rank, world, device, args.sustain)
-        result["sustained"] = {"value": sv, "unit": head["unit"], "seconds": sec, "steps": nsteps,
-                               "us_per_step": sec / nsteps * 1e6}
-    if rank == 0:
-        full = dict(result)
-        full["also"] = also
-        full["notes"] = NOTES
-        try:
-            os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(REPO, "gpurun_out", "bench_full.json"), "w") as f:
+        if args.detail:
+            full = dict(result)
+            full["also"] = also
+            full["notes"] = NOTES
+            with open(args.detail, "w") as f:
                 json.dump(full, f, indent=1)
-        except OSError:
-            pass
-        print(json.dumps(compact_line(result, also)), flush=True)
+        print(json.dumps(compact_line(result, also, detail=args.detail)), flush=True)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

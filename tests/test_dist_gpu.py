@@ -66,13 +66,14 @@ def test_rccl_path_at_world_size_one(tmp_path):
 
 
 def test_bench_n1_line_under_the_driver_command(tmp_path):
-    """the driver's own N = 1 command with a short K: the last stdout line parses, is below 4 KB and carries roofline (with the
-    rotating-buffer figures and the provenance of `traffic`) and cpu_baseline"""
+    """the driver's N = 1 command with --full and a short K: the last stdout line parses, is below 4 KB and carries roofline (with
+    the rotating-buffer figures and the provenance of `traffic`) and cpu_baseline"""
     import json
     env = dict(os.environ)
     env.update({"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-also",
-                        "--sustain", "0", "--settle", "0.2"], env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full",
+                        "--no-also", "--sustain", "0", "--settle", "0.2"], env=env, capture_output=True, text=True, timeout=600,
+                       cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     last = p.stdout.strip().splitlines()[-1]
     assert len(last) < 4000
@@ -83,3 +84,33 @@ def test_bench_n1_line_under_the_driver_command(tmp_path):
     rf = line["roofline"]
     assert rf["bound"] == "hbm" and rf["kernel"].startswith("k_mel_pw<1024") and rf["kernel_us_rotating"] > 0
     assert line["cpu_baseline"]["cores"] >= 1 and line["cpu_baseline"]["screened"]
+
+
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """the driver's N = 1 command without --full: the result line holds the contract's keys and nothing that --full measures,
+    and --dump-outputs writes the headline's last timed output (one mel row per frame)"""
+    import json
+    import numpy as np
+    env = dict(os.environ)
+    env.update({"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--settle", "0.2",
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.strip().splitlines()
+    line = json.loads(lines[-1])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in line, k
+    assert line["metric"] == "mel-frames/sec" and line["unit"] == "mel-frames/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["steps"] == 5 and line["warmup"] == 2
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    frames = line["config"]["frames_per_step_per_gpu"]
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - frames) < 1e-6 * frames
+    for k in ("roofline", "roofline_compute", "cpu_baseline", "gpu_over_cpu", "sustained", "also", "sclk_mhz", "kernel_frames_per_s",
+              "detail"):
+        assert k not in line, k
+    assert not any(l.startswith('{"also"') for l in lines)
+    name = line["config"]["workload"]
+    a = np.load(out / (name + ".npy"))
+    assert a.dtype == np.float32 and a.shape[0] == line["config"]["per_gpu_batch"] and a.size == frames * line["config"]["n_mels"]
+    assert np.isfinite(a).all()

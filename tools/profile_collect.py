@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Distil gpurun_out/prof_<round>/ (written by tools/profile_round.sh on the GPU box) into
 profiles/: kernel statistics CSVs, per-counter CSV extracts for the mel kernel, the HBM traffic
-JSON that bench.py reads, and a counter summary.  Usage: tools/profile_collect.py r01"""
+JSON that bench.py reads, and a counter summary.  Usage: tools/profile_collect.py r01 [end_of_round.sh log directory]"""
 import csv, glob, json, os, shutil, sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,9 +107,11 @@ for w, spec in bench.WORKLOADS.items():
         json.dump(out, open(os.path.join(dst, "%s_sq_counters_%s.json" % (rnd, w)), "w"), indent=1)
 print(json.dumps({"traffic": traffic, "counters": summary}, indent=1))
 
-# the logs of tools/end_of_round.sh (GPU suite, stand-alone fuzz, bench line, multi-process rehearsal) of the same binary
+# the logs of tools/end_of_round.sh (GPU suite, stand-alone fuzz, bench line, multi-process rehearsal) of the same binary, from
+# its log directory (argument 2, default logs/)
+logs = sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "logs")
 for name in ("pytest_gpu_final.log", "fuzz_seed0.log", "fuzz_seed17.log", "fuzz_seed23.log", "bench_line.json", "bench_full.json",
              "rehearsal_n2_one_gpu.log"):
-    f = os.path.join(REPO, "gpurun_out", "%s_%s" % (rnd, name))
+    f = os.path.join(logs, "%s_%s" % (rnd, name))
     if os.path.exists(f) and os.path.getsize(f):
         shutil.copy(f, os.path.join(dst, "%s_%s" % (rnd, name)))

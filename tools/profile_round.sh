@@ -18,7 +18,7 @@ WL=$(python -c "import sys; sys.path.insert(0, '$REPO'); import bench; print(' '
 # 1. kernel statistics, one bench.py workload per run (--no-also / --workload: the kernel's AverageNs is then
 #    comparable with the kernel_us bench.py prints for that workload)
 for W in $WL; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- python $REPO/bench.py --steps 100 --warmup 10 --workload $W --no-also --no-cpu-baseline --sustain 0 > $OUT/bench_under_rocprof_$W.json 2> $OUT/stats_$W.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- python $REPO/bench.py --steps 100 --warmup 10 --workload $W --full --no-also --no-cpu-baseline --sustain 0 > $OUT/bench_under_rocprof_$W.json 2> $OUT/stats_$W.log
   prune
 done
 if [ "$2" = "stats" ]; then ls $OUT | head -40; exit 0; fi     # tools/profile_round.sh r03 stats: kernel statistics only

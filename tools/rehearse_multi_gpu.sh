@@ -7,4 +7,4 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd $REPO
 KAPRE_AMD_DIST_BACKEND=gloo KAPRE_AMD_SHARE_DEVICE=1 HSA_ENABLE_IPC_MODE_LEGACY=0 \
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port ${1:-29517} \
-    bench.py --gpus 2 --steps 50 --warmup 5
+    bench.py --gpus 2 --steps 50 --warmup 5 --full
