@@ -402,6 +402,41 @@ int kpr_energy_bwd_f32(const float* x, const float* g, int64_t batch, int channe
 int kpr_delta_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout,
                       int win_length, int pad_mode, float* gx, kpr_stream_t stream);
 
+/* ---- augmentation.py: SpecAugment and ChannelSwap (training-only layers) ---------------------------------------
+ * SpecAugment.  x / out: float32, n_items blocks of n_time x n_freq (one channel, so (B, T, F, 1) and (B, 1, T, F)
+ * are the same bytes).  table: device int32 [n_items][n_time_masks + n_freq_masks][2] = (first, last) INCLUSIVE
+ * (augmentation.py:211-214), time masks first.  At most 32 masks per axis (KPR_E_BADARG beyond).
+ *
+ * kpr_spec_augment_draw fills `table` on the device and adds 1 to the call counter: no host-to-device copy per step,
+ * and a captured graph draws a new table at every replay.
+ *   state : 16 bytes of device memory OWNED BY THE CALLER: uint64 seed, uint64 calls.  The caller initialises both
+ *           (calls usually 0) and must not touch them while a draw is in flight; two draws on one state must be
+ *           ordered (same stream, or events).
+ *   draws : Philox4x32-10, counter (item, mask, calls_lo, calls_hi), key (seed_lo, seed_hi) -> r0, r1;
+ *           width = mulhi32(r0, param), first = mulhi32(r1, limit - width), last = first + width
+ *           (param = the axis' mask parameter, limit = n_time / n_freq): 1 .. param elements inside the axis.
+ *           An entry depends on (seed, calls, item, mask) only -- never on the launch geometry.
+ *   errors: a mask parameter outside [1, axis length] on an axis that has masks -> KPR_E_BADARG.
+ *           One workgroup draws the whole table: at most 2^20 entries (n_items x masks; KPR_E_UNSUPPORTED beyond).
+ *
+ * kpr_spec_augment_apply_f32: out = mask_value on the elements whose frame lies in a time interval or whose bin lies
+ * in a frequency interval of the item, x elsewhere (bit for bit: NaN, Inf, -0 and denormals pass).
+ *   out != x: a copy (x is not modified; x and out must not overlap partially).  out == x: the same kernel in place.
+ *   n_freq <= 65536 (KPR_E_UNSUPPORTED beyond).
+ *   Intervals are clamped to the axes; with mask_value = 0 the call is the layer's own adjoint. */
+int kpr_spec_augment_draw(int32_t* table, int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq,
+                          int time_mask_param, int freq_mask_param, void* state, kpr_stream_t stream);
+int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table, int64_t n_items, int n_time_masks,
+                               int n_freq_masks, int n_time, int n_freq, float mask_value, kpr_stream_t stream);
+
+/* ChannelSwap (tf.gather along the channel axis): x, out viewed as (outer, n_ch, inner) elements of elem_bytes = 4
+ * (float32) or 8 (complex64); out[o][c][:] = x[o][perm_host[c]][:].  channels_first: outer = batch, inner = the rest;
+ * channels_last: outer = everything in front of the channel axis, inner = 1.
+ *   perm_host: n_ch HOST int32 in [0, n_ch) -- copied into the kernel arguments, so the call neither reads it later nor
+ *              copies anything to the device.  At most 64 channels (KPR_E_UNSUPPORTED beyond).  In place is not allowed. */
+int kpr_channel_gather(const void* x, void* out, int64_t outer, int n_ch, int64_t inner, int elem_bytes,
+                       const int32_t* perm_host, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

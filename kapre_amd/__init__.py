@@ -25,6 +25,9 @@ from .time_frequency import (
 from . import signal
 from .signal import Frame, Energy, LogmelToMFCC
 
+from . import augmentation
+from .augmentation import SpecAugment, ChannelSwap
+
 from .composed import (
     get_stft_magnitude_layer,
     get_melspectrogram_layer,
@@ -63,6 +66,8 @@ __all__ = [
     'Frame',
     'Energy',
     'LogmelToMFCC',
+    'SpecAugment',
+    'ChannelSwap',
     'get_stft_magnitude_layer',
     'get_melspectrogram_layer',
     'get_log_frequency_spectrogram_layer',

@@ -136,6 +136,14 @@ EXPORTS = {
     "kpr_delta_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_void_p, ctypes.c_void_p]),
+    # augmentation layers (kapre_amd/augmentation.py)
+    "kpr_spec_augment_draw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_spec_augment_apply_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                  ctypes.c_void_p]),
+    "kpr_channel_gather": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -523,4 +531,37 @@ def delta(x, fmt, win_length, mode: str, backward: bool = False):
     out = torch.empty_like(x)
     _call("kpr_delta_bwd_f32" if backward else "kpr_delta_f32", x.device, ptr(x), b, c, t, f, layout(fmt), win_length,
           PAD_MODES[mode.lower()], ptr(out))
+    return out
+
+
+# augmentation layers (kapre_amd/augmentation.py)
+def spec_augment_draw(state, n_items, n_time_masks, n_freq_masks, n_time, n_freq, time_mask_param, freq_mask_param):
+    """A fresh SpecAugment mask table, drawn on the device from ``state`` (int64[2] there: seed, calls; calls advances by
+    one): int32 (n_items, n_time_masks + n_freq_masks, 2) of inclusive (first, last), time masks first."""
+    import torch
+    table = torch.empty((n_items, n_time_masks + n_freq_masks, 2), dtype=torch.int32, device=state.device)
+    _call("kpr_spec_augment_draw", state.device, ptr(table), n_items, n_time_masks, n_freq_masks, n_time, n_freq,
+          int(time_mask_param), int(freq_mask_param), ptr(state))
+    return table
+
+
+def spec_augment_apply(x, table, n_time_masks, n_freq_masks, n_time, n_freq, mask_value, inplace=False):
+    """``mask_value`` on the masked elements of the float32 ``x`` (n_items blocks of n_time x n_freq), ``x`` elsewhere:
+    a new tensor, or with ``inplace`` ``x`` itself (the same kernel with out == x: no second buffer)."""
+    import torch
+    out = x if inplace else torch.empty_like(x)
+    _call("kpr_spec_augment_apply_f32", x.device, ptr(x), ptr(out), ptr(table), table.shape[0], n_time_masks, n_freq_masks,
+          n_time, n_freq, float(mask_value))
+    return out
+
+
+def channel_gather(x, ch_axis: int, perm):
+    """``x`` (float32 / complex64) with the channels of axis ``ch_axis`` in the order ``perm`` (tf.gather)."""
+    import torch
+    shape = tuple(x.shape)
+    outer = int(np.prod(shape[:ch_axis], dtype=np.int64))
+    inner = int(np.prod(shape[ch_axis + 1:], dtype=np.int64))
+    out = torch.empty_like(x)
+    perm_host = (ctypes.c_int32 * len(perm))(*[int(p) for p in perm])
+    _call("kpr_channel_gather", x.device, ptr(x), ptr(out), outer, shape[ch_axis], inner, x.element_size(), perm_host)
     return out

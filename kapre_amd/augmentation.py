@@ -1,0 +1,208 @@
+"""Augmentation layers -- the training-only layers of the reference's ``kapre/augmentation.py``: ``SpecAugment``
+(:115-326) and ``ChannelSwap`` (:17-112).  Constructor signatures, defaults, ``get_config`` keys and raised exception
+types are the reference's; with ``training`` in ``(None, False)`` both return their input OBJECT and launch nothing.
+
+``SpecAugment`` draws its masks on the device (``kpr_spec_augment_draw``: Philox4x32-10 over a 16-byte device state
+``(seed, calls)``), so a training step copies nothing from the host and a captured graph draws new masks at every
+replay.  The stream is this package's own: TensorFlow's generator is not reproduced (and could not be).  ``set_seed``
+makes runs repeatable; the layer's config carries no seed, as upstream.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from . import _ffi, autograd, backend
+from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
+from .keras_shim import Layer, register_keras_serializable
+
+__all__ = ['SpecAugment', 'ChannelSwap', 'set_seed']
+
+_seed = None          # what set_seed gave; None: OS entropy at the first use of a device
+_states = {}          # device index -> int64[2] on that device: (seed, calls) as kpr_spec_augment_draw reads them
+
+
+def _as_int64(v: int) -> int:
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def set_seed(seed: int) -> None:
+    """Seed SpecAugment's device generator: every device's state becomes ``(seed, calls = 0)`` -- the states that exist are
+    rewritten where they are (a captured graph keeps drawing from the address it recorded), the others start there."""
+    global _seed
+    import torch
+
+    _seed = int(seed)
+    for state in _states.values():
+        state.copy_(torch.tensor([_as_int64(_seed), 0], dtype=torch.int64))
+
+
+def device_state(device):
+    """The generator state of ``device`` (created on first use; not inside a graph capture: it is a host-to-device copy)."""
+    import torch
+
+    state = _states.get(device.index)
+    if state is None:
+        seed = _seed if _seed is not None else int.from_bytes(os.urandom(8), 'little')
+        state = _states[device.index] = torch.tensor([_as_int64(seed), 0], dtype=torch.int64).to(device)
+    return state
+
+
+def _resolve_format(data_format):
+    backend.validate_data_format_str(data_format)
+    if isinstance(data_format, dict):           # (the reference's workaround for a Keras deserialisation bug)
+        data_format = data_format['config']
+    return backend.image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+
+
+def _config_format(data_format):
+    return data_format if data_format in (_CH_FIRST_STR, _CH_LAST_STR) else 'default'
+
+
+@register_keras_serializable(package='Kapre')
+class ChannelSwap(Layer):
+    """Randomly permute the channels of a batch of signals (rank 3) or spectrograms (rank 4); reference :17-112.
+
+    ONE permutation per call, drawn with ``np.random.permutation`` as upstream, so ``np.random.seed`` governs it.  It travels
+    in the kernel's arguments: a captured graph replays the permutation it was captured with (a traced TensorFlow function
+    does the same).  float32 and complex64 data, at most 64 channels.  ``last_permutation`` is that of the last training call.
+    """
+
+    def __init__(self, data_format='default', **kwargs):
+        super(ChannelSwap, self).__init__(**kwargs)
+        self.data_format = _resolve_format(data_format)
+        self.last_permutation = None
+
+    def call(self, x, training=None):
+        if training in (None, False):
+            return x
+        ndim = len(x.shape)
+        if ndim not in (3, 4):
+            raise ValueError(
+                'ndim of input tensor x should be 3 (batch signal) or 4 (batch spectrogram),'
+                'but it is %d' % ndim
+            )
+        ch_axis = ndim - 1 if self.data_format == _CH_LAST_STR else 1
+        n_ch = int(x.shape[ch_axis])
+        if n_ch == 1:
+            return x
+        perm = np.random.permutation(n_ch).tolist()
+        self.last_permutation = perm
+        if autograd.needs_grad(x):
+            dtype = 'complex64' if x.is_complex() else 'float32'
+            return autograd.channel_gather(autograd.prep(x, dtype), ch_axis, perm)
+        return self._forward(x, ch_axis, perm)
+
+    @staticmethod
+    def _forward(x, ch_axis, perm):
+        import torch
+
+        complex_in = np.iscomplexobj(x) if isinstance(x, np.ndarray) else (isinstance(x, torch.Tensor) and x.is_complex())
+        return _ffi.channel_gather(_ffi.as_device(x, torch.complex64 if complex_in else torch.float32), ch_axis, perm)
+
+    def get_config(self):
+        config = super(ChannelSwap, self).get_config()
+        config.update({'data_format': _config_format(self.data_format)})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class SpecAugment(Layer):
+    """SpecAugment (Park et al. 2019, https://arxiv.org/abs/1904.08779) of a one-channel spectrogram batch; reference :115-326.
+
+    Args are the reference's: ``freq_mask_param`` (F of the paper), ``time_mask_param`` (T), ``n_freq_masks=1`` (mF),
+    ``n_time_masks=1`` (mT), ``mask_value=0.0``, ``data_format='default'``.  Every batch item gets its own masks; a mask
+    covers ``width + 1`` frames / bins, ``width`` uniform in ``0 .. param - 1`` (the reference's ``<=``, :211-214).
+    At most 32 masks per axis.  After a training call ``last_mask_table`` is the device table of that call: int32
+    ``(batch, n_time_masks + n_freq_masks, 2)`` of inclusive ``(first, last)``, time masks first.
+    """
+
+    def __init__(
+        self,
+        freq_mask_param,
+        time_mask_param,
+        n_freq_masks=1,
+        n_time_masks=1,
+        mask_value=0.0,
+        data_format='default',
+        **kwargs,
+    ):
+        super(SpecAugment, self).__init__(**kwargs)
+        data_format = _resolve_format(data_format)
+        self.freq_mask_param = freq_mask_param
+        self.time_mask_param = time_mask_param
+        self.n_freq_masks = n_freq_masks
+        self.n_time_masks = n_time_masks
+        self.mask_value = mask_value
+        if not self.freq_mask_param or not self.time_mask_param:
+            raise RuntimeError(
+                "Both freq_mask_param and time_mask_param must be defined and different "
+                "than zero"
+            )
+        self.data_format = data_format
+        self.last_mask_table = None
+
+    def _mask_counts(self):
+        """(time masks, frequency masks): the reference applies an axis' masks when its count is >= 1"""
+        return max(int(self.n_time_masks), 0), max(int(self.n_freq_masks), 0)
+
+    def _check(self, shape):
+        """The reference's checks, in its order (:296-306, :245); returns (n_time, n_freq)."""
+        if len(shape) != 4:
+            raise ValueError(
+                'ndim of input tensor x should be 4 (batch spectrogram),' 'but it is %d' % len(shape)
+            )
+        ch_axis = 1 if self.data_format == 'channels_first' else 3
+        if shape[ch_axis] != 1:
+            raise RuntimeError(
+                'SpecAugment does not support spectrograms with depth greater than 1'
+            )
+        n_time, n_freq = (shape[1], shape[2]) if ch_axis == 3 else (shape[2], shape[3])
+        n_tm, n_fm = self._mask_counts()
+        if (n_tm and n_time < self.time_mask_param) or (n_fm and n_freq < self.freq_mask_param):
+            raise ValueError(
+                "Time and freq axis shapes must be greater than time_mask_param "
+                "and freq_mask_param respectively"
+            )
+        return int(n_time), int(n_freq)
+
+    def call(self, x, training=None, **kwargs):
+        if training in (None, False):
+            return x
+        if autograd.needs_grad(x):
+            return autograd.spec_augment(self, autograd.prep(x, 'float32'))       # (its forward is _forward)
+        return self._forward(x)
+
+    def _forward(self, x, inplace=False):
+        """The training pass: the reference's checks, a fresh table, then the masks.  ``inplace`` (fuse_and_run, on a tensor
+        nobody else holds) masks ``x`` itself; otherwise ``x`` is left as it is."""
+        import torch
+
+        n_time, n_freq = self._check(tuple(x.shape))
+        x = _ffi.as_device(x, torch.float32)
+        n_tm, n_fm = self._mask_counts()
+        table = _ffi.spec_augment_draw(device_state(x.device), x.shape[0], n_tm, n_fm, n_time, n_freq,
+                                       self.time_mask_param, self.freq_mask_param)
+        self.last_mask_table = table
+        return self._apply(x, table, self.mask_value, inplace)
+
+    def _apply(self, x, table, mask_value, inplace=False):
+        n_tm, n_fm = self._mask_counts()
+        n_time, n_freq = (x.shape[1], x.shape[2]) if self.data_format == _CH_LAST_STR else (x.shape[2], x.shape[3])
+        return _ffi.spec_augment_apply(x, table, n_tm, n_fm, n_time, n_freq, mask_value, inplace=inplace)
+
+    def get_config(self):
+        config = super(SpecAugment, self).get_config()
+        config.update(
+            {
+                'freq_mask_param': self.freq_mask_param,
+                'time_mask_param': self.time_mask_param,
+                'n_freq_masks': self.n_freq_masks,
+                'n_time_masks': self.n_time_masks,
+                'mask_value': self.mask_value,
+                'data_format': _config_format(self.data_format),
+            }
+        )
+        return config

@@ -7,6 +7,8 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   (window ``n_fft * w``, interior bins halved), ``InverseSTFT^T`` an STFT launch (window
   ``2 / n_fft * w_synth``, edge bins halved), ``ApplyFilterbank^T`` / ``LogmelToMFCC^T`` the same
   GEMM with the transposed matrix; ``Frame`` / ``Energy`` / ``Delta`` have gather-form adjoint kernels;
+* ``SpecAugment^T`` is its own out-of-place kernel on the cotangent with the saved mask table and mask value 0,
+  ``ChannelSwap^T`` the channel gather with the inverse permutation;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -265,8 +267,35 @@ def _functions():
             g = g.contiguous().to(torch.float32)
             return _ffi.delta(g, layer.data_format, int(layer.win_length), layer.mode, backward=True), None
 
+    class SpecAugmentFn(torch.autograd.Function):
+        """y = x off the masks, mask_value on them: the adjoint is the same selection of the cotangent with 0 on the masks
+        (the out-of-place apply with the table the forward drew)."""
+
+        @staticmethod
+        def forward(ctx, x, layer):
+            ctx.layer = layer
+            y = layer._forward(x.detach())
+            ctx.table = layer.last_mask_table
+            return y
+
+        @staticmethod
+        def backward(ctx, g):
+            return ctx.layer._apply(g.contiguous().to(torch.float32), ctx.table, 0.0), None
+
+    class ChannelGatherFn(torch.autograd.Function):
+        """y[c] = x[perm[c]]; backward = the gather with the inverse permutation."""
+
+        @staticmethod
+        def forward(ctx, x, ch_axis, perm):
+            ctx.ch_axis, ctx.inverse, ctx.dtype = ch_axis, np.argsort(perm).tolist(), x.dtype
+            return _ffi.channel_gather(x.detach(), ch_axis, perm)
+
+        @staticmethod
+        def backward(ctx, g):
+            return _ffi.channel_gather(g.contiguous().to(ctx.dtype), ctx.ch_axis, ctx.inverse), None, None
+
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
-               frame=FrameFn, delta=DeltaFn)
+               frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn)
     return _FN
 
 
@@ -311,3 +340,11 @@ def energy(layer, x):
 
 def delta(layer, x):
     return _functions()['delta'].apply(x, layer)
+
+
+def spec_augment(layer, x):
+    return _functions()['spec_augment'].apply(x, layer)
+
+
+def channel_gather(x, ch_axis, perm):
+    return _functions()['channel_gather'].apply(x, ch_axis, perm)

@@ -62,6 +62,7 @@
 #include "kpr_generic_kernels.h"
 #include "kpr_misc_kernels.h"
 #include "kpr_grad_kernels.h"
+#include "kpr_augment_kernels.h"
 
 namespace kpr {
 
@@ -2948,6 +2949,103 @@ int kpr_delta_bwd_f32(const float* g, int64_t batch, int channels, int64_t frame
     hipLaunchKernelGGL(k_delta_bwd, dim3(grid_1d(total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, g, outer,
                        (long long)frames, inner, n, pad_mode, (float)(1.0 / denom), gx);
     return launch_check("k_delta_bwd");
+}
+
+/* ---- SpecAugment / ChannelSwap (kpr_augment_kernels.h) -------------------------------------- */
+static int aug_geom(int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq, AugGeom* a) {
+    if (n_items < 0 || n_time <= 0 || n_freq <= 0) return fail(KPR_E_BADARG, "bad n_items/n_time/n_freq");
+    if (n_time_masks < 0 || n_freq_masks < 0 || n_time_masks > kAugMaxMasks || n_freq_masks > kAugMaxMasks)
+        return fail(KPR_E_BADARG, "mask counts (%d, %d) outside [0, %d] per axis", n_time_masks, n_freq_masks, kAugMaxMasks);
+    if ((long long)n_time * n_freq > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "n_time * n_freq = %lld elements per item: 2^31 or more is not supported",
+                    (long long)n_time * n_freq);
+    *a = AugGeom{(int)n_items, n_time_masks, n_freq_masks, n_time, n_freq, 0, 0};
+    return 0;
+}
+
+int kpr_spec_augment_draw(int32_t* table, int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq,
+                          int time_mask_param, int freq_mask_param, void* state, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    AugGeom a;
+    if (int e = aug_geom(n_items, n_time_masks, n_freq_masks, n_time, n_freq, &a)) return e;
+    // augmentation.py:245: an axis shorter than its mask parameter is an error (only asked of an axis that has masks)
+    if (n_time_masks > 0 && (time_mask_param < 1 || time_mask_param > n_time))
+        return fail(KPR_E_BADARG, "time_mask_param %d outside [1, n_time = %d]", time_mask_param, n_time);
+    if (n_freq_masks > 0 && (freq_mask_param < 1 || freq_mask_param > n_freq))
+        return fail(KPR_E_BADARG, "freq_mask_param %d outside [1, n_freq = %d]", freq_mask_param, n_freq);
+    // the draw is one workgroup (the counter has one writer): 2^20 entries are 1024 per lane, some tens of microseconds
+    if (n_items * (long long)(n_time_masks + n_freq_masks) > (1LL << 20))
+        return fail(KPR_E_UNSUPPORTED, "mask table of %lld entries: the one-workgroup draw takes at most 2^20",
+                    (long long)(n_items * (long long)(n_time_masks + n_freq_masks)));
+    if (!state) return fail(KPR_E_BADARG, "state must not be NULL");
+    if (a.n_items * (a.n_tm + a.n_fm) > 0 && !table) return fail(KPR_E_BADARG, "table must not be NULL");
+    a.tparam = time_mask_param;
+    a.fparam = freq_mask_param;
+    // (a call without entries still advances the counter: one launch, one step of the stream)
+    hipLaunchKernelGGL(k_specaug_draw, dim3(1), dim3(1024), 0, (hipStream_t)stream, table, a, (unsigned long long*)state);
+    return launch_check("k_specaug_draw");
+}
+
+int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table, int64_t n_items, int n_time_masks,
+                               int n_freq_masks, int n_time, int n_freq, float mask_value, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    AugGeom a;
+    if (int e = aug_geom(n_items, n_time_masks, n_freq_masks, n_time, n_freq, &a)) return e;
+    if (n_items == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if (n_time_masks + n_freq_masks > 0 && !table) return fail(KPR_E_BADARG, "table must not be NULL");
+    const long long isz = (long long)n_time * n_freq;
+    const bool vec = ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    if (n_freq > kAugMaxFreq)
+        return fail(KPR_E_UNSUPPORTED, "n_freq = %d: the copy form holds at most %d bins per row", n_freq, kAugMaxFreq);
+    if (x != out) {   // partial overlap would let a workgroup read what another has already masked (out == x: in place)
+        const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, nb = (uintptr_t)(n_items * isz * 4);
+        if (xa < oa + nb && oa < xa + nb) return fail(KPR_E_BADARG, "x and out overlap (only out == x, in place, is allowed)");
+    }
+    const long long chunks = (isz + kAugChunk - 1) / kAugChunk;
+    if (n_items * chunks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many items");
+    if (vec)
+        hipLaunchKernelGGL(k_specaug_apply<4>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
+                           (int)chunks, mask_value, out);
+    else
+        hipLaunchKernelGGL(k_specaug_apply<1>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
+                           (int)chunks, mask_value, out);
+    return launch_check("k_specaug_apply");
+}
+
+int kpr_channel_gather(const void* x, void* out, int64_t outer, int n_ch, int64_t inner, int elem_bytes, const int32_t* perm,
+                       kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (outer < 0 || n_ch <= 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/n_ch/inner");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(KPR_E_BADARG, "elem_bytes must be 4 (float32) or 8 (complex64), got %d", elem_bytes);
+    if (n_ch > kGatherMaxCh)
+        return fail(KPR_E_UNSUPPORTED, "%d channels: the permutation travels in the kernel arguments, at most %d", n_ch, kGatherMaxCh);
+    if (!perm) return fail(KPR_E_BADARG, "perm must not be NULL");
+    GatherPerm gp{};
+    for (int c = 0; c < n_ch; ++c) {
+        if (perm[c] < 0 || perm[c] >= n_ch) return fail(KPR_E_BADARG, "perm[%d] = %d outside [0, %d)", c, perm[c], n_ch);
+        gp.p[c] = perm[c];
+    }
+    const long long words = inner * (elem_bytes / 4);                 // 4-byte words per (o, c) row
+    if (outer == 0 || words == 0) return 0;
+    if (!x || !out || x == out) return fail(KPR_E_BADARG, "x / out must not be NULL or aliased");
+    const long long rows = outer * n_ch;
+    if (words < 64) {
+        if (words * n_ch > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "row too long");
+        hipLaunchKernelGGL(k_channel_gather_rows, dim3(grid_1d(outer, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned*)x, (unsigned*)out, (long long)outer, n_ch, (int)words, gp);
+        return launch_check("k_channel_gather_rows");
+    }
+    const bool vec = (words & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    const long long units = vec ? words / 4 : words;
+    const dim3 grid((unsigned)std::min<long long>((units + 1023) / 1024, 64), (unsigned)std::min<long long>(rows, 65535));
+    if (vec)
+        hipLaunchKernelGGL(k_channel_gather<uint4>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)out, rows,
+                           n_ch, units, gp);
+    else
+        hipLaunchKernelGGL(k_channel_gather<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)x,
+                           (unsigned*)out, rows, n_ch, units, gp);
+    return launch_check("k_channel_gather");
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 
 The reference's "operator API" is the Keras layer protocol:
 ``Layer.__init__(**kwargs)`` swallowing ``name`` / ``input_shape`` / ``dtype``,
-``__call__(x, training=None) -> call(x)``, ``get_config()`` / ``from_config()``,
+``__call__(x, training=None) -> call(x)`` (``call(x, training=...)`` for the layers whose ``call`` takes it), ``get_config()`` / ``from_config()``,
 ``@register_keras_serializable(package='Kapre')`` and composition in ``keras.Sequential``
 (``add``, ``.layers``, ``.name``, ``__call__``, ``predict(np) -> np``, ``get_config``).
 TensorFlow/Keras are not available on the target image, so this module re-provides exactly that
@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import collections
 import datetime
+import inspect
 import io
 import json
 import os
@@ -32,6 +33,7 @@ import numpy as np
 
 _NAME_COUNTS: Dict[str, int] = collections.defaultdict(int)
 _REGISTRY: Dict[str, type] = {}
+_TAKES_TRAINING: Dict[type, bool] = {}
 
 
 def _to_snake_case(name: str) -> str:
@@ -67,8 +69,22 @@ def get_registered_object(name: str):
     return _REGISTRY.get(name)
 
 
+def _takes_training(cls) -> bool:
+    """True when ``cls.call`` has a ``training`` parameter (looked up once per class)."""
+    takes = _TAKES_TRAINING.get(cls)
+    if takes is None:
+        takes = _TAKES_TRAINING[cls] = 'training' in inspect.signature(cls.call).parameters
+    return takes
+
+
 class Layer:
-    """Minimal keras.layers.Layer: naming, config round trip, __call__ -> call."""
+    """Minimal keras.layers.Layer: naming, config round trip, __call__ -> call.
+
+    Contract of the layers defined in THIS package (``fuse_and_run`` relies on it when, in training, it lets ``SpecAugment``
+    mask the output of the layer in front of it in place): ``call`` returns either its input object or a tensor that the
+    layer does not keep a reference to.  A view of the input is recognised by its storage and treated as the input; a layer
+    that caches what it returns must live outside the package's modules or copy.  Layers defined elsewhere are never
+    assumed to follow this."""
 
     def __init__(self, name: Optional[str] = None, input_shape=None, dtype=None,
                  trainable: bool = True, batch_input_shape=None, **kwargs):
@@ -120,6 +136,9 @@ class Layer:
         return x
 
     def __call__(self, x, training=None, **kwargs):
+        # the layers that behave differently in training (augmentation.py, Sequential) declare ``training`` in ``call``
+        if training is not None and _takes_training(type(self)):
+            return self.call(x, training=training)
         return self.call(x)
 
     def get_config(self) -> Dict[str, Any]:
@@ -182,9 +201,9 @@ class Sequential(Layer):
                 flat.append(layer)
         return flat
 
-    def call(self, x):
+    def call(self, x, training=None):
         from .time_frequency import fuse_and_run
-        return fuse_and_run(self._flat_layers(), x)
+        return fuse_and_run(self._flat_layers(), x, training=training)
 
     # -- static shapes ------------------------------------------------------------------------------
     @property

@@ -19,6 +19,7 @@ import ctypes
 import numpy as np
 
 from . import _ffi, autograd, backend
+from .augmentation import SpecAugment
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
@@ -701,11 +702,30 @@ def _run_stft_phase(group, x):
     return group[0]._run(x, _ffi.OUT_PHASE)
 
 
-def fuse_and_run(layers, x):
+def _chain_owns(layer, x, y, owned: bool) -> bool:
+    """True when ``y = layer(x)`` is a tensor only this chain holds: the owned ``x`` handed through, or the output of one of
+    this package's layers that does not share ``x``'s storage (keras_shim.Layer: the layers of this package return fresh
+    tensors and keep no reference to them; a view of the input is recognised here and counts as the input)."""
+    import torch
+
+    if y is x:
+        return owned
+    if (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.device == y.device
+            and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr()):
+        return owned
+    return type(layer).__module__.startswith(__package__ + '.')
+
+
+def fuse_and_run(layers, x, training=None):
     """Run a flat list of layers, fusing the Kapre chains that have a single-kernel form.  When ``x`` carries gradient
     a fused group runs as one autograd node (forward = the fused launch, backward = recomputation through the
-    individual layers, kapre_amd/autograd.py)."""
+    individual layers, kapre_amd/autograd.py).  ``training`` goes to the layers whose ``call`` takes it; when it is true a
+    ``SpecAugment`` masks IN PLACE a float32 tensor that a kernel of this chain produced, that nobody else holds and that
+    carries no gradient (no second buffer) -- the chain's own input is never modified."""
+    import torch
+
     i, n = 0, len(layers)
+    owned = False                    # x is an output of this chain that nobody else holds
     while i < n:
         layer = layers[i]
         group, runner = None, None
@@ -728,8 +748,15 @@ def fuse_and_run(layers, x):
                 group, runner = layers[i:i + 2], _run_stft_phase
         if group is not None:
             x = autograd.chain(group, x, runner) if autograd.needs_grad(x) else runner(group, x)
+            owned = True
             i += len(group)
             continue
-        x = layer(x)
+        if (type(layer) is SpecAugment and training not in (None, False) and owned and isinstance(x, torch.Tensor)
+                and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and not x.requires_grad):
+            x = layer._forward(x, inplace=True)
+        else:
+            y = layer(x, training=training)
+            owned = _chain_owns(layer, x, y, owned)
+            x = y
         i += 1
     return x
