@@ -437,6 +437,35 @@ int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table,
 int kpr_channel_gather(const void* x, void* out, int64_t outer, int n_ch, int64_t inner, int elem_bytes,
                        const int32_t* perm_host, kpr_stream_t stream);
 
+/* ---- signal.py: MuLawEncoding / MuLawDecoding (backend.mu_law_encoding / mu_law_decoding, backend.py:302-341) ----
+ * Elementwise over n elements of any shape; mu = quantization_channels - 1, quantization_channels in [2, 65536]
+ * (KPR_E_BADARG outside).  Pointers are 4-byte aligned device pointers at ANY word (views are fine); out may be the
+ * input itself (in place), partial overlap is KPR_E_BADARG.  n <= 2^40 (KPR_E_UNSUPPORTED beyond); n == 0 launches nothing.
+ *   encode    : out = int32(trunc((sign(x) log1p(mu |x|) / log1p(mu) + 1) / 2 * mu + 0.5)).  Inputs outside [-1, 1] are
+ *               NOT clipped (the formula as it stands, as TensorFlow); a NaN gives code 0 (TensorFlow leaves that cast
+ *               unspecified).  Against the formula in float64: never more than one code away, and the same code wherever
+ *               the value before truncation is at least quantization_channels * 2^-21 away from an integer.
+ *   decode    : s = 2 code / mu - 1, out = sign(s) (exp(|s| log1p(mu)) - 1) / mu, from int32 codes (_i32) or from float32
+ *               codes (_f32: what Keras' cast to floatx hands the layer, and the differentiable form).
+ *   decode_bwd: gx = g * 2 log1p(mu) / mu^2 * exp(|s| log1p(mu)), the derivative of decode_f32 w.r.t. the code. */
+int kpr_mu_law_encode_f32(const float* x, int64_t n, int quantization_channels, int32_t* out, kpr_stream_t stream);
+int kpr_mu_law_decode_i32(const int32_t* code, int64_t n, int quantization_channels, float* out, kpr_stream_t stream);
+int kpr_mu_law_decode_f32(const float* code, int64_t n, int quantization_channels, float* out, kpr_stream_t stream);
+int kpr_mu_law_decode_bwd_f32(const float* code, const float* g, int64_t n, int quantization_channels, float* gx,
+                              kpr_stream_t stream);
+
+/* ---- time_frequency.py:647-744: ConcatenateFrequencyMap ---------------------------------------------------------
+ * x: float32 (batch, frames, n_freq, channels) [LAST] or (batch, channels, frames, n_freq) [FIRST]; out: the same with
+ * channels + 1.  The first `channels` channels are x bit for bit; the new last channel holds f / (n_freq - 1) for bin f
+ * (tf.linspace(0, 1, n_freq)): exactly 0.0 at f = 0, exactly 1.0 at f = n_freq - 1, within 2^-24 elsewhere; n_freq == 1: 0.0.
+ * One pass: every output byte is written once, every input byte read once.  4-byte aligned pointers at any word; x and out
+ * must not overlap.  frames * n_freq * (channels + 1) < 2^31 per batch item (KPR_E_UNSUPPORTED beyond).
+ * _bwd is the adjoint: gx = g without its last channel (g has channels + 1 channels, gx has `channels`). */
+int kpr_freq_map_concat_f32(const float* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* out,
+                            kpr_stream_t stream);
+int kpr_freq_map_concat_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout,
+                                float* gx, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

@@ -20,10 +20,11 @@ from .time_frequency import (
     MagnitudeToDecibel,
     ApplyFilterbank,
     Delta,
+    ConcatenateFrequencyMap,
 )
 
 from . import signal
-from .signal import Frame, Energy, LogmelToMFCC
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC
 
 from . import augmentation
 from .augmentation import SpecAugment, ChannelSwap
@@ -51,11 +52,32 @@ def check_device(device=None):
         torch.cuda.synchronize(device)
     _ffi.device_status(synchronize=False, raise_on_error=True)
 
+def install_as_kapre():
+    """Make ``import kapre`` mean this package: registers it in ``sys.modules`` as ``kapre`` and its modules as
+    ``kapre.backend``, ``kapre.composed``, ``kapre.time_frequency``, ``kapre.signal`` and ``kapre.augmentation``, so that the
+    ``from kapre import ...`` / ``from kapre.time_frequency import ...`` lines of an existing model run unedited.  Opt-in: nothing
+    happens unless it is called; a second call changes nothing.  Raises ``RuntimeError`` when another ``kapre`` is already
+    imported or can be found on the path -- shadowing a real installation silently would be worse than editing an import."""
+    import importlib.util
+    import sys
+
+    this = sys.modules[__name__]
+    have = sys.modules.get('kapre')
+    if have is not None and have is not this:
+        raise RuntimeError('install_as_kapre: another module named kapre is already imported (%r)' % (have,))
+    if have is None and importlib.util.find_spec('kapre') is not None:
+        raise RuntimeError('install_as_kapre: a kapre package can be imported from %s; remove it from the path or import '
+                           'kapre_amd under its own name' % (importlib.util.find_spec('kapre').origin,))
+    sys.modules['kapre'] = this
+    for name in ('backend', 'composed', 'time_frequency', 'signal', 'augmentation'):
+        sys.modules['kapre.' + name] = sys.modules[__name__ + '.' + name]
+
 
 __all__ = [
     '__version__',
     'VERSION',
     'check_device',
+    'install_as_kapre',
     'STFT',
     'InverseSTFT',
     'Magnitude',
@@ -63,8 +85,11 @@ __all__ = [
     'MagnitudeToDecibel',
     'ApplyFilterbank',
     'Delta',
+    'ConcatenateFrequencyMap',
     'Frame',
     'Energy',
+    'MuLawEncoding',
+    'MuLawDecoding',
     'LogmelToMFCC',
     'SpecAugment',
     'ChannelSwap',

@@ -144,6 +144,19 @@ EXPORTS = {
                                                   ctypes.c_void_p]),
     "kpr_channel_gather": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # mu-law companding (kapre_amd/signal.py) and ConcatenateFrequencyMap (kapre_amd/time_frequency.py)
+    "kpr_mu_law_encode_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "kpr_mu_law_decode_i32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "kpr_mu_law_decode_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "kpr_mu_law_decode_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_freq_map_concat_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_freq_map_concat_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -564,4 +577,44 @@ def channel_gather(x, ch_axis: int, perm):
     out = torch.empty_like(x)
     perm_host = (ctypes.c_int32 * len(perm))(*[int(p) for p in perm])
     _call("kpr_channel_gather", x.device, ptr(x), ptr(out), outer, shape[ch_axis], inner, x.element_size(), perm_host)
+    return out
+
+
+# mu-law companding (kapre_amd/signal.py) and ConcatenateFrequencyMap (kapre_amd/time_frequency.py)
+def mu_law_encode(x, quantization_channels: int):
+    """backend.mu_law_encoding of the float32 ``x`` (any shape): int32 codes."""
+    import torch
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    _call("kpr_mu_law_encode_f32", x.device, ptr(x), x.numel(), int(quantization_channels), ptr(out))
+    return out
+
+
+def mu_law_decode(code, quantization_channels: int):
+    """backend.mu_law_decoding of int32 or float32 codes (any shape): float32."""
+    import torch
+    out = torch.empty(code.shape, dtype=torch.float32, device=code.device)
+    _call("kpr_mu_law_decode_i32" if code.dtype == torch.int32 else "kpr_mu_law_decode_f32", code.device, ptr(code),
+          code.numel(), int(quantization_channels), ptr(out))
+    return out
+
+
+def mu_law_decode_bwd(code, g, quantization_channels: int):
+    """Cotangent of the float32 ``code`` from the cotangent ``g`` of ``mu_law_decode(code, ...)``."""
+    import torch
+    g = g.contiguous().to(torch.float32)
+    gx = torch.empty_like(code)
+    _call("kpr_mu_law_decode_bwd_f32", code.device, ptr(code), ptr(g), code.numel(), int(quantization_channels), ptr(gx))
+    return gx
+
+
+def freq_map_concat(x, fmt, backward: bool = False):
+    """The rank-4 float32 ``x`` with the frequency map f / (n_freq - 1) as one more (last) channel, or with ``backward`` the
+    adjoint: ``x`` (then the cotangent) without its last channel."""
+    import torch
+    b, c, t, f = dims_of(x.shape, fmt)
+    if backward:
+        c -= 1
+    out = torch.empty(shape_of(fmt, b, c + (0 if backward else 1), t, f), dtype=torch.float32, device=x.device)
+    _call("kpr_freq_map_concat_bwd_f32" if backward else "kpr_freq_map_concat_f32", x.device, ptr(x), b, c, t, f,
+          layout(fmt), ptr(out))
     return out

@@ -8,7 +8,9 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   ``2 / n_fft * w_synth``, edge bins halved), ``ApplyFilterbank^T`` / ``LogmelToMFCC^T`` the same
   GEMM with the transposed matrix; ``Frame`` / ``Energy`` / ``Delta`` have gather-form adjoint kernels;
 * ``SpecAugment^T`` is its own out-of-place kernel on the cotangent with the saved mask table and mask value 0,
-  ``ChannelSwap^T`` the channel gather with the inverse permutation;
+  ``ChannelSwap^T`` the channel gather with the inverse permutation; ``ConcatenateFrequencyMap^T`` drops the map channel
+  of the cotangent (one kernel); mu-law decoding of float codes has an elementwise backward kernel, mu-law encoding
+  returns integers and ends the tape;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -294,8 +296,34 @@ def _functions():
         def backward(ctx, g):
             return _ffi.channel_gather(g.contiguous().to(ctx.dtype), ctx.ch_axis, ctx.inverse), None, None
 
+    class MuLawDecodeFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, code, quantization_channels):
+            ctx.q = quantization_channels
+            code = code.detach()
+            ctx.save_for_backward(code)
+            return _ffi.mu_law_decode(code, quantization_channels)
+
+        @staticmethod
+        def backward(ctx, g):
+            (code,) = ctx.saved_tensors
+            return _ffi.mu_law_decode_bwd(code, g, ctx.q), None
+
+    class FreqMapFn(torch.autograd.Function):
+        """y = x with the frequency map as one more channel; backward = the cotangent without that channel."""
+
+        @staticmethod
+        def forward(ctx, x, data_format):
+            ctx.data_format = data_format
+            return _ffi.freq_map_concat(x.detach(), data_format)
+
+        @staticmethod
+        def backward(ctx, g):
+            return _ffi.freq_map_concat(g.contiguous().to(torch.float32), ctx.data_format, backward=True), None
+
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
-               frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn)
+               frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn)
     return _FN
 
 
@@ -348,3 +376,11 @@ def spec_augment(layer, x):
 
 def channel_gather(x, ch_axis, perm):
     return _functions()['channel_gather'].apply(x, ch_axis, perm)
+
+
+def mu_law_decode(code, quantization_channels):
+    return _functions()['mu_law_decode'].apply(code, quantization_channels)
+
+
+def freq_map_concat(x, data_format):
+    return _functions()['freq_map'].apply(x, data_format)

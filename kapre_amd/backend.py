@@ -2,7 +2,8 @@
 
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
-``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299).
+``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -290,3 +291,37 @@ def filterbank_log(sample_rate: int, n_freq: int, n_bins: int = 84, bins_per_oct
         )
     basis = _normalize(basis, norm=1, axis=1)
     return np.ascontiguousarray(basis.astype(_get_floatx()).T)
+
+
+# --------------------------------------------------------------------------------------
+# mu-law companding
+# --------------------------------------------------------------------------------------
+def _is_float(x) -> bool:
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        return x.is_floating_point()
+    return np.issubdtype(np.asarray(x).dtype, np.floating)
+
+
+def mu_law_encoding(signal, quantization_channels: int):
+    """Mu-law compression on the GPU (reference: backend.py:302-319): a signal scaled to [-1, 1] becomes int32 codes in
+    ``0 .. quantization_channels - 1``.  Any shape, numpy array or torch tensor; computed in float32.  Values outside
+    [-1, 1] are not clipped (the formula as it stands, as TensorFlow); a NaN gives code 0.  The result carries no gradient."""
+    import torch
+
+    x = signal.detach() if isinstance(signal, torch.Tensor) else signal
+    return _ffi.mu_law_encode(_ffi.as_device(x, torch.float32), quantization_channels)
+
+
+def mu_law_decoding(signal_mu, quantization_channels: int):
+    """Mu-law expansion on the GPU (reference: backend.py:322-341): float32 of the shape of ``signal_mu``.  int32 and
+    float32 codes have kernels of their own; other integer dtypes are converted to int32, other float dtypes to float32,
+    first.  A float tensor that ``requires_grad`` gets a ``grad_fn`` (kapre_amd/autograd.py)."""
+    import torch
+
+    from . import autograd
+    if autograd.needs_grad(signal_mu):
+        return autograd.mu_law_decode(autograd.prep(signal_mu, 'float32'), quantization_channels)
+    dtype = torch.float32 if _is_float(signal_mu) else torch.int32
+    return _ffi.mu_law_decode(_ffi.as_device(signal_mu, dtype), quantization_channels)

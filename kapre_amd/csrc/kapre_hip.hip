@@ -25,6 +25,9 @@
 //                             kernel covers -- the idea of the reference's kapre/tflite_compatible_stft.py:14-75)
 //   kpr_grad_kernels.h        backward passes of the elementwise layers (tf.abs / tf.math.angle on complex data, the
 //                             decibel map, the bin scaling that turns the inverse-STFT launch into STFT^T and back)
+//   kpr_augment_kernels.h     SpecAugment (device-drawn masks) and ChannelSwap (augmentation.py)
+//   kpr_companding_kernels.h  mu-law encode / decode (signal.py:236-361) and ConcatenateFrequencyMap (time_frequency.py:647-744),
+//                             forward and backward: output-driven streaming kernels
 // This file: table caches, launch plans, argument validation and the C ABI.
 //
 // gfx950 only: wave64, v_mfma_f32_16x16x4_f32, 160 KiB LDS.  No CUDA/compat paths.
@@ -63,6 +66,7 @@
 #include "kpr_misc_kernels.h"
 #include "kpr_grad_kernels.h"
 #include "kpr_augment_kernels.h"
+#include "kpr_companding_kernels.h"
 
 namespace kpr {
 
@@ -1743,6 +1747,88 @@ static int run_db_bwd(const T* x, const T* gy, int64_t n_items, int64_t item_siz
                        (long long)item_size, (T)amin_k, (T)ref_term, (T)dynamic_range, gx);
     return launch_check("k_db_bwd");
 }
+// ---- mu-law companding / ConcatenateFrequencyMap (kpr_companding_kernels.h): launch helpers of the C entry points ----
+static int mu_law_args(int64_t n, int quantization_channels, MuLawDev* p) {
+    if (n < 0) return fail(KPR_E_BADARG, "negative element count");
+    if (quantization_channels < 2 || quantization_channels > 65536)
+        return fail(KPR_E_BADARG, "quantization_channels %d outside [2, 65536]", quantization_channels);
+    if (n > kCompandMaxElems)
+        return fail(KPR_E_UNSUPPORTED, "%lld elements: one call takes at most 2^40", (long long)n);
+    const double q = quantization_channels, mu = q - 1.0, l2q = std::log2(q), c = l2q / mu, inv = 1.0 / mu;
+    p->mu = (float)mu;
+    p->half_mu = (float)(0.5 * mu);
+    p->half_q = (float)(0.5 * q);
+    p->inv_log2q = (float)(1.0 / l2q);
+    p->c_hi = (float)c;
+    p->c_lo = (float)(c - (double)p->c_hi);
+    p->inv_hi = (float)inv;
+    p->inv_lo = (float)(inv - (double)p->inv_hi);
+    p->gcoef = (float)(2.0 * std::log(q) / (mu * mu));
+    return 0;
+}
+
+// the pointers of a streaming call: not NULL, 4-byte aligned, out either the input itself or clear of it
+static int stream_ptrs(const void* in, const void* in2, const void* out, int64_t n, const char* names) {
+    if (!in || !in2 || !out) return fail(KPR_E_BADARG, "%s must not be NULL", names);
+    if ((((uintptr_t)in) | ((uintptr_t)in2) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "%s must be 4-byte aligned", names);
+    const uintptr_t nb = (uintptr_t)n * 4, oa = (uintptr_t)out;
+    for (const void* q : {in, in2}) {
+        const uintptr_t a = (uintptr_t)q;
+        if (a != oa && a < oa + nb && oa < a + nb) return fail(KPR_E_BADARG, "%s overlap (only out == in, in place, is allowed)", names);
+    }
+    return 0;
+}
+
+template <int OP>
+static int run_mu_law(const void* in, const void* g, void* out, int64_t n, int quantization_channels, const char* names,
+                      kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    MuLawDev p;
+    if (int e = mu_law_args(n, quantization_channels, &p)) return e;
+    if (n == 0) return 0;
+    if (int e = stream_ptrs(in, g, out, n, names)) return e;
+    const long long groups = n / 4 + 1;
+    hipLaunchKernelGGL(k_mu_law<OP>, dim3((unsigned)((groups + kStreamChunk - 1) / kStreamChunk)), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned*)in, (const unsigned*)g, (unsigned*)out, (long long)n, p);
+    return launch_check(OP == MU_ENCODE ? "k_mu_law_encode" : OP == MU_DECODE_BWD ? "k_mu_law_decode_bwd" : "k_mu_law_decode");
+}
+
+template <bool DROP>
+static int run_freq_map(const float* in, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* out,
+                        kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (batch < 0 || channels <= 0 || frames < 0 || n_freq <= 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/frames/n_freq/layout");
+    const long long plane = (long long)frames * n_freq;
+    if (plane * ((long long)channels + 1) > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "frames * n_freq * (channels + 1) = %lld elements per item: 2^31 or more is not supported",
+                    plane * ((long long)channels + 1));
+    if (batch == 0 || plane == 0) return 0;
+    const long long n_in = batch * plane * (channels + (DROP ? 1 : 0)), n_out = batch * plane * (channels + (DROP ? 0 : 1));
+    if (!in || !out) return fail(KPR_E_BADARG, "%s must not be NULL", DROP ? "g / gx" : "x / out");
+    if ((((uintptr_t)in) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out;
+        if (ia < oa + (uintptr_t)n_out * 4 && oa < ia + (uintptr_t)n_in * 4) return fail(KPR_E_BADARG, "input and output overlap");
+    }
+    const bool cl = layout == KPR_CHANNELS_LAST;
+    FmapArgs a;
+    a.rin = (unsigned)(cl ? channels : plane * channels);
+    a.rmap = (unsigned)(cl ? 1 : plane);
+    a.n_freq = (unsigned)n_freq;
+    a.osz = (unsigned)(plane * (channels + (DROP ? 0 : 1)));
+    a.last = n_freq > 1 ? n_freq - 1 : -1;
+    a.inv = n_freq > 1 ? (float)(1.0 / (double)(n_freq - 1)) : 0.0f;
+    a.chunks = (int)(((long long)(a.osz >> 2) + kStreamChunk) / kStreamChunk);
+    if (batch * a.chunks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many items");
+    const dim3 grid((unsigned)(batch * a.chunks));
+    if (cl)
+        hipLaunchKernelGGL((k_freq_map<DROP, true>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)in, (unsigned*)out, a);
+    else
+        hipLaunchKernelGGL((k_freq_map<DROP, false>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)in, (unsigned*)out, a);
+    return launch_check(DROP ? "k_freq_map_drop" : "k_freq_map_concat");
+}
+
 extern "C" {
 
 int kpr_version(void) { return KPR_VERSION; }
@@ -3046,6 +3132,30 @@ int kpr_channel_gather(const void* x, void* out, int64_t outer, int n_ch, int64_
         hipLaunchKernelGGL(k_channel_gather<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)x,
                            (unsigned*)out, rows, n_ch, units, gp);
     return launch_check("k_channel_gather");
+}
+
+/* ---- mu-law companding / ConcatenateFrequencyMap (kpr_companding_kernels.h) ------------------ */
+int kpr_mu_law_encode_f32(const float* x, int64_t n, int quantization_channels, int32_t* out, kpr_stream_t stream) {
+    return run_mu_law<MU_ENCODE>(x, x, out, n, quantization_channels, "x / out", stream);
+}
+int kpr_mu_law_decode_i32(const int32_t* code, int64_t n, int quantization_channels, float* out, kpr_stream_t stream) {
+    return run_mu_law<MU_DECODE_I32>(code, code, out, n, quantization_channels, "code / out", stream);
+}
+int kpr_mu_law_decode_f32(const float* code, int64_t n, int quantization_channels, float* out, kpr_stream_t stream) {
+    return run_mu_law<MU_DECODE_F32>(code, code, out, n, quantization_channels, "code / out", stream);
+}
+int kpr_mu_law_decode_bwd_f32(const float* code, const float* g, int64_t n, int quantization_channels, float* gx,
+                              kpr_stream_t stream) {
+    return run_mu_law<MU_DECODE_BWD>(code, g, gx, n, quantization_channels, "code / g / gx", stream);
+}
+
+int kpr_freq_map_concat_f32(const float* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* out,
+                            kpr_stream_t stream) {
+    return run_freq_map<false>(x, batch, channels, frames, n_freq, layout, out, stream);
+}
+int kpr_freq_map_concat_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* gx,
+                                kpr_stream_t stream) {
+    return run_freq_map<true>(g, batch, channels, frames, n_freq, layout, gx, stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 (reference: /root/reference/kapre/signal.py).  Frame, Energy and LogmelToMFCC keep the reference's
 constructor signatures, validation, get_config() keys and output shapes; the arithmetic runs in
 libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with a DCT-II matrix).
-MuLawEncoding / MuLawDecoding are out of scope."""
+MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.mu_law_encoding / mu_law_decoding
+(kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32)."""
 import math
 
 import numpy as np
@@ -11,7 +12,7 @@ from . import _ffi, autograd, backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
-__all__ = ['Frame', 'Energy', 'LogmelToMFCC']
+__all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC']
 
 
 def _resolve_format(fmt):
@@ -126,6 +127,58 @@ class Energy(Layer):
                        'frame_length': self.frame_length, 'hop_length': self.hop_length,
                        'pad_end': self.pad_end, 'pad_value': self.pad_value,
                        'data_format': self.data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class MuLawEncoding(Layer):
+    """Mu-law encoding (compression) of an audio signal in [-1, 1] to int32 codes in ``0 .. quantization_channels - 1``
+    (reference: signal.py:236-306).  Any shape; the shape does not change.  ``quantization_channels``: 256 for 8 bits.
+    Values outside [-1, 1] are not clipped; a NaN sample gives code 0.  The output is an integer tensor without ``grad_fn``."""
+
+    def __init__(self, quantization_channels, **kwargs):
+        super(MuLawEncoding, self).__init__(**kwargs)
+        if quantization_channels < 2:
+            raise ValueError(
+                f'quantization_channels must be at least 2, got: {quantization_channels}'
+            )
+        if quantization_channels > 65536:
+            raise ValueError(
+                f'quantization_channels must be <= 65536, got: {quantization_channels}'
+            )
+        self.quantization_channels = quantization_channels
+
+    def compute_output_shape(self, input_shape):
+        return tuple(input_shape)
+
+    def call(self, x):
+        return backend.mu_law_encoding(x, self.quantization_channels)
+
+    def get_config(self):
+        config = super(MuLawEncoding, self).get_config()
+        config.update({'quantization_channels': self.quantization_channels})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class MuLawDecoding(Layer):
+    """Mu-law decoding (expansion) of mu-law codes to float32 in [-1, 1] (reference: signal.py:309-361).  Any shape; int32
+    or float32 codes (other dtypes are converted first).  As upstream the constructor validates nothing; a value outside
+    ``2 .. 65536`` is refused by the library at call time.  Float codes that ``requires_grad`` are differentiable."""
+
+    def __init__(self, quantization_channels, **kwargs):
+        super(MuLawDecoding, self).__init__(**kwargs)
+        self.quantization_channels = quantization_channels
+
+    def compute_output_shape(self, input_shape):
+        return tuple(input_shape)
+
+    def call(self, x):
+        return backend.mu_law_decoding(x, self.quantization_channels)
+
+    def get_config(self):
+        config = super(MuLawDecoding, self).get_config()
+        config.update({'quantization_channels': self.quantization_channels})
         return config
 
 

@@ -2,7 +2,8 @@
 
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
-``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559).  Constructor signatures,
+``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
+``ConcatenateFrequencyMap`` (:647-744).  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -31,6 +32,7 @@ __all__ = [
     'MagnitudeToDecibel',
     'ApplyFilterbank',
     'Delta',
+    'ConcatenateFrequencyMap',
 ]
 
 
@@ -597,6 +599,61 @@ class Delta(Layer):
         config = super(Delta, self).get_config()
         config.update({'win_length': self.win_length, 'mode': self.mode,
                        'data_format': self.data_format_original})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class ConcatenateFrequencyMap(Layer):
+    """Adds a frequency-information channel to a batch of spectrograms or feature maps (reference: time_frequency.py:647-744;
+    with a following ``Conv2D``: frequency-aware convolution, Koutini et al. 2019).  The new last channel holds
+    ``f / (n_freq - 1)`` for bin ``f``: 0.0 at the lowest bin, exactly 1.0 at the highest (0.0 when there is one bin).
+    (b, t, f, ch) -> (b, t, f, ch + 1) for ``channels_last``, (b, ch, t, f) -> (b, ch + 1, t, f) for ``channels_first``;
+    float32; one kernel writes the whole output in one pass (kpr_freq_map_concat_f32)."""
+
+    def __init__(self, data_format='default', **kwargs):
+        super(ConcatenateFrequencyMap, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):           # (the reference's workaround for a Keras deserialisation bug)
+            data_format = data_format['config']
+        self.data_format_original = data_format
+        self.data_format = _resolve_format(data_format)
+
+    def compute_output_shape(self, input_shape):
+        shape = list(input_shape)
+        ch_axis = 3 if self.data_format == _CH_LAST_STR else 1
+        if shape[ch_axis] is not None:
+            shape[ch_axis] = int(shape[ch_axis]) + 1
+        return tuple(shape)
+
+    @staticmethod
+    def _check(x):
+        """float32 and rank 4, asked before anything reaches the device"""
+        import torch
+
+        if isinstance(x, torch.Tensor):
+            dtype, ok = x.dtype, x.dtype == torch.float32
+        else:
+            x = x if isinstance(x, np.ndarray) else np.asarray(x)
+            dtype, ok = x.dtype, x.dtype == np.float32
+        if not ok:
+            raise TypeError('ConcatenateFrequencyMap expects a float32 input, got %s' % (dtype,))
+        if len(x.shape) != 4:
+            raise ValueError('ConcatenateFrequencyMap expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+
+    def call(self, x):
+        self._check(x)
+        if autograd.needs_grad(x):
+            return autograd.freq_map_concat(autograd.prep(x, 'float32'), self.data_format)
+        return self._forward(x)
+
+    def _forward(self, x):
+        import torch
+
+        return _ffi.freq_map_concat(_ffi.as_device(x, torch.float32), self.data_format)
+
+    def get_config(self):
+        config = super(ConcatenateFrequencyMap, self).get_config()
+        config.update({'data_format': self.data_format_original})
         return config
 
 
