@@ -466,6 +466,32 @@ int kpr_freq_map_concat_f32(const float* x, int64_t batch, int channels, int64_t
 int kpr_freq_map_concat_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout,
                                 float* gx, kpr_stream_t stream);
 
+/* ---- PCEN: per-channel energy normalisation (Wang et al. 2017), kapre_amd.time_frequency.PCEN ------------------------
+ * x: a non-negative float32 spectrogram seen as a contiguous (outer, frames, inner) block scanned along `frames`; the band
+ * of inner index i is i / band_div and inner == n_bands * band_div (KPR_E_BADARG otherwise):
+ *   (batch, ch, frames, mel) [channels_first]: outer = batch * ch, inner = mel,      band_div = 1
+ *   (batch, frames, mel, ch) [channels_last] : outer = batch,      inner = mel * ch, band_div = ch
+ * s, alpha, delta, r: device float32 vectors of n_bands values (0 < s <= 1, alpha >= 0, delta > 0, r > 0: the caller checks
+ * them, the library does not read them on the host); eps > 0.  Per (outer, inner) column, a = 1 - s:
+ *   S[0] = x[0], S[t] = a S[t-1] + s x[t];  out[t] = (x[t] (eps + S[t])^-alpha + delta)^r - delta^r
+ * x == 0 gives exactly 0.0.  A negative x is outside the contract (NaN where the base of a power goes negative).
+ * smooth_out (may be NULL): receives S, which kpr_pcen_bwd_f32 takes as `smooth`.
+ * _bwd: gx = d sum(gy * out) / dx (the parameters are constants), one launch:
+ *   G = (eps + S)^-alpha, u = x G + delta, p = gy r u^(r-1), q = -alpha p x G / (eps + S), N[t] = q[t] + a N[t+1], N[frames] = 0,
+ *   gx[t] = p G + s N[t] for t >= 1, gx[0] = p G + N[0].
+ * One pass: every input byte is read once, every output byte written once.  Pointers are 4-byte aligned; 16-byte accesses
+ * are used when inner % 4 == 0 and every pointer is 16-byte aligned.  Outputs must not overlap inputs or each other (x == out
+ * is KPR_E_BADARG).  frames * inner < 2^31 (KPR_E_UNSUPPORTED beyond).  outer, frames or inner == 0: returns 0, launches nothing.
+ * kpr_pcen_plan (host only): the time tiling of the dispatch -- a workgroup of *waves_per_group waves covers
+ * *waves_per_group * *rows_per_wave consecutive frames per step, *rows_per_wave per wave; chunk boundaries for tests. */
+int kpr_pcen_plan(int64_t frames, int64_t inner, int* rows_per_wave, int* waves_per_group);
+int kpr_pcen_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, int band_div, int n_bands, const float* s,
+                 const float* alpha, const float* delta, const float* r, float eps, float* out, float* smooth_out,
+                 kpr_stream_t stream);
+int kpr_pcen_bwd_f32(const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                     int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
+                     float* gx, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

@@ -21,6 +21,7 @@ from .time_frequency import (
     ApplyFilterbank,
     Delta,
     ConcatenateFrequencyMap,
+    PCEN,
 )
 
 from . import signal
@@ -86,6 +87,7 @@ __all__ = [
     'ApplyFilterbank',
     'Delta',
     'ConcatenateFrequencyMap',
+    'PCEN',
     'Frame',
     'Energy',
     'MuLawEncoding',

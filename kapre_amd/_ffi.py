@@ -157,6 +157,15 @@ EXPORTS = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "kpr_freq_map_concat_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # PCEN (kapre_amd/time_frequency.py)
+    "kpr_pcen_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int)]),
+    "kpr_pcen_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_pcen_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -618,3 +627,40 @@ def freq_map_concat(x, fmt, backward: bool = False):
     _call("kpr_freq_map_concat_bwd_f32" if backward else "kpr_freq_map_concat_f32", x.device, ptr(x), b, c, t, f,
           layout(fmt), ptr(out))
     return out
+
+
+# PCEN (kapre_amd/time_frequency.py)
+def pcen_plan(frames: int, inner: int):
+    """(rows_per_wave, waves_per_group): the time tiling kpr_pcen_f32 uses (host only)."""
+    rows, waves = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().kpr_pcen_plan(int(frames), int(inner), ctypes.byref(rows), ctypes.byref(waves)), "kpr_pcen_plan")
+    return rows.value, waves.value
+
+
+def _pcen_geometry(x, fmt):
+    """(outer, frames, inner, band_div, n_bands) of the rank-4 ``x``"""
+    b, c, t, m = dims_of(x.shape, fmt)
+    if fmt in ("channels_last", CHANNELS_LAST):
+        return b, t, m * c, c, m
+    return b * c, t, m, 1, m
+
+
+def pcen(x, fmt, params, eps: float, want_smooth: bool = False):
+    """PCEN of the rank-4 float32 ``x``; ``params``: the device float32 vectors (s, alpha, delta, r), one value per band.
+    With ``want_smooth`` returns (out, S), S being what ``pcen_bwd`` needs."""
+    import torch
+    out = torch.empty_like(x)
+    smooth = torch.empty_like(x) if want_smooth else None
+    _call("kpr_pcen_f32", x.device, ptr(x), *_pcen_geometry(x, fmt), *(ptr(p) for p in params), float(eps), ptr(out),
+          ptr(smooth))
+    return (out, smooth) if want_smooth else out
+
+
+def pcen_bwd(x, smooth, g, fmt, params, eps: float):
+    """Cotangent of ``x`` from the cotangent ``g`` of ``pcen(x, ...)`` and the smoother ``smooth`` of that call."""
+    import torch
+    g = g.contiguous().to(torch.float32)
+    gx = torch.empty_like(x)
+    _call("kpr_pcen_bwd_f32", x.device, ptr(x), ptr(smooth), ptr(g), *_pcen_geometry(x, fmt), *(ptr(p) for p in params),
+          float(eps), ptr(gx))
+    return gx

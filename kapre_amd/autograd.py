@@ -10,7 +10,8 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
 * ``SpecAugment^T`` is its own out-of-place kernel on the cotangent with the saved mask table and mask value 0,
   ``ChannelSwap^T`` the channel gather with the inverse permutation; ``ConcatenateFrequencyMap^T`` drops the map channel
   of the cotangent (one kernel); mu-law decoding of float codes has an elementwise backward kernel, mu-law encoding
-  returns integers and ends the tape;
+  returns integers and ends the tape; ``PCEN`` keeps its smoother ``S`` (the forward kernel's second output) and runs
+  one backward kernel, the forward scan in reversed time (input gradient only: its parameters are constants);
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -321,9 +322,23 @@ def _functions():
         def backward(ctx, g):
             return _ffi.freq_map_concat(g.contiguous().to(torch.float32), ctx.data_format, backward=True), None
 
+    class PcenFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, data_format, params, eps):
+            ctx.data_format, ctx.params, ctx.eps = data_format, params, eps
+            x = x.detach()
+            y, smooth = _ffi.pcen(x, data_format, params, eps, want_smooth=True)
+            ctx.save_for_backward(x, smooth)
+            return y
+
+        @staticmethod
+        def backward(ctx, g):
+            x, smooth = ctx.saved_tensors
+            return _ffi.pcen_bwd(x, smooth, g, ctx.data_format, ctx.params, ctx.eps), None, None, None
+
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
-               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn)
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn)
     return _FN
 
 
@@ -384,3 +399,7 @@ def mu_law_decode(code, quantization_channels):
 
 def freq_map_concat(x, data_format):
     return _functions()['freq_map'].apply(x, data_format)
+
+
+def pcen(x, data_format, params, eps):
+    return _functions()['pcen'].apply(x, data_format, params, eps)

@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen`` has no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -325,3 +325,71 @@ def mu_law_decoding(signal_mu, quantization_channels: int):
         return autograd.mu_law_decode(autograd.prep(signal_mu, 'float32'), quantization_channels)
     dtype = torch.float32 if _is_float(signal_mu) else torch.int32
     return _ffi.mu_law_decode(_ffi.as_device(signal_mu, dtype), quantization_channels)
+
+
+# --------------------------------------------------------------------------------------
+# PCEN
+# --------------------------------------------------------------------------------------
+def pcen_parameters(s, alpha, delta, r, eps):
+    """Validated PCEN parameters: ``s``, ``alpha``, ``delta``, ``r`` as float32 arrays of shape () or (n,), ``eps`` as a
+    float.  ``ValueError`` unless 0 < s <= 1, alpha >= 0, delta > 0, r > 0, eps > 0 (and each is a scalar or 1-D)."""
+    out = []
+    for name, value, ok, rule in (('s', s, lambda v: (v > 0) & (v <= 1), '0 < s <= 1'),
+                                  ('alpha', alpha, lambda v: v >= 0, 'alpha >= 0'),
+                                  ('delta', delta, lambda v: v > 0, 'delta > 0'),
+                                  ('r', r, lambda v: v > 0, 'r > 0')):
+        v = np.asarray(value, dtype=np.float64)
+        if v.ndim > 1 or v.size == 0:
+            raise ValueError('PCEN: %s must be a scalar or a 1-D array with one value per band, got shape %s' % (name, v.shape))
+        v32 = v.astype(np.float32)
+        if not (np.all(ok(v)) and np.all(ok(v32))):          # (NaN fails every rule; so does a value float32 rounds out of range)
+            raise ValueError('PCEN: %s is required, got %s = %r' % (rule, name, value))
+        out.append(v32)
+    if np.ndim(eps) != 0 or not float(np.float32(eps)) > 0:
+        raise ValueError('PCEN: eps must be a positive scalar, got %r' % (eps,))
+    return out[0], out[1], out[2], out[3], float(eps)
+
+
+def pcen_band_table(params, n_bands: int) -> np.ndarray:
+    """The (4, n_bands) float32 table (rows s, alpha, delta, r) the kernel reads: scalars repeated, vectors checked against
+    ``n_bands`` (``ValueError``)."""
+    table = np.empty((4, n_bands), dtype=np.float32)
+    for row, (name, v) in enumerate(zip(('s', 'alpha', 'delta', 'r'), params)):
+        if v.ndim == 1 and v.shape[0] != n_bands:
+            raise ValueError('PCEN: %s has %d values, the input has %d bands' % (name, v.shape[0], n_bands))
+        table[row] = v
+    return table
+
+
+def _pcen_run(x, table_of, eps, data_format):
+    """PCEN of ``x`` (rank 4); ``table_of(n_bands, device)``: the device copy of ``pcen_band_table``"""
+    import torch
+
+    from . import autograd
+    if len(x.shape) != 4:
+        raise ValueError('PCEN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise NotImplementedError('PCEN has float32 kernels only; got a float64 input (cast it to float32)')
+    grad = autograd.needs_grad(x)
+    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
+    n_bands = x.shape[2] if data_format == _CH_LAST_STR else x.shape[3]
+    params = tuple(table_of(int(n_bands), x.device)) if n_bands > 0 else (None,) * 4
+    if grad:
+        return autograd.pcen(x, data_format, params, eps)
+    return _ffi.pcen(x, data_format, params, eps)
+
+
+def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='default'):
+    """Per-channel energy normalisation (Wang et al. 2017) of a non-negative spectrogram batch on the GPU:
+    (b, time, freq, ch) for ``channels_last``, (b, ch, time, freq) for ``channels_first``; float32 out, same shape.
+
+        S[0] = x[0], S[t] = (1 - s) S[t-1] + s x[t];   y[t] = (x[t] (eps + S[t])^-alpha + delta)^r - delta^r
+
+    ``s``, ``alpha``, ``delta``, ``r``: a scalar or one value per frequency band.  One kernel, one pass over ``x``.  A tensor
+    that ``requires_grad`` gets a ``grad_fn`` (gradient with respect to ``x`` only)."""
+    import torch
+
+    validate_data_format_str(data_format)
+    *params, eps = pcen_parameters(s, alpha, delta, r, eps)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt)

@@ -28,6 +28,8 @@
 //   kpr_augment_kernels.h     SpecAugment (device-drawn masks) and ChannelSwap (augmentation.py)
 //   kpr_companding_kernels.h  mu-law encode / decode (signal.py:236-361) and ConcatenateFrequencyMap (time_frequency.py:647-744),
 //                             forward and backward: output-driven streaming kernels
+//   kpr_pcen_kernels.h        per-channel energy normalisation and its input gradient: a recurrence along time, tiled over
+//                             the waves of a workgroup (chunk end values through LDS, one barrier per super-block)
 // This file: table caches, launch plans, argument validation and the C ABI.
 //
 // gfx950 only: wave64, v_mfma_f32_16x16x4_f32, 160 KiB LDS.  No CUDA/compat paths.
@@ -67,6 +69,7 @@
 #include "kpr_grad_kernels.h"
 #include "kpr_augment_kernels.h"
 #include "kpr_companding_kernels.h"
+#include "kpr_pcen_kernels.h"
 
 namespace kpr {
 
@@ -1829,6 +1832,62 @@ static int run_freq_map(const float* in, int64_t batch, int channels, int64_t fr
     return launch_check(DROP ? "k_freq_map_drop" : "k_freq_map_concat");
 }
 
+// ---- PCEN (kpr_pcen_kernels.h): argument checks and launch of the forward / backward C entry points ----
+// x (and smooth, gy for the backward pass) -> out; smooth_out only for the forward pass, may be NULL
+static int run_pcen(bool bwd, const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                    int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
+                    float* out, float* smooth_out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (outer < 0 || frames < 0 || inner < 0 || band_div <= 0 || n_bands <= 0)
+        return fail(KPR_E_BADARG, "bad outer/frames/inner/band_div/n_bands");
+    if (outer == 0 || frames == 0 || inner == 0) return 0;
+    if (inner != (int64_t)n_bands * band_div)
+        return fail(KPR_E_BADARG, "inner = %lld is not n_bands * band_div = %d * %d", (long long)inner, n_bands, band_div);
+    if (!(eps > 0.0f)) return fail(KPR_E_BADARG, "eps must be positive");
+    if (!x || !out || !s || !alpha || !delta || !r || (bwd && (!smooth || !gy)))
+        return fail(KPR_E_BADARG, bwd ? "x / smooth / gy / gx and the parameter vectors must not be NULL"
+                                      : "x / out and the parameter vectors must not be NULL");
+    if (frames * inner > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "frames * inner = %lld elements per outer item: 2^31 or more is not supported",
+                    (long long)(frames * inner));
+    uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)smooth | (uintptr_t)gy | (uintptr_t)smooth_out;
+    if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4;
+        auto clash = [nb](const void* p, const void* q) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nb && (uintptr_t)q < (uintptr_t)p + nb;
+        };
+        bool bad = clash(out, smooth_out);
+        for (const float* in : {x, smooth, gy}) bad = bad || clash(out, in) || clash(smooth_out, in);
+        if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
+    }
+    const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
+    PcenArgs a;
+    a.x = x; a.smooth = smooth; a.gy = gy; a.out = out; a.smooth_out = smooth_out;
+    a.s = s; a.alpha = alpha; a.delta = delta; a.r = r;
+    a.eps = eps;
+    a.frames = (int)frames;
+    a.inner = (unsigned)inner;
+    a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
+    a.band_div = (unsigned)band_div;
+    a.n_groups = (long long)outer * a.groups_per_item;
+    const long long blocks = (a.n_groups + 63) / 64;
+    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
+    const dim3 grid((unsigned)blocks), block(64 * kPcenWaves);
+    const hipStream_t st = (hipStream_t)stream;
+    if (bwd) {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD>), grid, block, 0, st, a);
+    } else if (smooth_out) {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
+    } else {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD>), grid, block, 0, st, a);
+    }
+    return launch_check(bwd ? "k_pcen_bwd" : "k_pcen", v4 ? 4 : 1);
+}
+
 extern "C" {
 
 int kpr_version(void) { return KPR_VERSION; }
@@ -3156,6 +3215,25 @@ int kpr_freq_map_concat_f32(const float* x, int64_t batch, int channels, int64_t
 int kpr_freq_map_concat_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* gx,
                                 kpr_stream_t stream) {
     return run_freq_map<true>(g, batch, channels, frames, n_freq, layout, gx, stream);
+}
+
+/* ---- PCEN (kpr_pcen_kernels.h) ---------------------------------------------------------------- */
+int kpr_pcen_plan(int64_t frames, int64_t inner, int* rows_per_wave, int* waves_per_group) {
+    if (frames < 0 || inner < 0 || !rows_per_wave || !waves_per_group) return fail(KPR_E_BADARG, "bad frames/inner or NULL result");
+    *rows_per_wave = kPcenRows;
+    *waves_per_group = kPcenWaves;
+    return 0;
+}
+int kpr_pcen_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, int band_div, int n_bands, const float* s,
+                 const float* alpha, const float* delta, const float* r, float eps, float* out, float* smooth_out,
+                 kpr_stream_t stream) {
+    return run_pcen(false, x, nullptr, nullptr, outer, frames, inner, band_div, n_bands, s, alpha, delta, r, eps, out, smooth_out,
+                    stream);
+}
+int kpr_pcen_bwd_f32(const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                     int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
+                     float* gx, kpr_stream_t stream) {
+    return run_pcen(true, x, smooth, gy, outer, frames, inner, band_div, n_bands, s, alpha, delta, r, eps, gx, nullptr, stream);
 }
 
 }  // extern "C"

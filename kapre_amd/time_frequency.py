@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744).  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN`` is this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -33,6 +33,7 @@ __all__ = [
     'ApplyFilterbank',
     'Delta',
     'ConcatenateFrequencyMap',
+    'PCEN',
 ]
 
 
@@ -654,6 +655,50 @@ class ConcatenateFrequencyMap(Layer):
     def get_config(self):
         config = super(ConcatenateFrequencyMap, self).get_config()
         config.update({'data_format': self.data_format_original})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class PCEN(Layer):
+    """Per-channel energy normalisation (Wang et al. 2017, "Trainable frontend for robust and far-field keyword spotting"):
+    the normalisation used in place of ``MagnitudeToDecibel`` behind a (mel) magnitude spectrogram.  Per batch item, channel
+    and frequency band, along time:
+
+        S[0] = x[0], S[t] = (1 - smooth_coef) S[t-1] + smooth_coef x[t]
+        y[t] = (x[t] (eps + S[t])^-alpha + delta)^r - delta^r
+
+    ``smooth_coef``, ``alpha``, ``delta``, ``r``: a scalar or a 1-D array with one value per band (0 < smooth_coef <= 1,
+    alpha >= 0, delta > 0, r > 0, eps > 0: ``ValueError`` at construction; a vector's length is checked against the input at
+    call time).  They are constants: the layer is differentiable with respect to its input only.
+    (b, t, f, ch) for ``channels_last``, (b, ch, t, f) for ``channels_first``, same shape out; float32 (a float64 layer raises
+    ``NotImplementedError``); one kernel, one pass (kpr_pcen_f32).  No frames: an empty tensor, nothing is launched."""
+
+    def __init__(self, smooth_coef=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='default', **kwargs):
+        super(PCEN, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):
+            data_format = data_format['config']
+        *self._params, self.eps = backend.pcen_parameters(smooth_coef, alpha, delta, r, eps)
+        self.smooth_coef, self.alpha, self.delta, self.r = (
+            np.asarray(v, dtype=np.float64).tolist() for v in (smooth_coef, alpha, delta, r))     # JSON-ready
+        self.data_format_original = data_format
+        self.data_format = _resolve_format(data_format)
+        self._consts = _DeviceConstants()
+
+    def compute_output_shape(self, input_shape):
+        return tuple(input_shape)
+
+    def call(self, x):
+        if self._f64:
+            raise NotImplementedError('PCEN has float32 kernels only; build the layer with dtype float32')
+        return backend._pcen_run(
+            x, lambda n, device: self._consts.get(('pcen', n), device, lambda: backend.pcen_band_table(self._params, n)),
+            self.eps, self.data_format)
+
+    def get_config(self):
+        config = super(PCEN, self).get_config()
+        config.update({'smooth_coef': self.smooth_coef, 'alpha': self.alpha, 'delta': self.delta, 'r': self.r,
+                       'eps': self.eps, 'data_format': self.data_format_original})
         return config
 
 
