@@ -26,6 +26,7 @@
 #ifndef KAPRE_HIP_H
 #define KAPRE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -476,14 +477,30 @@ int kpr_freq_map_concat_bwd_f32(const float* g, int64_t batch, int channels, int
  *   S[0] = x[0], S[t] = a S[t-1] + s x[t];  out[t] = (x[t] (eps + S[t])^-alpha + delta)^r - delta^r
  * x == 0 gives exactly 0.0.  A negative x is outside the contract (NaN where the base of a power goes negative).
  * smooth_out (may be NULL): receives S, which kpr_pcen_bwd_f32 takes as `smooth`.
- * _bwd: gx = d sum(gy * out) / dx (the parameters are constants), one launch:
+ * _bwd: gx = d sum(gy * out) / dx (the parameters are constants; _bwd_params below is the form that differentiates them), one launch:
  *   G = (eps + S)^-alpha, u = x G + delta, p = gy r u^(r-1), q = -alpha p x G / (eps + S), N[t] = q[t] + a N[t+1], N[frames] = 0,
  *   gx[t] = p G + s N[t] for t >= 1, gx[0] = p G + N[0].
  * One pass: every input byte is read once, every output byte written once.  Pointers are 4-byte aligned; 16-byte accesses
  * are used when inner % 4 == 0 and every pointer is 16-byte aligned.  Outputs must not overlap inputs or each other (x == out
  * is KPR_E_BADARG).  frames * inner < 2^31 (KPR_E_UNSUPPORTED beyond).  outer, frames or inner == 0: returns 0, launches nothing.
  * kpr_pcen_plan (host only): the time tiling of the dispatch -- a workgroup of *waves_per_group waves covers
- * *waves_per_group * *rows_per_wave consecutive frames per step, *rows_per_wave per wave; chunk boundaries for tests. */
+ * *waves_per_group * *rows_per_wave consecutive frames per step, *rows_per_wave per wave; chunk boundaries for tests.
+ * _bwd_params: the backward pass of a PCEN whose parameters are learned.  gparams: (4, n_bands) float32, rows in the order of
+ * the arguments (s, alpha, delta, r), the gradient of sum(gy * out) with respect to each band's parameter.  With the values of
+ * _bwd and es = eps + S, the sums running over every (outer item, column of the band, frame):
+ *   g_alpha[b] = sum -p x G ln(es)
+ *   g_delta[b] = sum p - gy r delta^(r-1)                      (evaluated as gy r (u^(r-1) - delta^(r-1)))
+ *   g_r[b]     = sum gy (u^r ln u - delta^r ln delta)          (u^r as u u^(r-1))
+ *   g_s[b]     = sum over t >= 1 of N[t] (x[t] - S[t-1])       (frame 0 adds nothing: S[0] = x[0])
+ *   x == 0 everywhere gives g_alpha = g_s = 0 exactly; frames == 1 gives g_s = 0 exactly.
+ * gx: as _bwd writes it, bit for bit, or NULL: then no input gradient is computed or written (a frozen front end in front of a
+ * learned PCEN).  gparams has the same bits either way, and the same inputs give the same bits on every call: no atomics; each
+ * lane adds its frames in scan order, the waves of a workgroup are added in order, the workgroup leaves one float32 sum per
+ * (parameter, column) in the workspace, and a second kernel adds the outer * band_div columns of each band in double, in an
+ * order the shape fixes.  Two launches on `stream`, no host reads, capturable.
+ * workspace: kpr_pcen_bwd_params_workspace_bytes = 16 * outer * inner bytes (0 for an empty shape), 4-byte aligned (16-byte
+ * aligned for the 16-byte accesses); NULL or too small: KPR_E_WORKSPACE.  The argument rules of _bwd hold; gparams and the
+ * workspace must not overlap anything else.  outer, frames or inner == 0: gparams is zeroed (one memset on `stream`). */
 int kpr_pcen_plan(int64_t frames, int64_t inner, int* rows_per_wave, int* waves_per_group);
 int kpr_pcen_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, int band_div, int n_bands, const float* s,
                  const float* alpha, const float* delta, const float* r, float eps, float* out, float* smooth_out,
@@ -491,6 +508,11 @@ int kpr_pcen_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, i
 int kpr_pcen_bwd_f32(const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
                      int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
                      float* gx, kpr_stream_t stream);
+size_t kpr_pcen_bwd_params_workspace_bytes(int64_t outer, int64_t frames, int64_t inner);
+int kpr_pcen_bwd_params_f32(const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                            int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r,
+                            float eps, float* gx /* may be NULL */, float* gparams /* (4, n_bands) */, void* workspace,
+                            size_t workspace_bytes, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

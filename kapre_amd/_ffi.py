@@ -166,6 +166,11 @@ EXPORTS = {
     "kpr_pcen_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_pcen_bwd_params_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kpr_pcen_bwd_params_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -664,3 +669,18 @@ def pcen_bwd(x, smooth, g, fmt, params, eps: float):
     _call("kpr_pcen_bwd_f32", x.device, ptr(x), ptr(smooth), ptr(g), *_pcen_geometry(x, fmt), *(ptr(p) for p in params),
           float(eps), ptr(gx))
     return gx
+
+
+def pcen_bwd_params(x, smooth, g, fmt, params, eps: float, want_gx: bool = True):
+    """(gx or None, gparams): the cotangents of ``x`` (with ``want_gx``) and of the four parameter vectors, ``gparams`` being the
+    (4, n_bands) float32 tensor with rows s, alpha, delta, r.  Two launches; the same inputs give the same bits."""
+    import torch
+    g = g.contiguous().to(torch.float32)
+    geom = _pcen_geometry(x, fmt)
+    gx = torch.empty_like(x) if want_gx else None
+    gparams = torch.empty((4, geom[4]), dtype=torch.float32, device=x.device)
+    ws_bytes = int(lib().kpr_pcen_bwd_params_workspace_bytes(*geom[:3]))
+    ws = workspace(ws_bytes, x.device)
+    _call("kpr_pcen_bwd_params_f32", x.device, ptr(x), ptr(smooth), ptr(g), *geom, *(ptr(p) for p in params), float(eps),
+          ptr(gx), ptr(gparams), ptr(ws), ws_bytes)
+    return gx, gparams

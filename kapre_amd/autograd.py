@@ -323,18 +323,27 @@ def _functions():
             return _ffi.freq_map_concat(g.contiguous().to(torch.float32), ctx.data_format, backward=True), None
 
     class PcenFn(torch.autograd.Function):
+        """``s``, ``alpha``, ``delta``, ``r``: device float32 vectors of one value per band, inputs of the Function.  None of
+        them needs a gradient: the input-only backward launch.  Any does: kpr_pcen_bwd_params_f32, without the input gradient
+        when ``x`` needs none."""
+
         @staticmethod
-        def forward(ctx, x, data_format, params, eps):
-            ctx.data_format, ctx.params, ctx.eps = data_format, params, eps
+        def forward(ctx, x, data_format, s, alpha, delta, r, eps):
+            ctx.data_format, ctx.eps = data_format, eps
             x = x.detach()
+            params = tuple(None if p is None else p.detach() for p in (s, alpha, delta, r))
             y, smooth = _ffi.pcen(x, data_format, params, eps, want_smooth=True)
-            ctx.save_for_backward(x, smooth)
+            ctx.save_for_backward(x, smooth, *params)
             return y
 
         @staticmethod
         def backward(ctx, g):
-            x, smooth = ctx.saved_tensors
-            return _ffi.pcen_bwd(x, smooth, g, ctx.data_format, ctx.params, ctx.eps), None, None, None
+            x, smooth, *params = ctx.saved_tensors
+            need = ctx.needs_input_grad
+            if not any(need[2:6]):
+                return (_ffi.pcen_bwd(x, smooth, g, ctx.data_format, params, ctx.eps),) + (None,) * 6
+            gx, gp = _ffi.pcen_bwd_params(x, smooth, g, ctx.data_format, params, ctx.eps, want_gx=need[0])
+            return (gx, None) + tuple(gp[i] if need[2 + i] else None for i in range(4)) + (None,)
 
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
@@ -402,4 +411,4 @@ def freq_map_concat(x, data_format):
 
 
 def pcen(x, data_format, params, eps):
-    return _functions()['pcen'].apply(x, data_format, params, eps)
+    return _functions()['pcen'].apply(x, data_format, *params, eps)

@@ -361,8 +361,10 @@ def pcen_band_table(params, n_bands: int) -> np.ndarray:
     return table
 
 
-def _pcen_run(x, table_of, eps, data_format):
-    """PCEN of ``x`` (rank 4); ``table_of(n_bands, device)``: the device copy of ``pcen_band_table``"""
+def _pcen_run(x, table_of, eps, data_format, tensors=None):
+    """PCEN of ``x`` (rank 4); ``table_of(n_bands, device)``: the device copy of ``pcen_band_table``.  ``tensors``: for each of
+    s, alpha, delta, r either None or a float32 torch tensor of shape () or (n_bands,) that takes the table row's place; the
+    call is recorded for autograd when ``x`` or one of them requires grad."""
     import torch
 
     from . import autograd
@@ -370,13 +372,25 @@ def _pcen_run(x, table_of, eps, data_format):
         raise ValueError('PCEN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
     if _ffi.is_f64(x):
         raise NotImplementedError('PCEN has float32 kernels only; got a float64 input (cast it to float32)')
-    grad = autograd.needs_grad(x)
-    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
-    n_bands = x.shape[2] if data_format == _CH_LAST_STR else x.shape[3]
-    params = tuple(table_of(int(n_bands), x.device)) if n_bands > 0 else (None,) * 4
+    tensors = tuple(tensors) if tensors is not None else (None,) * 4
+    x_grad = autograd.needs_grad(x)
+    grad = x_grad or any(autograd.needs_grad(t) for t in tensors)
+    x = autograd.prep(x, 'float32') if x_grad else _ffi.as_device(x, torch.float32)
+    n_bands = int(x.shape[2] if data_format == _CH_LAST_STR else x.shape[3])
+    params = list(table_of(n_bands, x.device)) if n_bands > 0 else [None] * 4
+    for i, (name, t) in enumerate(zip(('s', 'alpha', 'delta', 'r'), tensors)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.dim() > 1 or (t.dim() == 1 and t.shape[0] != n_bands):
+            raise ValueError('PCEN: the tensor %s must be float32 of shape () or (%d,), got %s of shape %s'
+                             % (name, n_bands, t.dtype, tuple(t.shape)))
+        if t.device != x.device:
+            raise ValueError('PCEN: the tensor %s is on %s, the input on %s' % (name, t.device, x.device))
+        # (torch ops, recorded: the gradient of a 0-d tensor arrives summed over the bands)
+        params[i] = (t.expand(n_bands) if t.dim() == 0 else t).contiguous() if n_bands > 0 else None
     if grad:
-        return autograd.pcen(x, data_format, params, eps)
-    return _ffi.pcen(x, data_format, params, eps)
+        return autograd.pcen(x, data_format, tuple(params), eps)
+    return _ffi.pcen(x, data_format, tuple(params), eps)
 
 
 def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='default'):
@@ -386,10 +400,21 @@ def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='defaul
         S[0] = x[0], S[t] = (1 - s) S[t-1] + s x[t];   y[t] = (x[t] (eps + S[t])^-alpha + delta)^r - delta^r
 
     ``s``, ``alpha``, ``delta``, ``r``: a scalar or one value per frequency band.  One kernel, one pass over ``x``.  A tensor
-    that ``requires_grad`` gets a ``grad_fn`` (gradient with respect to ``x`` only)."""
+    that ``requires_grad`` gets a ``grad_fn``.
+
+    Each of the four may also be a float32 torch tensor on ``x``'s device, of shape () or (n_bands,): a learned parameter.  If it
+    requires grad, the output has a ``grad_fn`` (also when ``x`` does not) and ``backward()`` fills its ``.grad`` -- summed over
+    the bands for a 0-d tensor -- with one more launch pair (kpr_pcen_bwd_params_f32), which skips the input gradient when ``x``
+    needs none.  The shapes of tensors are checked, their values are not (that would read device memory on the host): the
+    caller keeps 0 < s <= 1, alpha >= 0, delta > 0, r > 0, e.g. by clamping after each optimiser step (``PCEN.constrain_``)."""
     import torch
 
     validate_data_format_str(data_format)
-    *params, eps = pcen_parameters(s, alpha, delta, r, eps)
+    given = (s, alpha, delta, r)
+    tensors = tuple(v if isinstance(v, torch.Tensor) else None for v in given)
+    # (a tensor's place in the table is overwritten: any valid number stands in for it in the validation)
+    numbers = [d if t is not None else v for v, t, d in zip(given, tensors, (0.025, 0.98, 2.0, 0.5))]
+    *params, eps = pcen_parameters(*numbers, eps)
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
-    return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt)
+    return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt,
+                     tensors if any(t is not None for t in tensors) else None)

@@ -1833,24 +1833,36 @@ static int run_freq_map(const float* in, int64_t batch, int channels, int64_t fr
 }
 
 // ---- PCEN (kpr_pcen_kernels.h): argument checks and launch of the forward / backward C entry points ----
-// x (and smooth, gy for the backward pass) -> out; smooth_out only for the forward pass, may be NULL
+// x (and smooth, gy for the backward pass) -> out; smooth_out only for the forward pass, may be NULL.
+// gparams != NULL: the backward pass with the parameter gradients (kpr_pcen_bwd_params_f32), out = gx may then be NULL
+static size_t pcen_params_workspace(int64_t outer, int64_t frames, int64_t inner) {
+    return outer > 0 && frames > 0 && inner > 0 ? (size_t)16 * (size_t)outer * (size_t)inner : 0;
+}
+
 static int run_pcen(bool bwd, const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
                     int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
-                    float* out, float* smooth_out, kpr_stream_t stream) {
+                    float* out, float* smooth_out, kpr_stream_t stream, bool with_params = false, float* gparams = nullptr,
+                    void* workspace = nullptr, size_t workspace_bytes = 0) {
     if (int e = api_enter()) return e;
     if (outer < 0 || frames < 0 || inner < 0 || band_div <= 0 || n_bands <= 0)
         return fail(KPR_E_BADARG, "bad outer/frames/inner/band_div/n_bands");
-    if (outer == 0 || frames == 0 || inner == 0) return 0;
+    if (with_params && (!gparams || ((uintptr_t)gparams & 3))) return fail(KPR_E_BADARG, "gparams must be a 4-byte aligned pointer");
+    if (outer == 0 || frames == 0 || inner == 0) {
+        if (!with_params) return 0;
+        KPR_HIP(hipMemsetAsync(gparams, 0, (size_t)n_bands * 4 * sizeof(float), (hipStream_t)stream));    // empty sums
+        return 0;
+    }
     if (inner != (int64_t)n_bands * band_div)
         return fail(KPR_E_BADARG, "inner = %lld is not n_bands * band_div = %d * %d", (long long)inner, n_bands, band_div);
     if (!(eps > 0.0f)) return fail(KPR_E_BADARG, "eps must be positive");
-    if (!x || !out || !s || !alpha || !delta || !r || (bwd && (!smooth || !gy)))
-        return fail(KPR_E_BADARG, bwd ? "x / smooth / gy / gx and the parameter vectors must not be NULL"
-                                      : "x / out and the parameter vectors must not be NULL");
+    if (!x || (!out && !with_params) || !s || !alpha || !delta || !r || (bwd && (!smooth || !gy)))
+        return fail(KPR_E_BADARG, with_params ? "x / smooth / gy and the parameter vectors must not be NULL"
+                                  : bwd       ? "x / smooth / gy / gx and the parameter vectors must not be NULL"
+                                              : "x / out and the parameter vectors must not be NULL");
     if (frames * inner > 0x7fffffffLL)
         return fail(KPR_E_UNSUPPORTED, "frames * inner = %lld elements per outer item: 2^31 or more is not supported",
                     (long long)(frames * inner));
-    uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)smooth | (uintptr_t)gy | (uintptr_t)smooth_out;
+    uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)smooth | (uintptr_t)gy | (uintptr_t)smooth_out | (uintptr_t)workspace;
     if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
     {
         const uintptr_t nb = (uintptr_t)outer * frames * inner * 4;
@@ -1860,6 +1872,20 @@ static int run_pcen(bool bwd, const float* x, const float* smooth, const float* 
         bool bad = clash(out, smooth_out);
         for (const float* in : {x, smooth, gy}) bad = bad || clash(out, in) || clash(smooth_out, in);
         if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
+    }
+    if (with_params) {
+        const size_t need = pcen_params_workspace(outer, frames, inner);
+        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4, ng = (uintptr_t)n_bands * 16;
+        auto within = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+        };
+        bool bad = within(gparams, ng, workspace, need);
+        for (const float* t : {x, smooth, gy, (const float*)out}) bad = bad || within(gparams, ng, t, nb) || within(workspace, need, t, nb);
+        for (const float* t : {s, alpha, delta, r}) bad = bad || within(gparams, ng, t, (uintptr_t)n_bands * 4);
+        if (bad) return fail(KPR_E_BADARG, "gparams or the workspace overlaps another argument");
+        if (!workspace || workspace_bytes < need)
+            return fail(KPR_E_WORKSPACE, "workspace of %zu bytes needed (kpr_pcen_bwd_params_workspace_bytes), got %zu", need,
+                        workspace ? workspace_bytes : (size_t)0);
     }
     const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
     PcenArgs a;
@@ -1871,10 +1897,24 @@ static int run_pcen(bool bwd, const float* x, const float* smooth, const float* 
     a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
     a.band_div = (unsigned)band_div;
     a.n_groups = (long long)outer * a.groups_per_item;
+    a.partials = (float*)workspace;
     const long long blocks = (a.n_groups + 63) / 64;
     if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
     const dim3 grid((unsigned)blocks), block(64 * kPcenWaves);
     const hipStream_t st = (hipStream_t)stream;
+    if (with_params) {
+        if (out) {
+            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
+        } else {
+            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
+        }
+        if (int e = launch_check(out ? "k_pcen_bwd_params" : "k_pcen_bwd_params_only", v4 ? 4 : 1)) return e;
+        hipLaunchKernelGGL(k_pcen_param_reduce, dim3(4u * (unsigned)n_bands), dim3(256), 0, st, (const float*)workspace, gparams,
+                           (long long)outer, (unsigned)inner, (unsigned)band_div, (unsigned)n_bands);
+        return launch_check("k_pcen_param_reduce");
+    }
     if (bwd) {
         if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD>), grid, block, 0, st, a);
@@ -3234,6 +3274,15 @@ int kpr_pcen_bwd_f32(const float* x, const float* smooth, const float* gy, int64
                      int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
                      float* gx, kpr_stream_t stream) {
     return run_pcen(true, x, smooth, gy, outer, frames, inner, band_div, n_bands, s, alpha, delta, r, eps, gx, nullptr, stream);
+}
+size_t kpr_pcen_bwd_params_workspace_bytes(int64_t outer, int64_t frames, int64_t inner) {
+    return pcen_params_workspace(outer, frames, inner);
+}
+int kpr_pcen_bwd_params_f32(const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                            int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r,
+                            float eps, float* gx, float* gparams, void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
+    return run_pcen(true, x, smooth, gy, outer, frames, inner, band_div, n_bands, s, alpha, delta, r, eps, gx, nullptr, stream, true,
+                    gparams, workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -113,7 +113,11 @@ class Layer:
         return []
 
     def count_params(self) -> int:
-        return 0          # all Kapre hot-path layers are parameter free (docs/quickstart.rst:76-78)
+        return 0          # all Kapre hot-path layers are parameter free (docs/quickstart.rst:76-78); PCEN can learn its own
+
+    def parameters(self):
+        """the layer's learned ``torch.nn.Parameter`` objects, for a torch optimiser (none but for ``PCEN(trainable_params=...)``)"""
+        return []
 
     def build(self, input_shape):
         pass
@@ -205,6 +209,17 @@ class Sequential(Layer):
         from .time_frequency import fuse_and_run
         return fuse_and_run(self._flat_layers(), x, training=training)
 
+    # -- learned parameters: the layers' own, in the order of the layers --------------------------------
+    def parameters(self):
+        return [p for layer in self._flat_layers() for p in layer.parameters()]
+
+    @property
+    def weights(self):
+        return [w for layer in self._flat_layers() for w in layer.weights]
+
+    def count_params(self) -> int:
+        return sum(layer.count_params() for layer in self._flat_layers())
+
     # -- static shapes ------------------------------------------------------------------------------
     @property
     def input_shape(self):
@@ -268,7 +283,7 @@ class Sequential(Layer):
         print_fn('Model: "%s"' % self.name)
         for l in self.layers:
             print_fn('  %-32s %s' % (l.name, type(l).__name__))
-        print_fn('Total params: 0')
+        print_fn('Total params: %d' % self.count_params())
 
 
 Model = Sequential

@@ -669,11 +669,23 @@ class PCEN(Layer):
 
     ``smooth_coef``, ``alpha``, ``delta``, ``r``: a scalar or a 1-D array with one value per band (0 < smooth_coef <= 1,
     alpha >= 0, delta > 0, r > 0, eps > 0: ``ValueError`` at construction; a vector's length is checked against the input at
-    call time).  They are constants: the layer is differentiable with respect to its input only.
+    call time).  By default they are constants: the layer is differentiable with respect to its input only.
     (b, t, f, ch) for ``channels_last``, (b, ch, t, f) for ``channels_first``, same shape out; float32 (a float64 layer raises
-    ``NotImplementedError``); one kernel, one pass (kpr_pcen_f32).  No frames: an empty tensor, nothing is launched."""
+    ``NotImplementedError``); one kernel, one pass (kpr_pcen_f32).  No frames: an empty tensor, nothing is launched.
 
-    def __init__(self, smooth_coef=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='default', **kwargs):
+    ``trainable_params``: ``True``, or a subset of ``('smooth_coef', 'alpha', 'delta', 'r')``, makes the named ones learned.
+    ``build(input_shape)``, or the first call, creates one float32 ``torch.nn.Parameter`` of ``n_bands`` values for each (the
+    constructor's value, a scalar broadcast), moved to the input's device by the first call there; ``parameters()`` lists them
+    for a torch optimiser (``weights`` too; ``count_params()`` counts them).  The output then has a ``grad_fn`` also for an
+    input that carries none, and ``backward()`` fills their ``.grad`` (kpr_pcen_bwd_params_f32; no input gradient is computed
+    when the input needs none).  With the Keras keyword ``trainable=False`` the parameters exist but do not require grad.
+    The kernels do not check the values: call ``constrain_()`` after an optimiser step to clamp them into the domain.
+    ``get_config()`` carries the current (learned) values as lists, so a saved model reloads with them."""
+
+    PARAM_NAMES = ('smooth_coef', 'alpha', 'delta', 'r')
+
+    def __init__(self, smooth_coef=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='default',
+                 trainable_params=False, **kwargs):
         super(PCEN, self).__init__(**kwargs)
         backend.validate_data_format_str(data_format)
         if isinstance(data_format, dict):
@@ -684,21 +696,101 @@ class PCEN(Layer):
         self.data_format_original = data_format
         self.data_format = _resolve_format(data_format)
         self._consts = _DeviceConstants()
+        if isinstance(trainable_params, bool):
+            names = self.PARAM_NAMES if trainable_params else ()
+        elif isinstance(trainable_params, (list, tuple)) and all(isinstance(n, str) for n in trainable_params):
+            unknown = sorted(set(trainable_params) - set(self.PARAM_NAMES))
+            if unknown or len(set(trainable_params)) != len(trainable_params):
+                raise ValueError('PCEN: trainable_params must name each of %s at most once, got %r'
+                                 % (self.PARAM_NAMES, trainable_params))
+            names = tuple(n for n in self.PARAM_NAMES if n in trainable_params)
+        else:
+            raise ValueError('PCEN: trainable_params must be True, False or a list of names out of %s, got %r'
+                             % (self.PARAM_NAMES, trainable_params))
+        self.trainable_params = trainable_params if isinstance(trainable_params, bool) else list(names)
+        self._trainable_names = names
+        self._weights = None                                  # name -> torch.nn.Parameter, made by build() / the first call
 
     def compute_output_shape(self, input_shape):
         return tuple(input_shape)
 
+    def build(self, input_shape, device=None):
+        """Create the learned parameters for an input of ``input_shape`` (with the batch axis) on ``device`` (default: the CPU;
+        the first call moves them to its input's device).  Nothing to do for a layer without learned parameters."""
+        if not self._trainable_names or self._weights is not None:
+            return
+        import torch
+
+        if len(input_shape) != 4:
+            raise ValueError('PCEN expects a rank-4 input, got shape %s' % (tuple(input_shape),))
+        n_bands = input_shape[2] if self.data_format == 'channels_last' else input_shape[3]
+        if n_bands is None or int(n_bands) <= 0:
+            raise ValueError('PCEN: the learned parameters need a known, positive number of bands, got input shape %s'
+                             % (tuple(input_shape),))
+        table = backend.pcen_band_table(self._params, int(n_bands))
+        self._weights = {
+            name: torch.nn.Parameter(torch.from_numpy(table[self.PARAM_NAMES.index(name)].copy()).to(device or 'cpu'),
+                                     requires_grad=bool(self.trainable))
+            for name in self._trainable_names}
+
+    def parameters(self):
+        """The learned parameters (``torch.nn.Parameter``, one value per band) in the order smooth_coef, alpha, delta, r: what a
+        torch optimiser takes.  ``RuntimeError`` before ``build`` / the first call of a layer that has some."""
+        if self._trainable_names and self._weights is None:
+            if self._input_shape_arg is None:
+                raise RuntimeError('PCEN: the parameters are created by build(input_shape) or the first call')
+            self.build((None,) + tuple(self._input_shape_arg))
+        return [self._weights[n] for n in self._trainable_names]
+
+    @property
+    def weights(self):
+        return [self._weights[n] for n in self._trainable_names] if self._weights is not None else []
+
+    def count_params(self) -> int:
+        return sum(int(w.numel()) for w in self.weights)
+
+    def constrain_(self):
+        """Clamp the learned parameters in place into the domain of the definition: smooth_coef into [2^-10, 1], alpha >= 0,
+        delta and r at least the smallest positive normal float32.  For use after an optimiser step."""
+        import torch
+
+        tiny = float(np.finfo(np.float32).tiny)
+        bounds = {'smooth_coef': (2.0 ** -10, 1.0), 'alpha': (0.0, None), 'delta': (tiny, None), 'r': (tiny, None)}
+        with torch.no_grad():
+            for name, w in zip(self._trainable_names, self.weights):
+                w.clamp_(min=bounds[name][0], max=bounds[name][1])
+        return self
+
     def call(self, x):
         if self._f64:
             raise NotImplementedError('PCEN has float32 kernels only; build the layer with dtype float32')
+        tensors = None
+        if self._trainable_names:
+            import torch
+
+            if len(x.shape) != 4:
+                raise ValueError('PCEN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+            _ffi.require_gpu()
+            device = x.device if isinstance(x, torch.Tensor) and x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+            self.build(tuple(x.shape), device)
+            for w in self._weights.values():
+                if w.device != device:
+                    w.data = w.data.to(device)                # (the Parameter an optimiser holds stays the same object)
+                w.requires_grad_(bool(self.trainable))
+            tensors = [self._weights.get(n) for n in self.PARAM_NAMES]
         return backend._pcen_run(
             x, lambda n, device: self._consts.get(('pcen', n), device, lambda: backend.pcen_band_table(self._params, n)),
-            self.eps, self.data_format)
+            self.eps, self.data_format, tensors)
 
     def get_config(self):
         config = super(PCEN, self).get_config()
-        config.update({'smooth_coef': self.smooth_coef, 'alpha': self.alpha, 'delta': self.delta, 'r': self.r,
-                       'eps': self.eps, 'data_format': self.data_format_original})
+        values = {'smooth_coef': self.smooth_coef, 'alpha': self.alpha, 'delta': self.delta, 'r': self.r}
+        for name, w in zip(self._trainable_names, self.weights):
+            values[name] = w.detach().cpu().numpy().astype(np.float64).tolist()       # the learned values
+        config.update(values)
+        config.update({'eps': self.eps, 'data_format': self.data_format_original})
+        if self._trainable_names:
+            config['trainable_params'] = self.trainable_params
         return config
 
 

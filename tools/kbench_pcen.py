@@ -7,7 +7,8 @@ after about half a second of continuous replay; beside each kernel, alternating 
 device-to-device copy (Tensor.copy_) that moves the SAME number of bytes (read + written).  Two blocks, channels_first:
 the headline output 256 x 83 x 128 (10.9 MB per stream, stays in the Infinity Cache) and 2048 x 998 x 80 (654 MB per
 stream, does not).  Forward reads E and writes y (with the smoother kept for a backward pass: writes S too); backward reads
-E, S and gy and writes gE.
+E, S and gy and writes gE; the backward pass of a learned PCEN (kpr_pcen_bwd_params_f32: two launches, the second reduces
+4 / frames of a block) reads the same and writes gE and the (4, bands) parameter gradients, or the latter alone.
 
     python tools/kbench_pcen.py [--out FILE] [--commit HASH]        needs a GPU: there is no fallback."""
 import argparse
@@ -48,8 +49,24 @@ def variants(b, t, m, dev):
             return (lambda: _ffi._call("kpr_pcen_bwd_f32", dev, *args)), (x, smooth, gy, gx)
         return make, 4
 
+    def backward_params(want_gx):
+        def make():
+            x = torch.rand((b, 1, t, m), device=dev)
+            _, smooth = _ffi.pcen(x, FMT, params, 1e-6, want_smooth=True)
+            gy, gx = torch.randn_like(x), (torch.empty_like(x) if want_gx else None)
+            geom = _ffi._pcen_geometry(x, FMT)
+            gp = torch.empty((4, m), device=dev)
+            ws_bytes = int(_ffi.lib().kpr_pcen_bwd_params_workspace_bytes(*geom[:3]))
+            ws = _ffi.workspace(ws_bytes, dev)
+            args = (_ffi.ptr(x), _ffi.ptr(smooth), _ffi.ptr(gy), *geom, *(_ffi.ptr(p) for p in params), 1e-6, _ffi.ptr(gx),
+                    _ffi.ptr(gp), _ffi.ptr(ws), ws_bytes)
+            return (lambda: _ffi._call("kpr_pcen_bwd_params_f32", dev, *args)), (x, smooth, gy, gx, gp, ws)
+        return make, 4 if want_gx else 3
+
     return {"forward (E -> y)": forward(False), "forward keeping the smoother (E -> y, S)": forward(True),
-            "backward (E, S, gy -> gE)": backward()}
+            "backward (E, S, gy -> gE)": backward(),
+            "backward with parameter gradients (E, S, gy -> gE, g)": backward_params(True),
+            "parameter gradients alone (E, S, gy -> g)": backward_params(False)}
 
 
 def main():
