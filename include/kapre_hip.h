@@ -514,6 +514,36 @@ int kpr_pcen_bwd_params_f32(const float* x, const float* smooth, const float* gy
                             float eps, float* gx /* may be NULL */, float* gparams /* (4, n_bands) */, void* workspace,
                             size_t workspace_bytes, kpr_stream_t stream);
 
+/* ---- Resample: rational sample-rate conversion, kapre_amd.signal.Resample -------------------------------------------
+ * Band-limited interpolation with a Hann-windowed sinc ("sinc_interp_hann").  With g = gcd(orig_freq, new_freq),
+ * orig = orig_freq / g, new = new_freq / g, base = rolloff min(orig, new), L = lowpass_filter_width:
+ *   h(tau) = (base / orig) sinc(base tau) cos^2(pi base tau / (2 L)) for |base tau| < L, else 0     (sinc(t) = sin(pi t) / (pi t))
+ *   y[m]   = sum_n x[n] h(n / orig - m / new),  x[n] = 0 outside 0 <= n < T,  m = 0 .. ceil(new T / orig) - 1
+ * and the adjoint gx[n] = sum_m gy[m] h(n / orig - m / new).  Both are one polyphase gather
+ *   out[i] = sum_{k < n_taps} table[i mod n_phases][k] * in[(i div n_phases) * step + first[i mod n_phases] + k]
+ * (reads outside 0 .. in_len - 1 give 0): forward (n_phases, step) = (new, orig), adjoint (orig, new), each with its own table.
+ * kpr_resample_table_size / kpr_resample_table / kpr_resample_plan are host only and touch no device.
+ *  _table_size: the shape of one direction's table (adjoint = 0 / 1).  n_taps is the largest support of a phase.  Supported:
+ *               n_taps <= 128 and n_phases * n_taps * 4 <= 1 MiB, else KPR_E_UNSUPPORTED (the text names the table's size);
+ *               rates <= 0, lowpass_filter_width < 1, rolloff outside (0, 1]: KPR_E_BADARG.
+ *  _table:      table_host (n_phases, n_taps) float32 row-major and first_host (n_phases) int32.  Coefficients are computed in
+ *               double and rounded once; a row is padded with 0.0 behind its support; first[] rises with the phase.
+ *  _plan:       *outputs_per_tile = the consecutive outputs of one signal that a workgroup's staged input span serves (a whole
+ *               number of n_phases): tile seams for tests.
+ *  _f32:        x: float32 (batch, in_len, channels) [LAST] or (batch, channels, in_len) [FIRST]; out: the same with out_len
+ *               (forward: ceil(new in_len / orig); adjoint: the forward's input length).  table_dev / first_dev: device copies of
+ *               what _table wrote for (n_phases, n_taps, step).  One launch, forward or adjoint; the sum of an output runs over
+ *               k in ascending order in float32 FMAs: the same inputs give the same bits (no atomics).  4-byte aligned pointers;
+ *               x and out must not overlap; 2^30 elements or more per signal (per batch item for LAST): KPR_E_UNSUPPORTED.
+ *               batch == 0 or out_len == 0: returns 0, launches nothing. */
+int kpr_resample_table_size(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, int* n_phases,
+                            int* n_taps, int* step);
+int kpr_resample_table(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, float* table_host,
+                       int32_t* first_host);
+int kpr_resample_plan(int n_phases, int n_taps, int step, int* outputs_per_tile);
+int kpr_resample_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table_dev,
+                     const int32_t* first_dev, int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

@@ -25,7 +25,7 @@ from .time_frequency import (
 )
 
 from . import signal
-from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample
 
 from . import augmentation
 from .augmentation import SpecAugment, ChannelSwap
@@ -93,6 +93,7 @@ __all__ = [
     'MuLawEncoding',
     'MuLawDecoding',
     'LogmelToMFCC',
+    'Resample',
     'SpecAugment',
     'ChannelSwap',
     'get_stft_magnitude_layer',

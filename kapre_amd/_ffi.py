@@ -171,6 +171,16 @@ EXPORTS = {
                                                ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # Resample (kapre_amd/signal.py)
+    "kpr_resample_table_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_int)]),
+    "kpr_resample_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_resample_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "kpr_resample_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -684,3 +694,78 @@ def pcen_bwd_params(x, smooth, g, fmt, params, eps: float, want_gx: bool = True)
     _call("kpr_pcen_bwd_params_f32", x.device, ptr(x), ptr(smooth), ptr(g), *geom, *(ptr(p) for p in params), float(eps),
           ptr(gx), ptr(gparams), ptr(ws), ws_bytes)
     return gx, gparams
+
+
+# Resample (kapre_amd/signal.py)
+E_UNSUPPORTED = -2
+
+
+def resample_table_size(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint: bool):
+    """(n_phases, n_taps, step) of one direction's polyphase table (host only).  ``ValueError`` naming the table's size when
+    the library does not support it, ``RuntimeError`` for any other failure."""
+    P, n, q = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().kpr_resample_table_size(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff),
+                                       int(bool(adjoint)), ctypes.byref(P), ctypes.byref(n), ctypes.byref(q))
+    if rc == E_UNSUPPORTED:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_resample_table_size")
+    return P.value, n.value, q.value
+
+
+def resample_table(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint: bool):
+    """(table, first, step): the float32 (n_phases, n_taps) coefficients and the int32 (n_phases,) first input offsets of one
+    direction, as numpy arrays (host only)."""
+    n_phases, n_taps, step = resample_table_size(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint)
+    table = np.zeros((n_phases, n_taps), dtype=np.float32)
+    first = np.zeros(n_phases, dtype=np.int32)
+    check(lib().kpr_resample_table(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff),
+                                   int(bool(adjoint)), table.ctypes.data_as(ctypes.c_void_p),
+                                   first.ctypes.data_as(ctypes.c_void_p)), "kpr_resample_table")
+    return table, first, step
+
+
+def resample_plan(n_phases: int, n_taps: int, step: int) -> int:
+    """outputs_per_tile of kpr_resample_f32's dispatch (host only)."""
+    n = ctypes.c_int(0)
+    check(lib().kpr_resample_plan(int(n_phases), int(n_taps), int(step), ctypes.byref(n)), "kpr_resample_plan")
+    return n.value
+
+
+class ResamplePlan:
+    """One direction of a rate conversion on one device: the table and the offsets there, and their shape."""
+    __slots__ = ("table", "first", "n_phases", "n_taps", "step")
+
+    def __init__(self, table, first, step):
+        self.table, self.first, self.step = table, first, int(step)
+        self.n_phases, self.n_taps = int(table.shape[0]), int(table.shape[1])
+
+
+_resample_plans = {}
+
+
+def resample_plans(orig_freq, new_freq, lowpass_filter_width, rolloff, device):
+    """(forward, adjoint) ``ResamplePlan`` of the conversion on ``device``, built and uploaded on first use and kept."""
+    import torch
+    key = (int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), str(device))
+    plans = _resample_plans.get(key)
+    if plans is None:
+        with _lock:
+            plans = _resample_plans.get(key)
+            if plans is None:
+                made = []
+                for adjoint in (False, True):
+                    table, first, step = resample_table(*key[:4], adjoint)
+                    made.append(ResamplePlan(torch.from_numpy(table).to(device), torch.from_numpy(first).to(device), step))
+                plans = _resample_plans[key] = tuple(made)
+    return plans
+
+
+def resample(x, fmt, plan: ResamplePlan, out_len: int):
+    """The polyphase gather ``plan`` of the float32 waveform ``x`` along time: ``out_len`` samples per signal (the forward
+    pass with the forward plan, its adjoint with the adjoint plan and the forward's input length)."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    out = torch.empty(shape_of(fmt, b, c, int(out_len)), dtype=torch.float32, device=x.device)
+    _call("kpr_resample_f32", x.device, ptr(x), b, c, t, layout(fmt), ptr(plan.table), ptr(plan.first), plan.n_phases,
+          plan.n_taps, plan.step, int(out_len), ptr(out))
+    return out

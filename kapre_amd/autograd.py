@@ -12,6 +12,7 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   of the cotangent (one kernel); mu-law decoding of float codes has an elementwise backward kernel, mu-law encoding
   returns integers and ends the tape; ``PCEN`` keeps its smoother ``S`` (the forward kernel's second output) and runs
   one backward kernel, the forward scan in reversed time (input gradient only: its parameters are constants);
+  ``Resample^T`` is the forward's polyphase kernel with the adjoint table;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -345,9 +346,23 @@ def _functions():
             gx, gp = _ffi.pcen_bwd_params(x, smooth, g, ctx.data_format, params, ctx.eps, want_gx=need[0])
             return (gx, None) + tuple(gp[i] if need[2 + i] else None for i in range(4)) + (None,)
 
+    class ResampleFn(torch.autograd.Function):
+        """y = R x, a linear map: backward = the same polyphase kernel with the adjoint table (one launch)."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, forward_plan, adjoint_plan, out_len):
+            ctx.data_format, ctx.adjoint_plan = data_format, adjoint_plan
+            ctx.in_len = _ffi.dims_of(x.shape, data_format)[2]
+            return _ffi.resample(x.detach(), data_format, forward_plan, out_len)
+
+        @staticmethod
+        def backward(ctx, g):
+            g = g.contiguous().to(torch.float32)
+            return _ffi.resample(g, ctx.data_format, ctx.adjoint_plan, ctx.in_len), None, None, None, None
+
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
-               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn)
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, resample=ResampleFn)
     return _FN
 
 
@@ -412,3 +427,7 @@ def freq_map_concat(x, data_format):
 
 def pcen(x, data_format, params, eps):
     return _functions()['pcen'].apply(x, data_format, *params, eps)
+
+
+def resample(x, data_format, forward_plan, adjoint_plan, out_len):
+    return _functions()['resample'].apply(x, data_format, forward_plan, adjoint_plan, out_len)

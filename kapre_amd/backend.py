@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen`` has no counterpart there.
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen`` and ``resample`` have no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -418,3 +418,75 @@ def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='defaul
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt,
                      tensors if any(t is not None for t in tensors) else None)
+
+
+# --------------------------------------------------------------------------------------
+# sample-rate conversion
+# --------------------------------------------------------------------------------------
+def resample_parameters(orig_freq, new_freq, lowpass_filter_width, rolloff):
+    """Validated (orig_freq, new_freq, lowpass_filter_width, rolloff): positive integer rates, lowpass_filter_width >= 1,
+    0 < rolloff <= 1 (``ValueError``)."""
+    for name, v in (('orig_freq', orig_freq), ('new_freq', new_freq)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError('resample: %s must be a positive integer, got %r' % (name, v))
+    if (isinstance(lowpass_filter_width, bool) or not isinstance(lowpass_filter_width, (int, np.integer))
+            or lowpass_filter_width < 1):
+        raise ValueError('resample: lowpass_filter_width must be an integer >= 1, got %r' % (lowpass_filter_width,))
+    if np.ndim(rolloff) != 0 or not 0.0 < float(rolloff) <= 1.0:
+        raise ValueError('resample: 0 < rolloff <= 1 is required, got %r' % (rolloff,))
+    if max(int(orig_freq), int(new_freq)) >= 2 ** 31:
+        raise ValueError('resample: the rates must be below 2^31, got %r and %r' % (orig_freq, new_freq))
+    return int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff)
+
+
+def resample_length(t, orig_freq: int, new_freq: int):
+    """ceil(new t / orig) with the rates reduced by their gcd; ``None`` stays ``None``."""
+    if t is None:
+        return None
+    g = int(np.gcd(orig_freq, new_freq))
+    orig, new = orig_freq // g, new_freq // g
+    return -(-new * int(t) // orig)
+
+
+_RESAMPLE_SUPPORTED = set()          # parameter tuples whose tables kpr_resample_table_size has accepted
+
+
+def _resample_run(x, params, fmt):
+    """``x`` (rank 3) through the conversion ``params`` = resample_parameters(...); ``fmt`` is resolved."""
+    import torch
+
+    from . import autograd
+    if len(x.shape) != 3:
+        raise ValueError('resample expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('resample has float32 kernels only; got a float64 input (cast it to float32)')
+    if params[0] == params[1]:
+        return x                                                     # nothing to convert, nothing launched
+    grad = autograd.needs_grad(x)
+    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
+    forward, adjoint = _ffi.resample_plans(*params, x.device)
+    out_len = resample_length(_ffi.dims_of(x.shape, fmt)[2], params[0], params[1])
+    if grad:
+        return autograd.resample(x, fmt, forward, adjoint, out_len)
+    return _ffi.resample(x, fmt, forward, out_len)
+
+
+def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default'):
+    """Sample-rate conversion of a waveform batch on the GPU by the rational ratio new_freq / orig_freq: band-limited
+    interpolation with a Hann-windowed sinc (the "sinc_interp_hann" method).  (b, time, ch) for ``channels_last``,
+    (b, ch, time) for ``channels_first``; float32 out with ceil(new_freq time / orig_freq) samples.
+
+        h(tau) = (base / orig) sinc(base tau) cos^2(pi base tau / (2 L)) for |base tau| < L,   y[m] = sum_n x[n] h(n / orig - m / new)
+
+    with the rates reduced by their gcd, base = rolloff min(orig, new), L = lowpass_filter_width.  One kernel launch; a
+    tensor that ``requires_grad`` gets a ``grad_fn`` whose backward is one launch of the same kernel with the adjoint table.
+    ``orig_freq == new_freq`` returns ``x`` itself.  ``ValueError`` for a ratio whose polyphase table the library does not
+    support (more than 128 taps or 1 MiB), ``TypeError`` for a float64 input."""
+    validate_data_format_str(data_format)
+    params = resample_parameters(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    if params[0] != params[1] and params not in _RESAMPLE_SUPPORTED:
+        for adjoint in (False, True):                      # an O(n_phases) walk on the host: once per conversion
+            _ffi.resample_table_size(*params, adjoint)
+        _RESAMPLE_SUPPORTED.add(params)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return _resample_run(x, params, fmt)

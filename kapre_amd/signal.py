@@ -3,7 +3,8 @@
 constructor signatures, validation, get_config() keys and output shapes; the arithmetic runs in
 libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with a DCT-II matrix).
 MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.mu_law_encoding / mu_law_decoding
-(kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32)."""
+(kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32).  Resample has no counterpart in the reference: it is
+the step in front of every front end (kpr_resample_f32)."""
 import math
 
 import numpy as np
@@ -12,7 +13,7 @@ from . import _ffi, autograd, backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
-__all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC']
+__all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample']
 
 
 def _resolve_format(fmt):
@@ -244,4 +245,44 @@ class LogmelToMFCC(Layer):
     def get_config(self):
         config = super(LogmelToMFCC, self).get_config()
         config.update({'n_mfccs': self.n_mfccs, 'data_format': self.data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class Resample(Layer):
+    """Sample-rate conversion from ``orig_freq`` to ``new_freq`` (positive integers; any rational ratio whose polyphase table
+    has at most 128 taps and 1 MiB -- every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz does): band-limited
+    interpolation with a Hann-windowed sinc of ``lowpass_filter_width`` zero crossings a side and cutoff ``rolloff`` times the
+    lower Nyquist frequency (``backend.resample``).
+
+    (batch, time, ch) -> (batch, ceil(new_freq time / orig_freq), ch) for ``channels_last``;
+    (batch, ch, time) -> (batch, ch, ceil(new_freq time / orig_freq)) for ``channels_first``.  numpy or torch, float32 (a
+    float64 input raises ``TypeError``).  One launch; differentiable (one more launch of the same kernel).  ``orig_freq ==
+    new_freq`` returns its input."""
+
+    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default', **kwargs):
+        super(Resample, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        self._params = backend.resample_parameters(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff = self._params
+        if self.orig_freq != self.new_freq:
+            for adjoint in (False, True):                    # ValueError for a table the library does not support
+                _ffi.resample_table_size(*self._params, adjoint)
+        self.data_format_str = data_format
+        self.data_format = _resolve_format(data_format)
+        self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
+
+    def compute_output_shape(self, input_shape):
+        """(b, t, ch) -> (b, ceil(new t / orig), ch); (b, ch, t) -> (b, ch, ceil(new t / orig))"""
+        b, c, t = _ffi.dims_of(input_shape, self.data_format)
+        return _ffi.shape_of(self.data_format, b, c, backend.resample_length(t, self.orig_freq, self.new_freq))
+
+    def call(self, x):
+        return backend._resample_run(x, self._params, self.data_format)
+
+    def get_config(self):
+        config = super(Resample, self).get_config()
+        config.update({'orig_freq': self.orig_freq, 'new_freq': self.new_freq,
+                       'lowpass_filter_width': self.lowpass_filter_width, 'rolloff': self.rolloff,
+                       'data_format': self.data_format_str})
         return config
