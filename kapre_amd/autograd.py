@@ -30,6 +30,9 @@ from . import _ffi
 
 _CH_LAST_STR = 'channels_last'
 
+# activations (complex spectrum + magnitudes) ChainFn.backward recomputes at a time; read at call time
+CHAIN_RECOMPUTE_BYTES = 256 << 20
+
 
 def needs_grad(x) -> bool:
     """True when the caller expects the layer output to be differentiable w.r.t. ``x``."""
@@ -226,7 +229,7 @@ def _functions():
                 per_item = per_item * (n_fft // 2 + 1) * 3 // max(1, hop)
             else:
                 per_item *= 4
-            step = int(max(1, min(n, (256 << 20) // max(1, per_item))))
+            step = int(max(1, min(n, CHAIN_RECOMPUTE_BYTES // max(1, per_item))))
             gx = torch.empty_like(x)
             for i0 in range(0, max(n, 1), step):
                 with torch.enable_grad():

@@ -25,6 +25,15 @@ def _geom(kw, x, time_axis_last):
     return b, c, t, n_fft, win, hop
 
 
+@pytest.fixture(scope="module", autouse=True)
+def program():
+    """tests/abi/test_abi is a build product that lives inside tests/ (kapre_amd/build.py puts it there, next to its source): a
+    tests/ tree that was put in place after the build does not have it.  Host compile of one file against the built library."""
+    from kapre_amd import build
+    if not os.path.exists(EXE) and os.path.exists(build.LIB):
+        build.build_abi_test()
+
+
 def test_binary_is_built_and_links_only_the_abi():
     assert os.path.exists(EXE), "tests/abi/test_abi missing: run python -m kapre_amd.build"
     out = subprocess.run(["ldd", EXE], capture_output=True, text=True).stdout

@@ -1,8 +1,8 @@
 """-m gpu: the layers are differentiable, like the TensorFlow graphs they replace (a Kapre front end sits inside
-model.fit; /root/reference/kapre/time_frequency.py:146-187, :289-319, :351-359, :402, :535-548, backend.py:186-192).
+model.fit; kapre/time_frequency.py:146-187, :289-319, :351-359, :402, :535-548, backend.py:186-192).
 
 Checker: the same layer arithmetic written with plain torch float64 ops on the CPU and differentiated by torch's own
-autograd (`ref_*` below, test infrastructure only); the HIP backward passes (kapre_amd/autograd.py,
+autograd (`ref_*` in tests/grad_model.py, test infrastructure only); the HIP backward passes (kapre_amd/autograd.py,
 csrc/kpr_grad_kernels.h, and the forward kernels they reuse as adjoints) must give the same input gradient for the same
 scalar loss <y, R> with a fixed random R.  Tolerance: 2e-4 of the largest gradient entry (float32), 1e-9 (float64).
 """
@@ -19,87 +19,11 @@ from kapre_amd import Delta
 
 pytestmark = pytest.mark.gpu
 
-CL, CF = 'channels_last', 'channels_first'
+from grad_model import (CL, CF, ref_stft, ref_istft, ref_db, ref_frame, to_bct, spec_from_bcfk, spec_to_bcfk, loss_of,
+                        cotangent, check, wave)
 
 
-# ---------------------------------------------------------------------------------------------
-# the checker: torch float64 on the CPU
-# ---------------------------------------------------------------------------------------------
-def ref_stft(x_bct, n_fft, win, hop, window, pad_begin, pad_end):
-    """tf.signal.stft as STFT.call drives it (time_frequency.py:164-182): (B, C, T) -> (B, C, F, K) complex128."""
-    x = x_bct
-    if pad_begin:
-        x = torch.nn.functional.pad(x, (n_fft - hop, 0))
-    t = x.shape[-1]
-    if pad_end:
-        n_frames = -(-t // hop)
-        x = torch.nn.functional.pad(x, (0, max(0, (n_frames - 1) * hop + win - t)))
-    frames = x.unfold(-1, win, hop) * torch.as_tensor(window, dtype=torch.float64)
-    return torch.fft.rfft(frames, n=n_fft)
-
-
-def ref_istft(spec_bcfk, n_fft, win, hop, synth):
-    """tf.signal.inverse_stft (time_frequency.py:307-314): (B, C, F, K) -> (B, C, (F - 1) hop + win)."""
-    y = torch.fft.irfft(spec_bcfk, n=n_fft)[..., :win] * torch.as_tensor(synth, dtype=torch.float64)
-    b, c, f, _ = y.shape
-    out = torch.zeros(b, c, (f - 1) * hop + win, dtype=torch.float64)
-    for i in range(f):
-        out[..., i * hop:i * hop + win] = out[..., i * hop:i * hop + win] + y[..., i, :]
-    return out
-
-
-def ref_db(x, ref_value, amin, dyn):
-    """backend.magnitude_to_decibel (backend.py:186-192), items = batch entries."""
-    log10 = lambda v: torch.log(v) / np.log(10.0)
-    amin_t = torch.tensor(amin, dtype=x.dtype)
-    l = 10.0 * log10(torch.maximum(x, amin_t)) - 10.0 * np.log10(max(amin, ref_value))
-    m = l.reshape(l.shape[0], -1).amax(dim=1).reshape([-1] + [1] * (l.dim() - 1))
-    return torch.maximum(l, m - dyn)
-
-
-def to_bct(x, fmt):
-    return x.permute(0, 2, 1) if fmt == CL else x
-
-
-def spec_from_bcfk(s, fmt):
-    return s.permute(0, 2, 3, 1) if fmt == CL else s
-
-
-def spec_to_bcfk(s, fmt):
-    return s.permute(0, 3, 1, 2) if fmt == CL else s
-
-
-def loss_of(y, r):
-    """<y, R> with R real; a complex y is viewed as (re, im) pairs."""
-    if y.is_complex():
-        y = torch.view_as_real(y)
-    return (y * r.to(y.device, y.dtype)).sum()
-
-
-def cotangent(shape, complex_, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(tuple(shape) + ((2,) if complex_ else ()), generator=g, dtype=torch.float64)
-
-
-def check(got, want, tol, what):
-    got = got.detach().cpu()
-    if got.is_complex():
-        got, want = torch.view_as_real(got.to(torch.complex128)), torch.view_as_real(want)
-    got, want = got.to(torch.float64), want.to(torch.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    scale = float(want.abs().max())
-    assert scale > 0, what
-    err = float((got - want).abs().max()) / scale
-    assert err <= tol, '%s: max error %.3g of the largest gradient entry (limit %.1g)' % (what, err, tol)
-
-
-def wave(batch, ch, t, fmt, seed, dtype=torch.float32):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand((batch, ch, t), generator=g, dtype=torch.float64) * 2 - 1
-    x = x * torch.linspace(0.2, 1.0, batch, dtype=torch.float64).reshape(-1, 1, 1)      # items of different loudness
-    x = (x.permute(0, 2, 1) if fmt == CL else x).contiguous()
-    return x.to(dtype)
-
+# the checker (torch float64 on the CPU) lives in tests/grad_model.py; tests/test_grad_model_host.py pins it
 
 # ---------------------------------------------------------------------------------------------
 # STFT
@@ -428,15 +352,6 @@ def test_no_grad_and_detached_inputs_take_the_plain_path():
 # ---------------------------------------------------------------------------------------------
 # Frame / Energy / Delta (signal.py:22-240, time_frequency.py:563-644)
 # ---------------------------------------------------------------------------------------------
-def ref_frame(x_bct, length, hop, pad_end, pad_value):
-    """tf.signal.frame on the last axis: (B, C, T) -> (B, C, F, L)."""
-    t = x_bct.shape[-1]
-    if pad_end:
-        n_frames = -(-t // hop)
-        x_bct = torch.nn.functional.pad(x_bct, (0, max(0, (n_frames - 1) * hop + length - t)), value=pad_value)
-    return x_bct.unfold(-1, length, hop)
-
-
 @pytest.mark.parametrize('fmt', [CL, CF])
 @pytest.mark.parametrize('length,hop,pad_end,t', [(256, 64, False, 3000), (200, 77, True, 2999), (64, 64, True, 1000)])
 def test_frame_backward(fmt, length, hop, pad_end, t):
