@@ -1,0 +1,455 @@
+// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN and
+// Resample entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h, kpr_augment_kernels.h,
+// kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_resample_kernels.h).
+// Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
+#pragma once
+
+namespace kpr {
+
+// ---- Magnitude / Phase: |x| (phase = 0) or the angle (1) of n complex64 (T = float) / complex128 (T = double) values ----
+// (the two precisions have always worded a negative n differently)
+template <typename T>
+static int run_cplx_to_real(const void* x, int64_t n, int phase, T* out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (n < 0) return fail(KPR_E_BADARG, sizeof(T) == 4 ? "negative size" : "negative element count");
+    if (n == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    const dim3 grid(grid_1d(n, 256));
+    if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(k_cplx_to_real, grid, dim3(256), 0, (hipStream_t)stream, (const float2*)x, (long long)n, phase, out);
+    else hipLaunchKernelGGL(k_cplx_to_real_f64, grid, dim3(256), 0, (hipStream_t)stream, (const double2*)x, (long long)n, phase, out);
+    return launch_check(sizeof(T) == 4 ? "k_cplx_to_real" : "k_cplx_to_real_f64");
+}
+
+// ---- backward passes (kpr_grad_kernels.h): launch helpers of the C entry points ----
+template <typename T>
+static int run_cplx_bwd(const void* x, const T* g, int64_t n, int phase, void* gx, kpr_stream_t stream) {
+    if (n < 0) return fail(KPR_E_BADARG, "negative element count");
+    if (n == 0) return 0;
+    if (!x || !g || !gx) return fail(KPR_E_BADARG, "x / g / gx must not be NULL");
+    hipLaunchKernelGGL(k_cplx_to_real_bwd<T>, dim3(grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const GCplx<T>*)x, g, (long long)n, phase, (GCplx<T>*)gx);
+    return launch_check("k_cplx_to_real_bwd");
+}
+template <typename T>
+static int run_edge_scale(const void* in, int64_t n, int n_freq, int inner, int n_fft, T s_edge, T s_mid, void* out,
+                          kpr_stream_t stream) {
+    if (n < 0 || n_freq <= 0 || inner <= 0 || n_fft <= 0) return fail(KPR_E_BADARG, "bad sizes");
+    if (n_freq != n_fft / 2 + 1) return fail(KPR_E_BADARG, "n_freq %d is not n_fft / 2 + 1 (n_fft %d)", n_freq, n_fft);
+    if (n % ((int64_t)n_freq * inner)) return fail(KPR_E_BADARG, "element count is not a multiple of n_freq * inner");
+    if (n == 0) return 0;
+    if (!in || !out) return fail(KPR_E_BADARG, "in / out must not be NULL");
+    const int nyq = (n_fft & 1) ? -1 : n_fft / 2;
+    hipLaunchKernelGGL(k_spec_edge_scale<T>, dim3(grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const GCplx<T>*)in, (long long)n, n_freq, inner, nyq, s_edge, s_mid, (GCplx<T>*)out);
+    return launch_check("k_spec_edge_scale");
+}
+template <typename T>
+static int run_db_bwd(const T* x, const T* gy, int64_t n_items, int64_t item_size, double ref_value, double amin,
+                      double dynamic_range, T* gx, kpr_stream_t stream) {
+    if (n_items < 0 || item_size < 0) return fail(KPR_E_BADARG, "negative size");
+    if (int e = check_db_values(ref_value, amin, dynamic_range)) return e;
+    if (n_items == 0 || item_size == 0) return 0;
+    if (!x || !gy || !gx) return fail(KPR_E_BADARG, "x / gy / gx must not be NULL");
+    if (n_items > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "decibel backward: more than 2^31 - 1 items");
+    const double ref_term = 10.0 * std::log10(std::max(amin, ref_value));
+    // float32: the forward (make_db / to_db) raises amin to the smallest normal float -- the backward floors at the same value
+    const double amin_k = sizeof(T) == 4 ? std::max(amin, 1.17549435e-38) : amin;
+    hipLaunchKernelGGL(k_db_bwd<T>, dim3((unsigned)n_items), dim3(1024), 0, (hipStream_t)stream, x, gy,
+                       (long long)item_size, (T)amin_k, (T)ref_term, (T)dynamic_range, gx);
+    return launch_check("k_db_bwd");
+}
+
+// ---- mu-law companding / ConcatenateFrequencyMap (kpr_companding_kernels.h): launch helpers of the C entry points ----
+static int mu_law_args(int64_t n, int quantization_channels, MuLawDev* p) {
+    if (n < 0) return fail(KPR_E_BADARG, "negative element count");
+    if (quantization_channels < 2 || quantization_channels > 65536)
+        return fail(KPR_E_BADARG, "quantization_channels %d outside [2, 65536]", quantization_channels);
+    if (n > kCompandMaxElems)
+        return fail(KPR_E_UNSUPPORTED, "%lld elements: one call takes at most 2^40", (long long)n);
+    const double q = quantization_channels, mu = q - 1.0, l2q = std::log2(q), c = l2q / mu, inv = 1.0 / mu;
+    p->mu = (float)mu;
+    p->half_mu = (float)(0.5 * mu);
+    p->half_q = (float)(0.5 * q);
+    p->inv_log2q = (float)(1.0 / l2q);
+    p->c_hi = (float)c;
+    p->c_lo = (float)(c - (double)p->c_hi);
+    p->inv_hi = (float)inv;
+    p->inv_lo = (float)(inv - (double)p->inv_hi);
+    p->gcoef = (float)(2.0 * std::log(q) / (mu * mu));
+    return 0;
+}
+
+// the pointers of a streaming call: not NULL, 4-byte aligned, out either the input itself or clear of it
+static int stream_ptrs(const void* in, const void* in2, const void* out, int64_t n, const char* names) {
+    if (!in || !in2 || !out) return fail(KPR_E_BADARG, "%s must not be NULL", names);
+    if ((((uintptr_t)in) | ((uintptr_t)in2) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "%s must be 4-byte aligned", names);
+    const uintptr_t nb = (uintptr_t)n * 4, oa = (uintptr_t)out;
+    for (const void* q : {in, in2}) {
+        const uintptr_t a = (uintptr_t)q;
+        if (a != oa && a < oa + nb && oa < a + nb) return fail(KPR_E_BADARG, "%s overlap (only out == in, in place, is allowed)", names);
+    }
+    return 0;
+}
+
+template <int OP>
+static int run_mu_law(const void* in, const void* g, void* out, int64_t n, int quantization_channels, const char* names,
+                      kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    MuLawDev p;
+    if (int e = mu_law_args(n, quantization_channels, &p)) return e;
+    if (n == 0) return 0;
+    if (int e = stream_ptrs(in, g, out, n, names)) return e;
+    const long long groups = n / 4 + 1;
+    hipLaunchKernelGGL(k_mu_law<OP>, dim3((unsigned)((groups + kStreamChunk - 1) / kStreamChunk)), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned*)in, (const unsigned*)g, (unsigned*)out, (long long)n, p);
+    return launch_check(OP == MU_ENCODE ? "k_mu_law_encode" : OP == MU_DECODE_BWD ? "k_mu_law_decode_bwd" : "k_mu_law_decode");
+}
+
+template <bool DROP>
+static int run_freq_map(const float* in, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* out,
+                        kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (batch < 0 || channels <= 0 || frames < 0 || n_freq <= 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/frames/n_freq/layout");
+    const long long plane = (long long)frames * n_freq;
+    if (plane * ((long long)channels + 1) > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "frames * n_freq * (channels + 1) = %lld elements per item: 2^31 or more is not supported",
+                    plane * ((long long)channels + 1));
+    if (batch == 0 || plane == 0) return 0;
+    const long long n_in = batch * plane * (channels + (DROP ? 1 : 0)), n_out = batch * plane * (channels + (DROP ? 0 : 1));
+    if (!in || !out) return fail(KPR_E_BADARG, "%s must not be NULL", DROP ? "g / gx" : "x / out");
+    if ((((uintptr_t)in) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out;
+        if (ia < oa + (uintptr_t)n_out * 4 && oa < ia + (uintptr_t)n_in * 4) return fail(KPR_E_BADARG, "input and output overlap");
+    }
+    const bool cl = layout == KPR_CHANNELS_LAST;
+    FmapArgs a;
+    a.rin = (unsigned)(cl ? channels : plane * channels);
+    a.rmap = (unsigned)(cl ? 1 : plane);
+    a.n_freq = (unsigned)n_freq;
+    a.osz = (unsigned)(plane * (channels + (DROP ? 0 : 1)));
+    a.last = n_freq > 1 ? n_freq - 1 : -1;
+    a.inv = n_freq > 1 ? (float)(1.0 / (double)(n_freq - 1)) : 0.0f;
+    a.chunks = (int)(((long long)(a.osz >> 2) + kStreamChunk) / kStreamChunk);
+    if (batch * a.chunks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many items");
+    const dim3 grid((unsigned)(batch * a.chunks));
+    if (cl)
+        hipLaunchKernelGGL((k_freq_map<DROP, true>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)in, (unsigned*)out, a);
+    else
+        hipLaunchKernelGGL((k_freq_map<DROP, false>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)in, (unsigned*)out, a);
+    return launch_check(DROP ? "k_freq_map_drop" : "k_freq_map_concat");
+}
+
+// ---- PCEN (kpr_pcen_kernels.h): argument checks and launch of the forward / backward C entry points ----
+// x (and smooth, gy for the backward pass) -> out; smooth_out only for the forward pass, may be NULL.
+// gparams != NULL: the backward pass with the parameter gradients (kpr_pcen_bwd_params_f32), out = gx may then be NULL
+static size_t pcen_params_workspace(int64_t outer, int64_t frames, int64_t inner) {
+    return outer > 0 && frames > 0 && inner > 0 ? (size_t)16 * (size_t)outer * (size_t)inner : 0;
+}
+
+static int run_pcen(bool bwd, const float* x, const float* smooth, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                    int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
+                    float* out, float* smooth_out, kpr_stream_t stream, bool with_params = false, float* gparams = nullptr,
+                    void* workspace = nullptr, size_t workspace_bytes = 0) {
+    if (int e = api_enter()) return e;
+    if (outer < 0 || frames < 0 || inner < 0 || band_div <= 0 || n_bands <= 0)
+        return fail(KPR_E_BADARG, "bad outer/frames/inner/band_div/n_bands");
+    if (with_params && (!gparams || ((uintptr_t)gparams & 3))) return fail(KPR_E_BADARG, "gparams must be a 4-byte aligned pointer");
+    if (outer == 0 || frames == 0 || inner == 0) {
+        if (!with_params) return 0;
+        KPR_HIP(hipMemsetAsync(gparams, 0, (size_t)n_bands * 4 * sizeof(float), (hipStream_t)stream));    // empty sums
+        return 0;
+    }
+    if (inner != (int64_t)n_bands * band_div)
+        return fail(KPR_E_BADARG, "inner = %lld is not n_bands * band_div = %d * %d", (long long)inner, n_bands, band_div);
+    if (!(eps > 0.0f)) return fail(KPR_E_BADARG, "eps must be positive");
+    if (!x || (!out && !with_params) || !s || !alpha || !delta || !r || (bwd && (!smooth || !gy)))
+        return fail(KPR_E_BADARG, with_params ? "x / smooth / gy and the parameter vectors must not be NULL"
+                                  : bwd       ? "x / smooth / gy / gx and the parameter vectors must not be NULL"
+                                              : "x / out and the parameter vectors must not be NULL");
+    if (frames * inner > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "frames * inner = %lld elements per outer item: 2^31 or more is not supported",
+                    (long long)(frames * inner));
+    uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)smooth | (uintptr_t)gy | (uintptr_t)smooth_out | (uintptr_t)workspace;
+    if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4;
+        auto clash = [nb](const void* p, const void* q) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nb && (uintptr_t)q < (uintptr_t)p + nb;
+        };
+        bool bad = clash(out, smooth_out);
+        for (const float* in : {x, smooth, gy}) bad = bad || clash(out, in) || clash(smooth_out, in);
+        if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
+    }
+    if (with_params) {
+        const size_t need = pcen_params_workspace(outer, frames, inner);
+        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4, ng = (uintptr_t)n_bands * 16;
+        auto within = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+        };
+        bool bad = within(gparams, ng, workspace, need);
+        for (const float* t : {x, smooth, gy, (const float*)out}) bad = bad || within(gparams, ng, t, nb) || within(workspace, need, t, nb);
+        for (const float* t : {s, alpha, delta, r}) bad = bad || within(gparams, ng, t, (uintptr_t)n_bands * 4);
+        if (bad) return fail(KPR_E_BADARG, "gparams or the workspace overlaps another argument");
+        if (!workspace || workspace_bytes < need)
+            return fail(KPR_E_WORKSPACE, "workspace of %zu bytes needed (kpr_pcen_bwd_params_workspace_bytes), got %zu", need,
+                        workspace ? workspace_bytes : (size_t)0);
+    }
+    const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
+    PcenArgs a;
+    a.x = x; a.smooth = smooth; a.gy = gy; a.out = out; a.smooth_out = smooth_out;
+    a.s = s; a.alpha = alpha; a.delta = delta; a.r = r;
+    a.eps = eps;
+    a.frames = (int)frames;
+    a.inner = (unsigned)inner;
+    a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
+    a.band_div = (unsigned)band_div;
+    a.n_groups = (long long)outer * a.groups_per_item;
+    a.partials = (float*)workspace;
+    const long long blocks = (a.n_groups + 63) / 64;
+    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
+    const dim3 grid((unsigned)blocks), block(64 * kPcenWaves);
+    const hipStream_t st = (hipStream_t)stream;
+    if (with_params) {
+        if (out) {
+            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
+        } else {
+            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
+        }
+        if (int e = launch_check(out ? "k_pcen_bwd_params" : "k_pcen_bwd_params_only", v4 ? 4 : 1)) return e;
+        hipLaunchKernelGGL(k_pcen_param_reduce, dim3(4u * (unsigned)n_bands), dim3(256), 0, st, (const float*)workspace, gparams,
+                           (long long)outer, (unsigned)inner, (unsigned)band_div, (unsigned)n_bands);
+        return launch_check("k_pcen_param_reduce");
+    }
+    if (bwd) {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD>), grid, block, 0, st, a);
+    } else if (smooth_out) {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
+    } else {
+        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD>), grid, block, 0, st, a);
+    }
+    return launch_check(bwd ? "k_pcen_bwd" : "k_pcen", v4 ? 4 : 1);
+}
+
+// ---- Resample (kpr_resample_kernels.h): the windowed-sinc tables of both directions, the tile plan, the launch ----
+// h(tau) = (base / orig) sinc(base tau) cos^2(pi base tau / (2 L)) for |base tau| < L, base = rolloff min(orig, new), with
+// orig, new reduced by their gcd.  Output phase p of P reads the inputs (block) Q + j with u = j P - p Q:
+// tau = +-u / (orig new) -- h is even, so the forward pass ((P, Q) = (new, orig)) and the adjoint ((orig, new)) are this one
+// construction -- and base tau = rolloff u / max(orig, new).  first[p] is the smallest j with |u| < U = L max / rolloff,
+// n_taps the largest support of a phase; first[] rises with p by at most ceil(Q / P) + 1 a step.
+struct ResampleShape {
+    int P, Q, n_taps;
+    int orig, fnew, L;
+    double rolloff, U;
+};
+
+static int resample_shape(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, ResampleShape* r) {
+    if (orig_freq <= 0 || new_freq <= 0)
+        return fail(KPR_E_BADARG, "orig_freq and new_freq must be positive, got %d and %d", orig_freq, new_freq);
+    if (lowpass_filter_width < 1) return fail(KPR_E_BADARG, "lowpass_filter_width must be at least 1, got %d", lowpass_filter_width);
+    if (!(rolloff > 0.0 && rolloff <= 1.0)) return fail(KPR_E_BADARG, "rolloff must lie in (0, 1], got %g", rolloff);
+    int a = orig_freq, b = new_freq;
+    while (b) { const int t = a % b; a = b; b = t; }
+    r->orig = orig_freq / a;
+    r->fnew = new_freq / a;
+    r->L = lowpass_filter_width;
+    r->rolloff = rolloff;
+    r->P = adjoint ? r->orig : r->fnew;
+    r->Q = adjoint ? r->fnew : r->orig;
+    r->U = (double)lowpass_filter_width * (double)std::max(r->orig, r->fnew) / rolloff;
+    // (the size before the walk over the phases: a support holds at most 2 U / P + 1 inputs)
+    const double est = 2.0 * r->U / (double)r->P + 1.0;
+    if (est > 132.0 || (double)r->P * est * 4.0 > 2.0 * 1048576.0)
+        return fail(KPR_E_UNSUPPORTED, "resample %d -> %d%s: a table of %d phases x about %.0f taps = %.0f bytes; supported are at most 128 "
+                    "taps and 1 MiB (1048576 bytes)", orig_freq, new_freq, adjoint ? " (adjoint)" : "", r->P, est, (double)r->P * est * 4.0);
+    return 0;
+}
+
+// [lo, hi]: the j with |j P - p Q| < U
+static void resample_support(const ResampleShape& r, int p, long long* lo, long long* hi) {
+    const long long pq = (long long)p * r.Q;
+    long long a = (long long)std::floor(((double)pq - r.U) / (double)r.P) + 1;
+    while ((double)(a * r.P - pq) <= -r.U) ++a;
+    while ((double)((a - 1) * r.P - pq) > -r.U) --a;
+    long long b = (long long)std::ceil(((double)pq + r.U) / (double)r.P) - 1;
+    while ((double)(b * r.P - pq) >= r.U) --b;
+    while ((double)((b + 1) * r.P - pq) < r.U) ++b;
+    *lo = a;
+    *hi = b;
+}
+
+static int resample_taps(const ResampleShape& r) {
+    long long n = 1;
+    for (int p = 0; p < r.P; ++p) {
+        long long lo, hi;
+        resample_support(r, p, &lo, &hi);
+        n = std::max(n, hi - lo + 1);
+    }
+    return (int)n;
+}
+
+static int resample_size(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, ResampleShape* r) {
+    if (int e = resample_shape(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint, r)) return e;
+    r->n_taps = resample_taps(*r);
+    const long long bytes = (long long)r->P * r->n_taps * 4;
+    if (r->n_taps > 128 || bytes > 1048576)
+        return fail(KPR_E_UNSUPPORTED, "resample %d -> %d%s: a table of %d phases x %d taps = %lld bytes; supported are at most 128 taps "
+                    "and 1 MiB (1048576 bytes)", orig_freq, new_freq, adjoint ? " (adjoint)" : "", r->P, r->n_taps, bytes);
+    return 0;
+}
+
+// the tile of the dispatch: `pt` phases x `nb` blocks per workgroup, work items of 8 blocks `ng` apart (kpr_resample_kernels.h).
+// The staged span of a tile is at most (nb - 1) Q + (first[p0 + pt - 1] - first[p0]) + n_taps words per channel; the plan holds
+// for both channel counts of the kernel, so kpr_resample_plan needs no layout.
+struct ResamplePlan {
+    int pt, n_pt, ng, nb, span, threads;
+};
+
+static ResamplePlan resample_plan(int P, int Q, int n_taps) {
+    auto span_of = [&](int pt, int nb) -> long long {
+        return (long long)(nb - 1) * Q + ((long long)(pt - 1) * Q) / P + 2 + n_taps;
+    };
+    // lanes at work in the rounds of `threads` work items
+    auto best_threads = [](long long items, int* threads) -> double {
+        double best = -1.0;
+        for (int t = 128; t <= kRsMaxThreads; t += 64) {
+            const double eff = (double)items / (double)((items + t - 1) / t * t);
+            if (eff > best + 1e-9) { best = eff; *threads = t; }
+        }
+        return best;
+    };
+    ResamplePlan pl;
+    pl.n_pt = (P + 1023) / 1024;
+    pl.pt = (P + pl.n_pt - 1) / pl.n_pt;
+    pl.ng = 0;
+    double best = -1.0;
+    for (int ng = 1; ng <= 1024; ++ng) {
+        const long long items = (long long)pl.pt * ng, outputs = items * kRsBlocks;
+        if (span_of(pl.pt, kRsBlocks * ng) > kRsLdsWords || (ng > 1 && outputs > 16384)) break;
+        int threads = 0;
+        double score = best_threads(items, &threads);
+        if (outputs < 2048) score *= (double)outputs / 2048.0;        // a small tile only when nothing larger fits
+        if (score > best + 1e-9) { best = score; pl.ng = ng; pl.threads = threads; }
+    }
+    if (pl.ng) {
+        pl.nb = kRsBlocks * pl.ng;
+    } else {                                     // a long step: fewer than eight blocks, then fewer phases
+        pl.ng = 1;
+        pl.nb = kRsBlocks - 1;
+        while (pl.nb > 1 && span_of(pl.pt, pl.nb) > kRsLdsWords) --pl.nb;
+        while (pl.pt > 1 && span_of(pl.pt, pl.nb) > kRsLdsWords) pl.pt = (pl.pt + 1) / 2;
+        pl.n_pt = (P + pl.pt - 1) / pl.pt;
+        best_threads(pl.pt, &pl.threads);
+    }
+    pl.span = (int)span_of(pl.pt, pl.nb);
+    return pl;
+}
+
+static int resample_dims(int n_phases, int n_taps, int step) {
+    if (n_phases < 1 || n_taps < 1 || step < 1) return fail(KPR_E_BADARG, "bad n_phases/n_taps/step (%d, %d, %d)", n_phases, n_taps, step);
+    if (n_taps > 128 || (long long)n_phases * n_taps * 4 > 1048576)
+        return fail(KPR_E_UNSUPPORTED, "a resample table of %d phases x %d taps = %lld bytes; supported are at most 128 taps and 1 MiB",
+                    n_phases, n_taps, (long long)n_phases * n_taps * 4);
+    if (step > 16 * 1048576) return fail(KPR_E_UNSUPPORTED, "a resample step of %d inputs per block is not supported", step);
+    return 0;
+}
+
+static int run_resample(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table, const int32_t* first,
+                        int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (batch < 0 || channels <= 0 || in_len < 0 || out_len < 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/in_len/out_len/layout");
+    if (int e = resample_dims(n_phases, n_taps, step)) return e;
+    // one signal is addressed with 32-bit element offsets (as kpr_num_frames)
+    const bool cl = layout == KPR_CHANNELS_LAST;
+    const long long reach = cl ? channels : 1;
+    if (in_len * reach >= (1LL << 30) || out_len * reach >= (1LL << 30))
+        return fail(KPR_E_UNSUPPORTED, "resample: %lld -> %lld samples x %d channels: 2^30 elements or more per signal are not supported",
+                    (long long)in_len, (long long)out_len, channels);
+    if (batch == 0 || out_len == 0) return 0;
+    if ((!x && in_len > 0) || !out || !table || !first) return fail(KPR_E_BADARG, "x / out / table_dev / first_dev must not be NULL");
+    if ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)table) | ((uintptr_t)first)) & 3)
+        return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out;
+        const uintptr_t nx = (uintptr_t)batch * channels * in_len * 4, no = (uintptr_t)batch * channels * out_len * 4;
+        if (x && xa < oa + no && oa < xa + nx) return fail(KPR_E_BADARG, "x and out overlap");
+    }
+    const ResamplePlan pl = resample_plan(n_phases, step, n_taps);
+    const long long n_blocks = (out_len + n_phases - 1) / n_phases;
+    if (n_blocks * step >= (1LL << 31) - (1LL << 26))
+        return fail(KPR_E_UNSUPPORTED, "resample: %lld outputs at %d inputs per %d outputs reach past 2^31 input samples", (long long)out_len,
+                    step, n_phases);
+    const int nch = cl && channels % 2 == 0 ? 2 : 1;
+    ResampleArgs a;
+    a.x = x; a.out = out; a.tab = table; a.first = first;
+    a.P = n_phases; a.Q = step; a.n_taps = n_taps;
+    a.in_len = (int)in_len; a.out_len = (int)out_len;
+    a.estride = cl ? channels : 1;
+    a.groups = channels / nch;
+    a.in_item = (long long)channels * in_len; a.out_item = (long long)channels * out_len;
+    a.in_group = cl ? nch : in_len; a.out_group = cl ? nch : out_len;
+    a.pt = pl.pt; a.n_pt = pl.n_pt; a.ng = pl.ng; a.nb = pl.nb;
+    a.n_blocks = (int)n_blocks;
+    const long long tiles = (long long)pl.n_pt * ((n_blocks + pl.nb - 1) / pl.nb);
+    a.tiles_per_signal = (int)tiles;
+    a.lds_stride = pl.span;
+    const long long grid = tiles * batch * a.groups;
+    if (tiles > 0x7fffffffLL || grid > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "resample: too many tiles (%lld)", grid);
+    const size_t lds = (size_t)nch * pl.span * sizeof(float);
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_resample<%d>: grid %lld, lds %zu B, %d phases x %d taps, step %d; tile %d phases x %d blocks "
+                "(%d outputs), %d block groups, %d lanes\n", nch, grid, lds, n_phases, n_taps, step, pl.pt, pl.nb, pl.nb * n_phases, pl.ng, pl.threads);
+    if (nch == 2) hipLaunchKernelGGL(k_resample<2>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_resample<1>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
+    return launch_check("k_resample", nch);
+}
+
+static int frame_args(int64_t batch, int channels, int64_t time, int layout, int frame_length,
+                      int hop_length, int pad_end, float pad_value, FrameArgs* a) {
+    if (batch < 0 || channels <= 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/layout (%lld, %d, %d)", (long long)batch, channels, layout);
+    const int64_t f = kpr_frame_count(time, frame_length, hop_length, pad_end);
+    if (f < 0) return KPR_E_BADARG;
+    if (f > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many frames per signal");
+    a->n_sig = batch * channels; a->T = time; a->C = channels; a->F = (int)f; a->L = frame_length;
+    a->hop = hop_length; a->cl = layout == KPR_CHANNELS_LAST && channels > 1; a->pad_value = pad_value;
+    return 0;
+}
+
+// Delta and its backward pass: the checks, the rows x columns view of the tensor and the filter's half width and scale
+struct DeltaArgs { long long total, outer, inner; int n; float scale; };
+static int delta_args(int64_t batch, int channels, int64_t frames, int n_freq, int layout, int win_length, int pad_mode, DeltaArgs* a) {
+    if (batch < 0 || channels <= 0 || frames < 0 || n_freq <= 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/frames/n_freq/layout");
+    if (win_length < 3 || (win_length & 1) == 0)
+        return fail(KPR_E_BADARG, "win_length must be odd and >= 3, got %d", win_length);
+    if (pad_mode < 0 || pad_mode > 2) return fail(KPR_E_BADARG, "bad pad mode %d", pad_mode);
+    a->total = (long long)batch * channels * frames * n_freq;
+    a->n = (win_length - 1) / 2;
+    double denom = 0;
+    for (int i = 1; i <= a->n; ++i) denom += 2.0 * i * i;
+    a->scale = (float)(1.0 / denom);
+    a->outer = layout == KPR_CHANNELS_LAST ? batch : batch * channels;
+    a->inner = layout == KPR_CHANNELS_LAST ? (long long)n_freq * channels : n_freq;
+    return 0;
+}
+
+static int aug_geom(int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq, AugGeom* a) {
+    if (n_items < 0 || n_time <= 0 || n_freq <= 0) return fail(KPR_E_BADARG, "bad n_items/n_time/n_freq");
+    if (n_time_masks < 0 || n_freq_masks < 0 || n_time_masks > kAugMaxMasks || n_freq_masks > kAugMaxMasks)
+        return fail(KPR_E_BADARG, "mask counts (%d, %d) outside [0, %d] per axis", n_time_masks, n_freq_masks, kAugMaxMasks);
+    if ((long long)n_time * n_freq > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "n_time * n_freq = %lld elements per item: 2^31 or more is not supported",
+                    (long long)n_time * n_freq);
+    *a = AugGeom{(int)n_items, n_time_masks, n_freq_masks, n_time, n_freq, 0, 0};
+    return 0;
+}
+
+}  // namespace kpr

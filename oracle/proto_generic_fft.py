@@ -6,7 +6,7 @@ import numpy as np
 
 
 def gen_plan(n):
-    """kapre_hip.hip: gen_plan -- 4s first, then a 2, then the odd primes up to 64; None when a larger prime remains."""
+    """kpr_host_fft.h: gen_plan -- 4s first, then a 2, then the odd primes up to 64; None when a larger prime remains."""
     radix, m = [], n
     while m % 4 == 0:
         radix.append(4)

@@ -11,7 +11,7 @@ N = P * R2 * R3 complex points, L = R2 * R3 lanes per frame, P points per lane.
 """
 import numpy as np
 
-# n_fft -> (P, R2, R3): the plans of mixed_radix_plan() in kapre_hip.hip
+# n_fft -> (P, R2, R3): the plans of mixed_radix_plan() in kpr_host_fft.h
 PLANS = {160: (20, 4, 1), 200: (20, 5, 1), 320: (20, 4, 2), 400: (20, 10, 1), 640: (20, 4, 4),
          800: (20, 20, 1), 1000: (20, 5, 5)}
 

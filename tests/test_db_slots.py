@@ -1,4 +1,4 @@
-"""-m gpu: statistics slots of the fused decibel kernels (DbDev::slot_mask; kapre_hip.hip: db_slots).  With few batch items
+"""-m gpu: statistics slots of the fused decibel kernels (DbDev::slot_mask; kpr_host_mel.h: db_slots).  With few batch items
 every workgroup's closing max / min atomics used to land on the same few words (8 six-channel items: 1024 waves on 16
 addresses, +13 us on a 12 us kernel); small batches now spread them over up to 32 slots per item, which k_db_clamp
 reduces.  The result must not change: one slot (`db_slots` 1, the layout of rounds 1-2) and the automatic number give the

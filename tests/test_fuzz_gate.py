@@ -3,7 +3,7 @@ so that EVERY dispatch threshold of the library is crossed in both directions an
 kernels is reached -- the class of bug that shipped twice in round 4 (a new large-launch instance x an untested layout pair x
 a launch size past a dispatch threshold) was only found by tools/fuzz_parity.py, which no gate runs.
 
-* thresholds (kapre_hip.hip; 256 CUs): k_stft3 from 8 frame groups per CU and its CL instances; k_istft_pw from 3/4 item per
+* thresholds (kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h; 256 CUs): k_stft3 from 8 frame groups per CU and its CL instances; k_istft_pw from 3/4 item per
   CU (all nine <n_fft, hop> instances + the interleaved ones), more items than workgroups, > 256 items, several segments per
   signal, k_istft_fused up to 3072 frames, the ring kernel in between; k_mel_pw with 4 / 8 / 16 waves per workgroup (4 and 16
   tickets per CU), its PAIR form from 24 pair tickets per CU; k_mel_mr; k_mel_ts / k_mel_ws for banks without a band plan.
@@ -35,7 +35,7 @@ def _nframes(t, n_fft, win, hop, pad_b, pad_e):
 
 
 def _stft_kernel(n_fft, ch, fi, fo, total):
-    """kapre_hip.hip launch_stft_inst on 256 CUs, complex / magnitude output"""
+    """kpr_host_stft.h launch_stft_inst on 256 CUs, complex / magnitude output"""
     g = 64 // (n_fft // 32)
     cfast = ch > 1 and (fi == CL or fo == CL)
     cl_out = fo == CL and ch > 1
@@ -46,7 +46,7 @@ def _stft_kernel(n_fft, ch, fi, fo, total):
 
 
 def _mel_kernel(n_fft, ch, fi, total):
-    """kapre_hip.hip kpr_mel_f32, banks with a band plan, on 256 CUs"""
+    """kpr_host_mel.h mel_route, banks with a band plan, on 256 CUs"""
     g = 64 // (n_fft // 32)
     tickets = -(-total // g)
     if fi == CL and ch > 1 and ch % 2 == 0 and n_fft in (1024, 2048) and (n_fft == 2048 or ch >= 4) and tickets >= 24 * 256:

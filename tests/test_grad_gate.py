@@ -1,5 +1,5 @@
 """-m gpu: the gradient gate.  tests/test_autograd.py checks every backward pass at batch 2 - 4 with a few dozen frames, where
-the host dispatch (kapre_amd/csrc/kapre_hip.hip) only ever picks its smallest route.  Here the same float64 checker
+the host dispatch (kapre_amd/csrc/kpr_host_*.h) only ever picks its smallest route.  Here the same float64 checker
 (tests/grad_model.py) meets the backward passes at the launch sizes where the choice of kernel changes:
 
   A  STFT^T = an inverse-STFT launch (istft_route): barrier kernel up to 3072 frames, ring kernel above, k_istft_pw / _il from

@@ -297,8 +297,11 @@ def test_options_api():
     assert L.kpr_set_option(b"istft_path", 4) == 0 and L.kpr_set_option(b"istft_path", 0) == 0
     assert L.kpr_set_option(b"istft_path", 5) == -1 and b"outside" in L.kpr_last_error()
     assert L.kpr_set_option(b"no_such_switch", 1) == -1 and b"unknown option" in L.kpr_last_error()
-    src = open(os.path.join(REPO, "kapre_amd", "csrc", "kapre_hip.hip")).read()
-    assert "getenv" not in src
+    csrc = os.path.join(REPO, "kapre_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert "kapre_hip.hip" in sources and "kpr_host.h" in sources
+    for f in sources:
+        assert "getenv" not in open(os.path.join(csrc, f)).read(), f
 
 
 def test_fails_loudly_without_a_gpu():

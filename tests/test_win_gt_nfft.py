@@ -3,7 +3,7 @@
 kapre/time_frequency.py:174-182 hands frame_length = win_length and fft_length = n_fft straight to tf.signal.stft: frames of
 win_length samples are cut (the frame COUNT follows win_length) and windowed, then rfft(fft_length) keeps their first n_fft
 samples.  Through round 5 float32 sent these calls to the DFT-as-GEMM fallback (untested on the GPU) and float64 refused them;
-since round 6 every FFT family takes them (kapre_hip.hip: forward_geom).  Oracle: oracle/kapre_oracle.py tf_stft (crop), numpy's
+since round 6 every FFT family takes them (kpr_host.h: forward_geom).  Oracle: oracle/kapre_oracle.py tf_stft (crop), numpy's
 rfft(n=...) for float64."""
 import numpy as np
 import pytest

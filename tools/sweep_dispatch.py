@@ -2,7 +2,7 @@
 """One pass over every dispatch decision the library makes by itself: for a grid of shapes and launch sizes, the kernel
 time of the automatic choice against every forced alternative (mel_variant, stft_variant, istft_path, db_slots), and a
 flag on each row where the automatic choice is more than 3 % behind the best one.  Meant as the FIRST GPU call of a round:
-the thresholds in kapre_hip.hip were set on a handful of shapes each, and in round 3 three of them turned out wrong
+the thresholds in the route functions (kpr_host_*.h) were set on a handful of shapes each, and in round 3 three of them turned out wrong
 elsewhere.  ~2-3 minutes on the GPU box.
     python tools/sweep_dispatch.py [mel] [logf] [stft] [istft] [db] [mr]          default: all but mr
 mr (round 6, before the prune of the mixed-radix ISTFT ring instances): every mixed-radix / two-pass size, the inverse transform
