@@ -4,8 +4,9 @@
 //   kpr_fft.h, kpr_fft_mr.h   FFT building blocks: packed-f32 complex arithmetic, in-register DFTs,
 //                             LDS exchange policies, the power-of-two Stockham passes, the mixed-radix
 //                             (2^a 5^b) passes, real-FFT pairing
-//   kpr_common.h              errors, frame geometry, sample fetch
-//   kpr_mel_kernels.h         k_mel_ws / k_mel_fused: waveform -> [frame + window + rFFT -> |X| -> (K x M)
+//   kpr_common.h              errors, frame geometry, sample fetch, and the wave-protocol pieces every kernel family shares:
+//                             ticket draw, bounded waits, window pairs into LDS
+//   kpr_mel_kernels.h         k_mel_ws: waveform -> [frame + window + rFFT -> |X| -> (K x M)
 //                             filterbank on fp32 MFMA -> optional 10 log10], the whole Sequential of
 //                             composed.py:138-261 in one launch; FROM_MAG: stand-alone ApplyFilterbank
 //   kpr_mel_ts_kernels.h      k_mel_ts: the same Sequential, tile-synchronous (16 equal waves, two barriers per round) --
@@ -113,9 +114,7 @@ __global__ void k_spin_selftest() {
     __shared__ int flag;
     if (threadIdx.x == 0) flag = 0;
     __syncthreads();
-    int spin = 0;
-    for (; spin < 64 && __hip_atomic_load(&flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 1; ++spin) __builtin_amdgcn_s_sleep(2);
-    if (__builtin_expect(spin >= 64, 0)) status_raise(kStSelfTest);
+    spin_until_ge<2, 64>(&flag, 1, kStSelfTest);
 }
 int kpr_debug_spin_timeout(kpr_stream_t stream) {
     if (int e = status_word_ready()) return e;

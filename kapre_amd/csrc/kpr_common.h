@@ -50,6 +50,51 @@ __device__ __forceinline__ void status_raise(unsigned bits) {             // (co
 }
 
 // ------------------------------------------------------------------------------------------
+// wave protocol pieces shared by the ring / per-wave kernels
+// ------------------------------------------------------------------------------------------
+// the next value of an LDS ticket counter, wave-uniform: lane 0 draws (relaxed, workgroup scope), every lane gets the value
+KPR_DEV int wave_ticket(int* counter, int lane) {
+    int v = 0;
+    if (lane == 0) v = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// polls of an LDS counter before a wave gives up waiting (>= 0.2 s)
+constexpr int kSpinLimit = 1 << 22;
+// bounded wait until *p >= need (acquire, workgroup scope), s_sleep NAP between polls.  A wait that runs out of polls -- a
+// protocol error -- ends as a wrong result AND status_bit in the device status word, never as a hung GPU.
+template <int NAP, int LIMIT = kSpinLimit>
+KPR_DEV void spin_until_ge(const int* p, int need, unsigned status_bit) {
+    int spin = 0;
+    for (; spin < LIMIT && __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need; ++spin)
+        __builtin_amdgcn_s_sleep(NAP);
+    if (__builtin_expect(spin >= LIMIT, 0)) status_raise(status_bit);
+}
+// the same for a wait on several lanes' conditions at once: ok() is this lane's predicate, the wave leaves when all hold
+template <int NAP, class OK>
+KPR_DEV void spin_until_all(OK&& ok, unsigned status_bit) {
+    int spin = 0;
+    for (; spin < kSpinLimit; ++spin) {
+        const bool k = ok();
+        if (__all(k)) break;
+        __builtin_amdgcn_s_sleep(NAP);
+    }
+    if (__builtin_expect(spin >= kSpinLimit, 0)) status_raise(status_bit);
+}
+
+// synthesis / analysis window as pairs in LDS: winl[i] = (scale_even w[2i], scale_odd w[2i+1]), i < count, zero beyond the
+// window's `win` samples (loads from a clamped index: no branch around them)
+KPR_DEV void stage_window_pairs(f2* winl, const float* window, int win, int count, int tid, int threads,
+                                float scale_even, float scale_odd) {
+    for (int i = tid; i < count; i += threads) {
+        const int n = 2 * i;
+        const float a = window[min(n, win - 1)], b = window[min(n + 1, win - 1)];
+        winl[i] = f2{(n < win) ? scale_even * a : 0.0f, (n + 1 < win) ? scale_odd * b : 0.0f};
+    }
+}
+// (Where a kernel still fills its window pairs by hand, sharing this loop changed its code object: see the comment there.)
+
+// ------------------------------------------------------------------------------------------
 // geometry shared by host and device
 // ------------------------------------------------------------------------------------------
 struct Geom {

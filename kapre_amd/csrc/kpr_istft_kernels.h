@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256, 2) void k_irfft_bs(const float2* __restrict__ 
     f2* btl = cwl + M;
     f2* tkl = btl + M;
     const float sc = 2.0f / (float)ncr;
-    for (int i = tid; i < M; i += 256) {
+    for (int i = tid; i < M; i += 256) {      // (window pairs by hand: the extra n < n_fft test, and the table copies share this loop)
         const int n = 2 * i;
         const float a = synth[min(n, g.win - 1)], b = synth[min(n + 1, g.win - 1)];
         winl[i] = f2{(n < g.win && n < g.n_fft) ? sc * a : 0.0f, (n + 1 < g.win && n + 1 < g.n_fft) ? sc * b : 0.0f};
@@ -103,11 +103,7 @@ __global__ __launch_bounds__(256, 2) void k_irfft_mr(const float2* __restrict__ 
     f2* winl = rows + 4 * G * RSF;                                // synthesis window / (2N), pairs
     f2* tab = winl + N;
     const float sc = 0.5f / (float)N;                             // 1/2 of the pairing, 1/N of the inverse DFT
-    for (int i = tid; i < N; i += 256) {
-        const int n = 2 * i;
-        const float a = synth[min(n, g.win - 1)], b = synth[min(n + 1, g.win - 1)];
-        winl[i] = f2{(n < g.win) ? sc * a : 0.0f, (n + 1 < g.win) ? sc * b : 0.0f};
-    }
+    stage_window_pairs(winl, synth, g.win, N, tid, 256, sc, sc);
     for (int i = tid; i < 2 * N; i += 256) { const float2 t = twtab[i]; tab[i] = f2{t.x, t.y}; }
     __syncthreads();
     const int ostride = spec_stride(g);
@@ -482,9 +478,8 @@ struct IstftWsPlan {
 };
 constexpr int kIwProd = 7;
 constexpr int kIwThreads = 512;
-// every wait is bounded (a few hundred ms): a protocol error must end as a wrong result that the
-// parity tests catch, never as a hung device
-constexpr int kIwSpinLimit = 1 << 22;
+// (every wait is bounded -- spin_until_ge / spin_until_all, kpr_common.h: a protocol error must end as a wrong result that
+// the parity tests catch and a bit in the device status word, never as a hung device)
 constexpr int kIwReads = 8;       // row reads (ds_read_b128) per consumer lane and pass
 
 // One consumer pass of k_istft_ws = the 64 * IT four-sample groups of the hop blocks [cq, qe),
@@ -570,14 +565,9 @@ KPR_DEV void iw_consume(IwPass<RJ, VEC>& s, const IwCtx& c, float* __restrict__ 
     if (!__all(s.flag >= s.want)) {
         // the producers are behind: wait for the frames, then read the rows again
         const int* flag = &c.done[(s.want - 1) & c.rmask];
-        int spin = 0;
-        for (; spin < kIwSpinLimit; ++spin) {
-            const bool ok = s.flag == 0x7fffffff ||
-                __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= s.want;
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(4);
-        }
-        if (__builtin_expect(spin >= kIwSpinLimit, 0)) status_raise(kStIstftWsCons);
+        spin_until_all<4>([&] {
+            return s.flag == 0x7fffffff || __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= s.want;
+        }, kStIstftWsCons);
         iw_issue<RJ, VEC>(s, c, s.cq, s.qe, lane, qk, o4k, false);
     }
     const int n4 = (min(s.qe * c.hop, c.t_out) - s.cq * c.hop) / VEC;
@@ -610,6 +600,24 @@ KPR_DEV void iw_consume(IwPass<RJ, VEC>& s, const IwCtx& c, float* __restrict__ 
         __hip_atomic_store(emitted, s.qe - c.q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// one segment of the ring kernels: hop blocks q0 .. q1-1 of signal `sig`, made from frames fa .. f_last.
+// (A macro shared by k_istft_ws and k_istft_ws_mr, not a function returning a struct: as a function -- plan by reference, by value
+//  or field by field -- the code objects of the ring kernels change.)
+#define IW_ITEM_PARAMS()                                                                          \
+        const int sig = item / pl.segs, seg = item - sig * pl.segs;                              \
+        const int q0 = seg * pl.QS, q1 = min(pl.Q, q0 + pl.QS);                                  \
+        const int fa = max(0, q0 - (pl.R - 1)), f_last = min(pl.F - 1, q1 - 1);                  \
+        const int nframes = f_last - fa + 1 /* >= 1 */
+// flags and counters of a segment (the first kIwProd tickets are taken: ticket w = wave w); all threads of the workgroup.
+// (NR by value and the counter's address before its value: with the plan by reference, or sync[tid] = ... in one statement, the
+//  code objects change)
+KPR_DEV void iw_segment_reset(int NR, int* done, int* sync, int tid) {
+    for (int i = tid; i < NR; i += kIwThreads) done[i] = 0;
+    int* const p = sync + tid;
+    if (tid < 2) *p = tid == 0 ? kIwProd : 0;
+    __syncthreads();
+}
+
 template <int NC, int RJ>
 __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restrict__ spec,
                                                          IstftWsPlan pl,
@@ -625,6 +633,7 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
     const int K = NC + 1;
     const int rmask = pl.NR - 1;
     // development aid (tools/stamps_istft.py): cycle stamps of workgroup 0, 32 per wave
+    // (stamps stay macros per kernel: through a shared recorder object the code objects change, product and stamp variants alike)
     int dbi = 0;
     const bool stamp_me = dbg && blockIdx.x == 0;
 #define IW_STAMP() do { if (stamp_me && lane == 0 && dbi < 32) dbg[wave * 32 + dbi++] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -639,18 +648,6 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
     int* sync = done + pl.NR;                                  // [0] tickets, [1] hop blocks emitted
     // (contiguous spectrogram rows only: the 32 loads of a frame are base + immediate offset)
 
-    // one segment: hop blocks q0 .. q1-1 of signal `sig`, made from frames fa .. f_last
-#define IW_ITEM_PARAMS()                                                                          \
-        const int sig = item / pl.segs, seg = item - sig * pl.segs;                              \
-        const int q0 = seg * pl.QS, q1 = min(pl.Q, q0 + pl.QS);                                  \
-        const int fa = max(0, q0 - (pl.R - 1)), f_last = min(pl.F - 1, q1 - 1);                  \
-        const int nframes = f_last - fa + 1 /* >= 1 */
-    // flags and counters of the segment (the first kIwProd tickets are taken: ticket w = wave w)
-#define IW_ITEM_SYNC()                                                                            \
-        for (int i = tid; i < pl.NR; i += kIwThreads) done[i] = 0;                               \
-        if (tid < 2) sync[tid] = tid == 0 ? kIwProd : 0;                                         \
-        __syncthreads()
-
     // The two roles run the segment loop separately (the same two workgroup barriers per segment
     // in each): the twiddles / window of the producers and the two passes of the consumer are then
     // never live together and the allocator does not spill either.
@@ -658,12 +655,6 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
         FftTw<NC> tw;
         WinRegs<NC> wr;
         float2 xa[kPts], xb[kPts];
-#define IW_TICKET(dst_)                                                                          \
-    do {                                                                                         \
-        int v_ = 0;                                                                              \
-        if (lane == 0) v_ = __hip_atomic_fetch_add(&sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        dst_ = __builtin_amdgcn_readfirstlane(v_);                                               \
-    } while (0)
         // unconditional loads from a clamped frame (idle slots are zeroed when consumed)
 #define IW_LOAD(n_)                                                                              \
     do {                                                                                         \
@@ -695,12 +686,11 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
             const float2* sp0 = spec + ((long long)sig * pl.F) * K;
             int n = wave;
             if (item != (int)blockIdx.x && n < n_tickets) IW_LOAD(n);
-            IW_ITEM_SYNC();
+            iw_segment_reset(pl.NR, done, sync, tid);
             IW_FSTAMP();
 #pragma unroll 1
             while (n < n_tickets) {
-                int n2;
-                IW_TICKET(n2);
+                const int n2 = wave_ticket(&sync[0], lane);
                 const int p = G * n + grp;
                 const bool valid = p < nframes;
                 f2 z[kPts];
@@ -717,13 +707,7 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
                 // the ring slots of this ticket are free once the consumer has emitted every block
                 // that reads the frames NR positions back: blocks < f_hi - NR + R
                 const int need = fa + min(G * n + G - 1, nframes - 1) - pl.NR + pl.R - q0;
-                if (need > 0) {
-                    int spin = 0;
-                    for (; spin < kIwSpinLimit &&
-                         __hip_atomic_load(&sync[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need; ++spin)
-                        __builtin_amdgcn_s_sleep(2);
-                    if (__builtin_expect(spin >= kIwSpinLimit, 0)) status_raise(kStIstftWsProd);
-                }
+                if (need > 0) spin_until_ge<2>(&sync[1], need, kStIstftWsProd);
                 float* row = valid ? smem + (p & rmask) * pl.RS
                                    : spare + (wave * (G - 1) + (grp > 0 ? grp - 1 : 0)) * pl.RS;
                 IW_FSTAMP();
@@ -746,12 +730,12 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
                 IW_STAMP();
                 n = n2;
             }
-#undef IW_TICKET
 #undef IW_LOAD
             __syncthreads();       // ring, flags and counters are reused by the next segment
         }
     } else {
         // consumer: group lane + 64 u of a pass = 4-sample group o4k[u] of hop block qk[u] of the batch
+        // (written out here and in k_istft_ws_mr: as one shared function the code objects of both kernels change)
         int qk[IwPass<RJ>::IT], o4k[IwPass<RJ>::IT];
         {
             const int nq4 = pl.hop >> 2;
@@ -766,7 +750,7 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
             IW_ITEM_PARAMS();
             (void)nframes;
             IW_FSTAMP();
-            IW_ITEM_SYNC();
+            iw_segment_reset(pl.NR, done, sync, tid);
             IW_FSTAMP();
             // ================================ consumer =======================================
             float* const osig = out + (long long)sig * pl.t_out;
@@ -793,8 +777,6 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws(const float2* __restric
             __syncthreads();
         }
     }
-#undef IW_ITEM_PARAMS
-#undef IW_ITEM_SYNC
 #undef IW_STAMP
 #undef IW_FSTAMP
 }
@@ -822,34 +804,19 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
     f2* tab = winl + N;                                        // exp(-2 pi i j / n_fft), j < n_fft
     {
         const float sc = 0.5f / (float)N;                      // 1/2 of the pairing, 1/N of the inverse DFT
-        for (int i = tid; i < N; i += kIwThreads) {
+        for (int i = tid; i < N; i += kIwThreads) {       // (by hand: through stage_window_pairs the code objects change)
             const int n = 2 * i;
             const float a = synth[min(n, pl.win - 1)], b = synth[min(n + 1, pl.win - 1)];
             winl[i] = f2{(n < pl.win) ? sc * a : 0.0f, (n + 1 < pl.win) ? sc * b : 0.0f};
         }
         for (int i = tid; i < 2 * N; i += kIwThreads) { const float2 t = twtab[i]; tab[i] = f2{t.x, t.y}; }
     }
-#define IW_ITEM_PARAMS()                                                                          \
-        const int sig = item / pl.segs, seg = item - sig * pl.segs;                              \
-        const int q0 = seg * pl.QS, q1 = min(pl.Q, q0 + pl.QS);                                  \
-        const int fa = max(0, q0 - (pl.R - 1)), f_last = min(pl.F - 1, q1 - 1);                  \
-        const int nframes = f_last - fa + 1 /* >= 1 */
-#define IW_ITEM_SYNC()                                                                            \
-        for (int i = tid; i < pl.NR; i += kIwThreads) done[i] = 0;                               \
-        if (tid < 2) sync[tid] = tid == 0 ? kIwProd : 0;                                         \
-        __syncthreads()
 
     if (wave < kIwProd) {
         const bool active = lane < G * L;
         const int grp = active ? lane / L : 0, l = active ? lane - grp * L : 0;
         const int li = min(l, LIN - 1);
         float2 xa[PIN], xb[PIN];
-#define IW_TICKET(dst_)                                                                          \
-    do {                                                                                         \
-        int v_ = 0;                                                                              \
-        if (lane == 0) v_ = __hip_atomic_fetch_add(&sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        dst_ = __builtin_amdgcn_readfirstlane(v_);                                               \
-    } while (0)
 #define IW_LOAD(n_)                                                                              \
     do {                                                                                         \
         const int p_ = G * (n_) + grp;                                                           \
@@ -874,11 +841,10 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
             const float2* sp0 = spec + ((long long)sig * pl.F) * K;
             int n = wave;
             if (item != (int)blockIdx.x && n < n_tickets) IW_LOAD(n);
-            IW_ITEM_SYNC();                                    // (first segment: also publishes winl / tab)
+            iw_segment_reset(pl.NR, done, sync, tid);          // (first segment: also publishes winl / tab)
 #pragma unroll 1
             while (n < n_tickets) {
-                int n2;
-                IW_TICKET(n2);
+                const int n2 = wave_ticket(&sync[0], lane);
                 const int p = G * n + grp;
                 const bool valid = active && p < nframes;
                 f2 z[P];
@@ -899,13 +865,7 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
                     if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);
                 }
                 const int need = fa + min(G * n + G - 1, nframes - 1) - pl.NR + pl.R - q0;
-                if (need > 0) {
-                    int spin = 0;
-                    for (; spin < kIwSpinLimit &&
-                         __hip_atomic_load(&sync[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need; ++spin)
-                        __builtin_amdgcn_s_sleep(2);
-                    if (__builtin_expect(spin >= kIwSpinLimit, 0)) status_raise(kStIstftWsProd);
-                }
+                if (need > 0) spin_until_ge<2>(&sync[1], need, kStIstftWsProd);
                 float* row = smem + ((valid ? p : 0) & rmask) * pl.RS;
                 F::run(z, l, valid, reinterpret_cast<f2*>(row), tab);           // Y = FFT_N(conj 2Z)
                 // next ticket's rows: requested AFTER the FFT (round 4).  In flight during the FFT -- 4 PIN registers on top of
@@ -931,7 +891,6 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
                     __hip_atomic_store(&done[p & rmask], p + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 n = n2;
             }
-#undef IW_TICKET
 #undef IW_LOAD
             __syncthreads();
         }
@@ -949,7 +908,7 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
         for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
             IW_ITEM_PARAMS();
             (void)nframes;
-            IW_ITEM_SYNC();
+            iw_segment_reset(pl.NR, done, sync, tid);
             float* const osig = out + (long long)sig * pl.t_out;
             __builtin_amdgcn_s_setprio(3);
             IwCtx c;
@@ -972,9 +931,8 @@ __global__ __launch_bounds__(kIwThreads) void k_istft_ws_mr(const float2* __rest
             __syncthreads();
         }
     }
-#undef IW_ITEM_PARAMS
-#undef IW_ITEM_SYNC
 }
+#undef IW_ITEM_PARAMS
 
 // overlap-add as a gather: out[t] = sum_{f : f*hop <= t < f*hop + win} frames[f][t - f*hop]
 template <class T>

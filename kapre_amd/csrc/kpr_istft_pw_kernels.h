@@ -41,7 +41,6 @@ struct IstftPwPlan {
     int C, in_cl, out_cl;
 };
 constexpr int kIpwTwRegs = 10;           // FftTw<NC>::kNumTw <= 10
-constexpr int kIpwSpinLimit = 1 << 22;   // every wait is bounded: a protocol error must end as a wrong result + KPR_E_DEVICE, not a hang
 
 __host__ __device__ constexpr int ipw_row_words(int NC) { return NC >= 512 ? ((SwzSkew::row_words(NC) + 3) & ~3) : NC; }
 __host__ __device__ inline size_t ipw_lds_bytes(int NC, int W) {           // without the stashes
@@ -173,11 +172,7 @@ __global__ __launch_bounds__(W * 64, 4) void k_istft_pw(const float2* __restrict
     {
         // irfft's 1 / n_fft and the conjugation after the forward FFT (IFFT(z) = conj(FFT(conj z))) folded into the window
         const float sc = 1.0f / (float)(2 * NC);
-        for (int i = tid; i < NC; i += W * 64) {
-            const int n = 2 * i;
-            const float a = synth[min(n, pl.win - 1)], b = synth[min(n + 1, pl.win - 1)];
-            winl[i] = f2{(n < pl.win) ? sc * a : 0.0f, (n + 1 < pl.win) ? -sc * b : 0.0f};
-        }
+        stage_window_pairs(winl, synth, pl.win, NC, tid, W * 64, sc, -sc);
     }
     if (tid < NSTR) flags[tid] = 0;
     // the first rows of the first item are requested before the barrier (after the table loads: 64 registers): they travel
@@ -314,11 +309,7 @@ __global__ __launch_bounds__(W * 64, 4) void k_istft_pw(const float2* __restrict
         const int tail_kind = (r.rb == pl.F) ? FINAL : (r.rr == RUNS - 1 ? DISCARD : RMW);
         float* osig = out_sig(it, r);
         if (tail_kind == RMW) {
-            int spin = 0;
-            for (; spin < kIpwSpinLimit &&
-                 __hip_atomic_load(&flags[r.sid + CS], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < item + 1; ++spin)
-                __builtin_amdgcn_s_sleep(2);
-            if (__builtin_expect(spin >= kIpwSpinLimit, 0)) status_raise(kStIstftPw);
+            spin_until_ge<2>(&flags[r.sid + CS], item + 1, kStIstftPw);      // (bounded, kpr_common.h)
             const int tb = r.rb * pl.hop + 2 * r.fl;                      // (rb < F: all of it inside the waveform)
             float* ob = osig + (long long)tb * es_out;
             float px[TAIL], py[TAIL];

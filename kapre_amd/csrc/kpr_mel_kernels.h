@@ -13,7 +13,6 @@ namespace kpr {
 #define KPR_RING_DEPTH 3
 #endif
 constexpr int kMaxTiles = 64;   // up to 1024 filters
-constexpr int kWsSpinLimit = 1 << 22;   // polls of an LDS counter before a wave gives up waiting (>= 0.2 s)
 constexpr int kFT = 16;         // frames per workgroup == MFMA N
 
 constexpr int kMaxSegs = kMaxTiles + 4;
@@ -84,9 +83,10 @@ template <> struct WsSwzFor<1024> { typedef SwzWide type; };      // 128-bit exc
 template <int NC>
 KPR_DEV void ws_frame(const float* __restrict__ x, const Geom& g, FftTw<NC, typename WsSwzFor<NC>::type>& tw,
                       const f2* winl, float* row, float* xrow, int gf_next, int f_end, int fl, int grp, int lane, int K, int S,
-                      f2 (&nz)[kPts], unsigned& nvm, f2 (&wv)[kPts], bool more, long long* dbgw, int& dbi) {
+                      f2 (&nz)[kPts], unsigned& nvm, f2 (&wv)[kPts], long long* dbgw, int& dbi) {
     constexpr int L = NC / kPts;
     typedef typename WsSwzFor<NC>::type WsSwz;
+    // (stamps stay macros per kernel: through a shared recorder object the code objects change, product and stamp variants alike)
 #ifdef KPR_FINE_STAMPS
 #define KPR_FS() do { if (dbgw && lane == 0 && dbi < 32) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dbgw[dbi++] = (long long)__builtin_readcyclecounter(); } } while (0)
 #else
@@ -168,7 +168,6 @@ KPR_DEV void ws_frame(const float* __restrict__ x, const Geom& g, FftTw<NC, type
 #undef KPR_XSQRT
     // the NEXT frame's window values: z is dead here, and the LDS round trip then runs under the ticket /
     // publish code instead of at the head of the next frame (one exposed LDS latency less per frame)
-    (void)more;
 #pragma unroll
     for (int m = 0; m < kPts; ++m) wv[m] = winl[fl + L * m];
     KPR_FS();
@@ -186,12 +185,6 @@ KPR_DEV void ws_loader(const float* __restrict__ x, const Geom& g, int K, int S,
     static_assert(kFT % RPT == 0, "a ticket never straddles two tiles");
     const int kend = mel_row_cap(K) + 2;               // columns the consumers may read
     const int n_tickets = (n_total + RPT - 1) / RPT;
-#define WL_TICKET(dst_)                                                                          \
-    do {                                                                                         \
-        int v_ = 0;                                                                              \
-        if (lane == 0) v_ = __hip_atomic_fetch_add(&sync[4], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        dst_ = __builtin_amdgcn_readfirstlane(v_);                                               \
-    } while (0)
 #define WL_LOAD(set_, n_)                                                                        \
     do {                                                                                         \
         _Pragma("unroll") for (int r = 0; r < RPT; ++r) {                                        \
@@ -228,7 +221,7 @@ KPR_DEV void ws_loader(const float* __restrict__ x, const Geom& g, int K, int S,
     int n[NSET];
 #pragma unroll
     for (int q = 0; q < NSET; ++q) {
-        WL_TICKET(n[q]);
+        n[q] = wave_ticket(&sync[4], lane);
         if (n[q] < n_tickets) WL_LOAD(v[q], n[q]);
     }
 #pragma unroll 1
@@ -238,12 +231,11 @@ KPR_DEV void ws_loader(const float* __restrict__ x, const Geom& g, int K, int S,
         for (int q = 0; q < NSET; ++q) {
             if (done || n[q] >= n_tickets) { done = true; continue; }      // tickets only grow: the later sets are done too
             WL_STORE(v[q], n[q]);
-            WL_TICKET(n[q]);
+            n[q] = wave_ticket(&sync[4], lane);
             if (n[q] < n_tickets) WL_LOAD(v[q], n[q]);
         }
         if (done) break;
     }
-#undef WL_TICKET
 #undef WL_LOAD
 #undef WL_STORE
 }
@@ -325,12 +317,10 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
     f2* winl = reinterpret_cast<f2*>(sync + 8);                          // (0.5 w[2n], 0.5 w[2n+1])
 #define WS_SIGNAL_N(p_, n_) do { if (lane == 0) __hip_atomic_fetch_add((p_), (n_), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); } while (0)
 #define WS_SIGNAL(p_) WS_SIGNAL_N(p_, 1)
-// bounded (like kIwSpinLimit of the ISTFT ring): a protocol bug becomes a wrong result AND a bit in the device status word
-// (kpr_common.h: the next API call fails with KPR_E_DEVICE), not a hung GPU
-#define WS_SPIN_UNTIL(p_, n_, nap_) do { int spin_ = 0; for (; spin_ < kWsSpinLimit && __hip_atomic_load((p_), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < (n_); ++spin_) __builtin_amdgcn_s_sleep(nap_); if (__builtin_expect(spin_ >= kWsSpinLimit, 0)) status_raise(kStMelWs); } while (0)
+    // (every wait on these counters is bounded: spin_until_ge, kpr_common.h)
 
     int dbi = 0;
-    // development aid: dbg[12*32] selects the workgroup whose waves record cycle stamps
+    // development aid: dbg[12*32] selects the workgroup whose waves record cycle stamps (macros: see ws_frame)
     const bool stamp_me = dbg && (long long)blockIdx.x == dbg[12 * 32];
 #ifdef KPR_DEV_STAMPS    /* tools/stamps.py needs a library built with -DKPR_DEV_STAMPS (tools/build_variant.py) */
 #define KPR_STAMP() do { if (stamp_me && lane == 0 && dbi < 32) dbg[wave * 32 + dbi++] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -342,7 +332,7 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
     // frames), so the runs differ by at most one ticket; it walks the run in tiles of 16 frames, the
     // last one possibly short.  Contiguous, not grid-strided: the next tile's samples overlap the
     // current one's and sit in the same pages.
-    // (frame numbers fit in 32 bits here: the launcher falls back to k_mel_fused otherwise)
+    // (frame numbers fit in 32 bits here: mel_route, kpr_host_mel.h, sends longer inputs elsewhere)
     // run_q, run_r = (tickets / workgroups, tickets % workgroups) from the host: the first run_r workgroups take
     // run_q + 1 tickets (two 64-bit divisions per wave used to sit on the prologue's critical path)
     const int bx = (int)blockIdx.x;
@@ -380,6 +370,7 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
             // right after the barrier, and a first touch after a kernel boundary costs a translation miss and an
             // HBM round trip (~3 us) that would otherwise sit on the first frame's critical path
             warm = reinterpret_cast<const float*>(twtab)[min(c0 * 16, 4 * NC - 1)];
+            // (by hand, not stage_window_pairs / a shared helper: sharing it changes this kernel's code object)
             float wa[WPT], wb[WPT];
 #pragma unroll
             for (int u = 0; u < WPT; ++u) {
@@ -406,20 +397,14 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
     if (warm == 1.2345678e-30f) sync[7] = 1;      // keeps the warm-up load alive (a twiddle is never this value)
 
 #ifdef KPR_FINE_STAMPS   /* stamps of workgroup 0 in tile 2 only (fits the 32-slot row) */
-#define KPR_DO_FRAME(row_, gf_next_, more_) ws_frame<NC>(x, g, tw, winl, smem + (row_), smem + (((row_) + 3) & ~3), (gf_next_), f_end, fl, grp, lane, K, S, nz, nvm, wv, (more_), (stamp_me && t == 2) ? dbg + wave * 32 : nullptr, dbi)
+#define KPR_DO_FRAME(row_, gf_next_) ws_frame<NC>(x, g, tw, winl, smem + (row_), smem + (((row_) + 3) & ~3), (gf_next_), f_end, fl, grp, lane, K, S, nz, nvm, wv, (stamp_me && t == 2) ? dbg + wave * 32 : nullptr, dbi)
 #else
-#define KPR_DO_FRAME(row_, gf_next_, more_) ws_frame<NC>(x, g, tw, winl, smem + (row_), smem + (((row_) + 3) & ~3), (gf_next_), f_end, fl, grp, lane, K, S, nz, nvm, wv, (more_), nullptr, dbi)
+#define KPR_DO_FRAME(row_, gf_next_) ws_frame<NC>(x, g, tw, winl, smem + (row_), smem + (((row_) + 3) & ~3), (gf_next_), f_end, fl, grp, lane, K, S, nz, nvm, wv, nullptr, dbi)
 #endif
 
     if (wave < NPROD) {
         // ================================ producers ==========================================
         const int n_total = f_end - f_begin;
-#define WS_TICKET(dst_)                                                                          \
-    do {                                                                                         \
-        int v_ = 0;                                                                              \
-        if (lane == 0) v_ = __hip_atomic_fetch_add(&sync[4], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        dst_ = __builtin_amdgcn_readfirstlane(v_);                                               \
-    } while (0)
         if constexpr (FROM_MAG) {
             // loader producers: row n of the run -> row n & 15 of tile n >> 4 (coalesced dword loads:
             // a row of K floats starts at an arbitrary 4-byte boundary).  A ticket is RPT consecutive
@@ -466,10 +451,9 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
             const int q0 = G * n;                                     // first frame of the ticket
             const int t = q0 >> 4, j = (q0 & (kFT - 1)) + grp;
             // buffer t & 1 is free once all four consumers have read tile t - 2 (monotonic counter)
-            if (t > t_free) { WS_SPIN_UNTIL(&sync[2], 4 * (t - 1), 2); t_free = t; }
-            KPR_DO_FRAME((t & 1) * (kFT * S) + j * S, (n2 < n_tickets) ? f_begin + G * n2 : f_end, n2 < n_tickets);
-            int n3;
-            WS_TICKET(n3);
+            if (t > t_free) { spin_until_ge<2>(&sync[2], 4 * (t - 1), kStMelWs); t_free = t; }
+            KPR_DO_FRAME((t & 1) * (kFT * S) + j * S, (n2 < n_tickets) ? f_begin + G * n2 : f_end);
+            int n3 = wave_ticket(&sync[4], lane);
             if (SKEW && n3 >= 16) n3 += 4;
             WS_SIGNAL_N(&sync[t & 1], min(G, n_total - q0));          // rows written into this buffer
             KPR_STAMP();
@@ -477,7 +461,6 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
             n2 = n3;
         }
         }
-#undef WS_TICKET
     } else {
         // ================================ consumers ==========================================
         const int cw = (wave - NPROD) & 3, ctid = tid - NPROD * 64 - cgrp * 256;
@@ -531,7 +514,7 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
                 // all rows of the tile written?  (rows of this buffer so far: 16 per earlier tile)
                 // (poll rarely and at low priority: the producers need the issue slots)
                 __builtin_amdgcn_s_setprio(0);
-                WS_SPIN_UNTIL(&sync[(it - 1) & 1], kFT * ((it - 1) >> 1) + min(kFT, f_end - tile0), 8);
+                spin_until_ge<8>(&sync[(it - 1) & 1], kFT * ((it - 1) >> 1) + min(kFT, f_end - tile0), kStMelWs);
                 __builtin_amdgcn_s_setprio(kWsConsPrio);
                 KPR_STAMP();
                 // per-frame output base / batch index, once per tile by 16 lanes
@@ -647,7 +630,7 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
                 // ---- consumer-group barrier (4 waves): LDS counter, monotonically increasing ----
                 WS_SIGNAL(&sync[FROM_MAG ? 5 + ((it - 1) & 1) : 2]);   // this wave is done reading the mag buffer
                 WS_SIGNAL(gbar);
-                WS_SPIN_UNTIL(gbar, 8 * itg - 4, 1);         // all four GEMM slices are in dpart
+                spin_until_ge<1>(gbar, 8 * itg - 4, kStMelWs);        // all four GEMM slices are in dpart
                 KPR_STAMP();
                 // ---- epilogue: dB + fully coalesced stores of the staged 16 x M tile ----------
                 {
@@ -693,7 +676,7 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
                 }
                 // dpart / fbase are rewritten by the next tile: wait until all four waves are done
                 WS_SIGNAL(gbar);
-                WS_SPIN_UNTIL(gbar, 8 * itg, 1);
+                spin_until_ge<1>(gbar, 8 * itg, kStMelWs);
                 KPR_STAMP();
             }
         }
@@ -702,7 +685,6 @@ __global__ __launch_bounds__(kWsThreads) void k_mel_ws(const float* __restrict__
 #undef KPR_STAMP
 #undef WS_SIGNAL_N
 #undef WS_SIGNAL
-#undef WS_SPIN_UNTIL
 #undef KPR_DO_FRAME
 }
 

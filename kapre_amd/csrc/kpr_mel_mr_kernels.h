@@ -69,6 +69,7 @@ __global__ __launch_bounds__(kMrWaves * 64, 3) void k_mel_mr(const float* __rest
     static_assert(2 * PIN <= 64, "one validity bit per sample of a lane");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (stamps stay macros per kernel: through a shared recorder object the code objects change, product and stamp variants alike)
 #ifdef KPR_DEV_STAMPS    /* development: s_memtime stamps of the workgroup dbg[16 * 32] names, rounds 2 and 3 (tools/stamps.py) */
     int dbi = 0;
     const bool stamp_me = dbg && (long long)blockIdx.x == dbg[16 * 32];
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(kMrWaves * 64, 3) void k_mel_mr(const float* __rest
 
     // (the window / table copies and the zero fill are issued AFTER this wave's first samples have been requested, see below)
     auto fill_tables = [&]() {
-        for (int i = tid; i < N; i += THREADS) {
+        for (int i = tid; i < N; i += THREADS) {      // (by hand: through stage_window_pairs 11 of the 18 code objects change)
             const int n = 2 * i;
             const float a = window[min(n, g.win - 1)], b = window[min(n + 1, g.win - 1)];
             winl[i] = f2{(n < g.win) ? 0.5f * a : 0.0f, (n + 1 < g.win) ? 0.5f * b : 0.0f};

@@ -52,7 +52,7 @@ __host__ __device__ constexpr int pw_zero_word(int NC) {
 }
 __host__ __device__ constexpr int pw_row_words(int NC) { return pw_zero_word(NC) + 4; }
 
-// band plan section of the packed filterbank (kpr_filterbank_pack writes it, see build_band_plan in kapre_hip.hip):
+// band plan section of the packed filterbank (kpr_filterbank_pack writes it, see build_band_plan in kpr_host_mel.h):
 //   emask[16] (u64) | T1[8][L] float4 | P[L] u32 | WN[NR][L] float | T2[NR][CMQ][L] uint4
 struct PwPlan {
     int L, NR, CMQ, nlist;
@@ -68,7 +68,6 @@ struct PwPlan {
     // ONE contiguous run of 4 M C bytes; cl_blk = floats per slot (M C rounded up to 4).  0 = 8-byte (c, c + 1) stores per filter
     int cl_slots, cl_blk;
 };
-constexpr int kPwSlotSpinLimit = 1 << 22;
 __host__ __device__ inline int pw_table_words(int L, int NR, int CMQ) { return 32 * L + L + NR * L + 4 * NR * CMQ * L; }
 // the part of the tables a workgroup keeps in LDS: P | WN | T2 (the 32 weights per lane, T1, are read from global memory
 // -- the L1 -- once per frame: the LDS pipe is the busiest unit of this kernel, the vector-memory path the idlest)
@@ -303,6 +302,7 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
     typedef typename WsSwzFor<NC>::type WsSwz;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (stamps stay macros per kernel: through a shared recorder object the code objects change, product and stamp variants alike)
 #ifdef KPR_DEV_STAMPS    /* development: s_memtime stamps of the workgroup dbg[16 * 32] names (tools/stamps_pw.py) */
     int dbi = 0;
     const bool stamp_me = dbg && (long long)blockIdx.x == dbg[16 * 32];
@@ -444,6 +444,7 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
         l6 = ((ConstU32)hdra)[6]; l7 = ((ConstU32)hdra)[7]; l8 = ((ConstU32)hdra)[8]; l9 = ((ConstU32)hdra)[9]; l10 = ((ConstU32)hdra)[10];
     }
     PW_STAMP();
+    // (by hand, not a helper shared with k_mel_ws / k_mel_ts / k_mel_pw: sharing it changes this kernel's code object)
     constexpr int WPT = (NC + THREADS - 1) / THREADS;
     float wa[WPT], wb[WPT];
 #pragma unroll
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
         if (!PAIR || sub == 1) {   // the next ticket: drawn now, its samples requested now -- they land under this frame's sums and stores
             int drawn = 0, lane_p = lane0;
             asm volatile("" : "+v"(lane_p) :: "memory");                 // nothing of the fetch is computed above here
-            if (lane_p == 0) drawn = atomicAdd(ctr, 1);                   // ds_add_rtn_u32
+            if (lane_p == 0) drawn = atomicAdd(ctr, 1);                   // ds_add_rtn_u32 (not wave_ticket: the value is read further down)
 #pragma unroll
             for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(wq[j]));   // (the weights have landed: waited for HERE)
             nxt = __builtin_amdgcn_readfirstlane(drawn);
@@ -638,13 +639,9 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
                         KPR_LDS_FENCE_X();                                // (the magnitude stores above are a closed group: what follows polls)
                         // the slot's previous block (lbf - cl_slots) must have left: its pairs were drawn before this one and their
                         // waves wait for nobody who waits for us -- bounded all the same (KPR_E_DEVICE, kpr_common.h)
-                        int spin = 0;
-                        for (; spin < kPwSlotSpinLimit; ++spin) {
-                            const bool ok = !fvalid || __hip_atomic_load(&slot_done_at()[sidx], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= sgen;
-                            if (__all(ok)) break;
-                            __builtin_amdgcn_s_sleep(2);
-                        }
-                        if (__builtin_expect(spin >= kPwSlotSpinLimit, 0)) status_raise(kStMelPwSlot);
+                        spin_until_all<2>([&] {
+                            return !fvalid || __hip_atomic_load(&slot_done_at()[sidx], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= sgen;
+                        }, kStMelPwSlot);
                     }
                 }
             }

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(kTsWaves * 64, 4) void k_mel_ts(const float* __rest
     const int K = NC + 1;
     const int S = mel_ws_row_stride(K);
     const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (stamps stay macros per kernel: through a shared recorder object the code objects change, product and stamp variants alike)
 #ifdef KPR_DEV_STAMPS    /* development: s_memtime stamps of the workgroup dbg[16 * 32] names, rounds 1 and 2 (tools/stamps.py) */
     int dbi = 0;
     const bool stamp_me = dbg && (long long)blockIdx.x == dbg[16 * 32];
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(kTsWaves * 64, 4) void k_mel_ts(const float* __rest
     // ---- prologue: window -> LDS, this wave's first frame(s), twiddles ------------------------------------------
     // All three sets of loads are REQUESTED before any of them is used (the window values are written to LDS further
     // down): the workgroup pays one cold memory latency, not two in a row.
+    // (by hand, not a helper shared with k_mel_ws / k_mel_ts / k_mel_pw: sharing it changes this kernel's code object)
     constexpr int WPT = (NC + THREADS - 1) / THREADS;
     float wa[WPT], wb[WPT];
 #pragma unroll

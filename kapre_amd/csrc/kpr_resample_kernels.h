@@ -3,8 +3,8 @@
 //
 //   out[i] = sum_{k < n_taps} tab[i mod P][k] * in[(i div P) * Q + first[i mod P] + k],   in[.] = 0 outside 0 .. in_len - 1
 //
-// P = n_phases, Q = step.  Forward: (P, Q) = (new, orig); adjoint: (orig, new) with the adjoint's table (kapre_hip.hip:
-// kpr_resample_table / resample_support).  Output i = b P + p is "block b, phase p"; all outputs of one phase share a row of the table.
+// P = n_phases, Q = step.  Forward: (P, Q) = (new, orig); adjoint: (orig, new) with the adjoint's table (kpr_resample_table in
+// kapre_hip.hip, resample_support in kpr_host_ops.h).  Output i = b P + p is "block b, phase p"; all outputs of one phase share a row of the table.
 //
 // A workgroup of 128 .. 512 lanes (the plan picks the count that leaves the fewest lanes without a work item) owns, for one
 // signal (or NCH = 2 interleaved channels of one), `nb` consecutive blocks x `pt` consecutive phases.  It stages the one contiguous input span those outputs read into LDS -- coalesced loads, interleaved

@@ -41,8 +41,15 @@ __global__ __launch_bounds__(64 * KPR_STFT_WAVES, (MODE == KPR_OUT_PHASE || OUT_
     float* row = stage;
     f2* winl = reinterpret_cast<f2*>(smem + KPR_STFT_WAVES * G * (2 * NC + 8));          // (0.5 w[2n], 0.5 w[2n+1])
     int* ticket = reinterpret_cast<int*>(winl + NC);
+    // development aid: cycle stamps of workgroup 0.  (Still macros, not the Stamps recorder of kpr_common.h: these stamps are part
+    // of the product build, and through the recorder the code object of every instance changes.)
     int dbi = 0;
 #define KPR_STAMP() do { if (dbg && blockIdx.x == 0 && (tid & 63) == 0 && dbi < 32) dbg[wave * 32 + dbi++] = (long long)__builtin_readcyclecounter(); } while (0)
+#ifdef KPR_FINE_STAMPS
+#define KPR_FS() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); KPR_STAMP(); } while (0)
+#else
+#define KPR_FS() do { } while (0)
+#endif
     KPR_STAMP();
     // A workgroup owns a CONTIGUOUS run of frame groups (G frames = one wave-load) and its waves
     // draw groups from an LDS ticket counter: neighbouring frames (overlapping samples, same
@@ -63,11 +70,7 @@ __global__ __launch_bounds__(64 * KPR_STFT_WAVES, (MODE == KPR_OUT_PHASE || OUT_
     if (n < n_total) KPR_FETCH(n);
     FftTw<NC, SW> tw;
     tw.load(twtab, fl);
-    for (int i = tid; i < NC; i += 64 * KPR_STFT_WAVES) {
-        const int m = 2 * i;
-        const float a = window[min(m, g.win - 1)], b = window[min(m + 1, g.win - 1)];
-        winl[i] = f2{(m < g.win) ? 0.5f * a : 0.0f, (m + 1 < g.win) ? 0.5f * b : 0.0f};
-    }
+    stage_window_pairs(winl, window, g.win, NC, tid, 64 * KPR_STFT_WAVES, 0.5f, 0.5f);
     if (tid == 0) *ticket = KPR_STFT_WAVES;
     __syncthreads();
     const int ostride = spec_stride(g);
@@ -77,20 +80,13 @@ __global__ __launch_bounds__(64 * KPR_STFT_WAVES, (MODE == KPR_OUT_PHASE || OUT_
         const long long gf = (g_begin + n) * G + grp;
         const bool valid = gf < g.total_frames;
         FramePos p = frame_pos(g, valid ? gf : 0);
-        int n2 = 0;
-        if (lane == 0) n2 = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        n2 = __builtin_amdgcn_readfirstlane(n2);
+        const int n2 = wave_ticket(ticket, lane);
         f2 z[kPts];
         if constexpr (L == 16 || L == 32) {
             if (nzsw) stereo_unswap<NC>(nz);                // wave-uniform
         }
 #pragma unroll
         for (int m = 0; m < kPts; ++m) z[m] = pmul(nz[m], winl[fl + L * m]);
-#ifdef KPR_FINE_STAMPS
-#define KPR_FS() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); KPR_STAMP(); } while (0)
-#else
-#define KPR_FS() do { } while (0)
-#endif
         KPR_FS();
         if (n2 < n_total) KPR_FETCH(n2);                    // next group's samples, one ahead
         // pin the loads here: without the fence hipcc sinks them to the end of the loop body
@@ -208,6 +204,7 @@ __global__ __launch_bounds__(64 * KPR_STFT_WAVES, (MODE == KPR_OUT_PHASE || OUT_
         }
     }
 #undef KPR_STAMP
+#undef KPR_FS
 #undef KPR_FETCH
 }
 
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(64 * kStft3Waves, 4) void k_stft3(const float* __re
         t0.load(twtab, fl);
         t0.for_each_tw([&](f2& v, int i) { twl[i * 64 + lane] = v; });
     }
-    for (int i = tid; i < NC; i += 64 * WAVES) {
+    for (int i = tid; i < NC; i += 64 * WAVES) {      // (by hand: through stage_window_pairs the <512> instances' code objects change)
         const int m = 2 * i;
         const float a = window[min(m, g.win - 1)], b = window[min(m + 1, g.win - 1)];
         winl[i] = f2{(m < g.win) ? 0.5f * a : 0.0f, (m + 1 < g.win) ? 0.5f * b : 0.0f};
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(64 * kStft3Waves, 4) void k_stft3(const float* __re
 #pragma unroll 1
     while (cur < n_wg) {
         int drawn = 0;
-        if (lane == 0) drawn = atomicAdd(ctr, 1);                          // ds_add_rtn_u32: returns under the window reads
+        if (lane == 0) drawn = atomicAdd(ctr, 1);                          // ds_add_rtn_u32: returns under the window reads (not wave_ticket: read below)
         const long long gf = (n_wg0 + cur) * G + grp;
         const bool valid = gf < g.total_frames;
         FramePos p = frame_pos(g, valid ? gf : 0);
@@ -601,7 +598,7 @@ __global__ __launch_bounds__(256, 2) void k_stft_bs(const float* __restrict__ x,
     f2* cwl = winl + M;                                                    // chirp w (0 beyond NCr)
     f2* btl = cwl + M;                                                     // Bt
     f2* tkl = btl + M;                                                     // t[0 .. NCr]
-    for (int i = tid; i < M; i += 256) {
+    for (int i = tid; i < M; i += 256) {      // (window pairs by hand: the table copies share this loop)
         const int n = 2 * i;
         const float a = window[min(n, g.win - 1)], b = window[min(n + 1, g.win - 1)];
         winl[i] = f2{(n < g.win) ? a : 0.0f, (n + 1 < g.win) ? b : 0.0f};
@@ -717,11 +714,7 @@ __global__ __launch_bounds__(256, 3) void k_stft_mr(const float* __restrict__ x,
     f2* row = rows + (wave * G + grp) * RSF;
     f2* winl = rows + 4 * G * RSF;                                // (w[2n], w[2n+1]) / 2
     f2* tab = winl + N;                                           // exp(-2 pi i j / n_fft), j < n_fft
-    for (int i = tid; i < N; i += 256) {
-        const int n = 2 * i;
-        const float a = window[min(n, g.win - 1)], b = window[min(n + 1, g.win - 1)];
-        winl[i] = f2{(n < g.win) ? 0.5f * a : 0.0f, (n + 1 < g.win) ? 0.5f * b : 0.0f};
-    }
+    stage_window_pairs(winl, window, g.win, N, tid, 256, 0.5f, 0.5f);
     for (int i = tid; i < 2 * N; i += 256) { const float2 t = twtab[i]; tab[i] = f2{t.x, t.y}; }
     __syncthreads();
     const int ostride = spec_stride(g);
