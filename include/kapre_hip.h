@@ -145,6 +145,10 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *   "fb_variant"   0 = automatic (default: stand-alone ApplyFilterbank with a band plan in the packed filterbank -- mel / triangular
  *                  banks, n_freq - 1 a multiple of four up to 1024 -- runs k_fb_pw, banded row sums, on contiguous rows and on rows of
  *                  two interleaved channels) | 1 = the MFMA kernels of rounds 2-5 for every bank (A/B runs, tests)
+ *   "mel_pw_plain" 1 = (default) n_fft 2048 mel launches without decibels on contiguous input rows with a linear output (one
+ *                  channel, or channels_first in and out) and a band plan of two rounds / one offset quad (the 128-filter mel bank
+ *                  at 44.1 kHz) run k_mel_plain_pw, the plain-output instance of k_mel_pw | 0 = k_mel_pw for those too (A/B runs,
+ *                  tests; bit-identical results)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);

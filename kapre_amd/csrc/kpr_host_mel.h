@@ -498,6 +498,41 @@ static int launch_mel_pw(const float* x, const Geom& g, const float* window, con
                        (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
     return launch_check("k_mel_pw", NC, W == 4 ? "w4" : W == 8 ? "w8" : "w16");
 }
+// the plain-output instance k_mel_plain_pw (kpr_mel_pw_kernels.h): n_fft 2048, no decibels, contiguous rows in, linear rows out,
+// a band plan of exactly (NR, CMQ) -- mel_route checks all of it (MelRoute::plain).  Same grid, LDS and ticket split as launch_mel_pw.
+template <int NC, int W, int NR, int CMQ>
+static int launch_mel_pw_plain(const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
+                               const PackInfo& pi, int M, float* out, hipStream_t st) {
+    PwPlan pl{(int)pi.L, (int)pi.NR, (int)pi.CMQ, (int)pi.nlist, M, reinterpret_cast<const unsigned*>(blob) + pi.band_off,
+              reinterpret_cast<const unsigned*>(blob), pi.band_off, 0, 0};
+    if (pl.L * kPts != NC || pl.NR != NR || pl.CMQ != CMQ) return no_instance("k_mel_plain_pw");
+    const size_t lds = pw_lds_bytes(NC, W, NR, CMQ);
+    static LdsOptIn lds_opt_in;
+    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_mel_plain_pw<NC, W, NR, CMQ>))) return e;
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const long long tickets = g.total_frames;                                   // a ticket = one frame of one wave
+    const int per_cu = std::max(1, std::min(16 / W, (int)(160 * 1024 / lds)));  // sixteen waves per CU (128 VGPRs)
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((tickets + W - 1) / W, (long long)per_cu * cus));
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_mel_pw<%d,%d,plain>: grid %u, lds %zu B, NR %d CMQ %d list %d, %lld tickets\n", NC, W, grid, lds,
+                pl.NR, pl.CMQ, pl.nlist, tickets);
+    if (int e = status_word_ready()) return e;                  // (a stale band plan is reported there)
+    hipLaunchKernelGGL((k_mel_plain_pw<NC, W, NR, CMQ>), dim3(grid), dim3(W * 64), lds, st, x, g, window, tw, pl, out,
+                       (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
+    // the general kernel's label with ",plain" behind it: "k_mel_pw<1024,w16>,plain" (what matches the general label matches this one)
+    if (int e = launch_check("k_mel_pw", NC, W == 4 ? "w4" : W == 8 ? "w8" : "w16")) return e;
+    if (g_launches.size() < 200) g_launches += ",plain";
+    return 0;
+}
+static int launch_mel_pw_plain_w(int w, const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
+                                 const PackInfo& pi, int M, float* out, hipStream_t st) {
+    switch (w) {
+        case 4:  return launch_mel_pw_plain<1024, 4, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
+        case 16: return launch_mel_pw_plain<1024, 16, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
+        default: return launch_mel_pw_plain<1024, 8, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
+    }
+}
 constexpr int kPwPairWaves = 12;                                 // waves per workgroup of the PAIR form
 // the PAIR form's channels_last staging: output slots (0: 8-byte stores) of M x C floats each
 static int mel_pw_pair_slots(const Geom& g, const PackInfo& pi, int M, const float* out) {
@@ -686,6 +721,7 @@ struct MelRoute {
     int fam;
     int cfast;                 // Geom::cfast of the launch
     int w;                     // MEL_PW: waves per workgroup
+    int plain;                 // MEL_PW: the plain-output instance k_mel_plain_pw (launch_mel_pw_plain)
     int cl_slots;              // MEL_PW_PAIR: mel_pw_pair_slots
     int rf64;                  // MEL_TS: the 64-frame-round instance (n_fft 512)
     int ws_form;               // MEL_WS, PROD_WS: mel_ws_form
@@ -698,7 +734,7 @@ struct MelRoute {
 
 // s: the cropped geometry, g: its Geom; packed: a verified packed filterbank (pi: its band plan), kr: k-ranges (NULL: dense)
 static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool packed, const PackInfo& pi, const MelSched& sch,
-                          const int32_t* kr, const float* out, int cus) {
+                          const int32_t* kr, const float* out, int cus, bool db_on) {
     MelRoute r{};
     const int n_fft = s->n_fft, mv = opt(OPT_MEL_VARIANT);
     const bool fits = g.total_frames < 0x7fffff00LL;
@@ -723,6 +759,10 @@ static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool pac
         const bool pair_ok = cfast && (g.C % 2) == 0 && (n_fft == 2048 || n_fft == 1024);
         const bool pair_auto = pair_ok && (n_fft == 2048 || g.C >= 4) && tickets_w >= 24LL * cus;
         r.fam = MEL_PW;
+        // n_fft 2048 without decibels on contiguous rows, linear output rows, the (NR, CMQ) = (2, 1) plan (128 mel filters at 44.1 kHz):
+        // the plain-output instance ("mel_pw_plain" 0 = never: A/B runs, tests); `fits` keeps total_frames below 2^31
+        r.plain = n_fft == 2048 && !db_on && (g.C == 1 || (!g.in_cl && !g.out_cl)) && pi.L == 64 && pi.NR == 2 && pi.CMQ == 1 &&
+                  opt(OPT_MEL_PW_PLAIN) != 0;
         if (pair_ok && (mv == 8 || (mv == 0 && pair_auto))) {
             Geom gk = g;
             gk.cfast = cfast;

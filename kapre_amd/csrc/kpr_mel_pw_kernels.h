@@ -129,7 +129,9 @@ KPR_DEV PwMasks pw_load_masks(const unsigned* __restrict__ sec) {
 // wq(j), j < 8: the lane's weight quads (w0, w1 of bins 2 j, 2 j + 1) -- an array element for the kernels that hold them in
 // registers, an LDS read for the ST instances of k_fb_pw, which have no 32 registers to spare (WLATE: each pair of quads is
 // fetched when its four bins are due, a scheduling barrier keeps hipcc from hoisting all eight reads to the top)
-template <int NC, bool EMIT_LDS, bool GATHER32, int IL, int NQ, bool WLATE = false, class WQ, class Emit>
+// SNR, SCMQ > 0 (k_mel_plain_pw): the plan's (NR, CMQ) are compile-time constants and stage 2 is spelled out -- every offset quad
+// and Nyquist weight is requested at once, all gathers follow, then the same additions in the same order as the loops below.
+template <int NC, bool EMIT_LDS, bool GATHER32, int IL, int NQ, bool WLATE = false, int SNR = 0, int SCMQ = 0, class WQ, class Emit>
 KPR_DEV void pw_band_core_w(float* row, int fl, const PwMasks& em, WQ&& wq, const float* tab, int NR, int CMQ,
                             const f4 (&mm)[NQ], float magn, unsigned ptr, Emit&& emit) {
     static_assert((IL == 0 && NQ == 4) || (IL > 0 && NQ == 8), "16 bins per lane: four quads, or eight with two channels interleaved");
@@ -192,6 +194,39 @@ KPR_DEV void pw_band_core_w(float* row, int fl, const PwMasks& em, WQ&& wq, cons
     const float* wn = tab + L + fl;
     const uint4* t2 = reinterpret_cast<const uint4*>(tab + (1 + NR) * L) + fl;
     const char* rowc = reinterpret_cast<const char*>(row);
+    if constexpr (SNR > 0) {
+        static_assert(GATHER32 && !EMIT_LDS, "the unrolled stage 2 is the 32-bit gather form");
+        uint4 o[SNR * SCMQ];
+        float wr_[SNR], gu[SNR * SCMQ][4], gt[SNR * SCMQ][4];
+#pragma unroll
+        for (int i = 0; i < SNR * SCMQ; ++i) o[i] = t2[i * L];
+#pragma unroll
+        for (int r = 0; r < SNR; ++r) wr_[r] = wn[r * L];
+#pragma unroll
+        for (int i = 0; i < SNR * SCMQ; ++i) {
+            const unsigned ow[4] = {o[i].x, o[i].y, o[i].z, o[i].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                gu[i][e] = *reinterpret_cast<const float*>(rowc + (ow[e] & 0xffffu));
+                gt[i][e] = *reinterpret_cast<const float*>(rowc + (ow[e] >> 16));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < SNR; ++r) {
+            float u = 0.0f, t = 0.0f;
+#pragma unroll
+            for (int q = 0; q < SCMQ; ++q) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    u += gu[r * SCMQ + q][e];
+                    t += gt[r * SCMQ + q][e];
+                }
+            }
+            emit(r, fmaf(wr_[r], magn, u + t));
+        }
+        KPR_LDS_FENCE_X();
+        return;
+    }
     float t_prev = 0.0f;                                                  // this lane's S1 sum of the round before
 #ifdef KPR_PW_KO_STAGE2         /* development knock-out (counters only, wrong sums): no gathers (tools/lds_conflicts.sh) */
     for (int r = 0; r < NR; ++r) emit(r, fmaf(wn[r * L], magn, acc.x));
@@ -703,6 +738,220 @@ __global__ __launch_bounds__(W * 64, PAIR ? 3 : 4) void k_mel_pw(const float* __
       cur = nxt;
     }
     if (db.enabled) db_flush_wave(dbrun, item_stats, db);
+#ifdef KPR_DEV_STAMPS    /* every workgroup: start / end on the constant 100 MHz clock and on the shader clock (dbg[1024 + 4 bx ..]) */
+    if (dbg && tid == 0 && blockIdx.x < 4096) {
+        long long* e = dbg + 1024 + 4 * (long long)blockIdx.x;
+        e[0] = (long long)wg_r0; e[1] = (long long)__builtin_amdgcn_s_memrealtime();
+        e[2] = (long long)wg_c0; e[3] = (long long)__builtin_readcyclecounter();
+    }
+#endif
+#undef PW_STAMP
+}
+
+// ---- k_mel_plain_pw: the plain-output instance of the one-frame-per-ticket kernel --------------------------------------------------
+// k_mel_pw<1024, W, false> is ONE code object for decibels on and off, one channel and channels_first, linear and strided outputs
+// and any (NR, CMQ) of the band plan, and pays for that choice in every frame (profiles/mel_pw_plain.md has the listing counts).
+// This kernel is the same frame loop for the launches that need none of it.  The host (mel_route) guarantees:
+//   no decibels; contiguous input rows and a linear output, frames numbered (b C + c) F + f (one channel, or channels_first in and
+//   out); total_frames < 2^31; the plan's (L, NR, CMQ) = (NC / 16, NR, CMQ) of the instance (the blob's header is still compared
+//   with the plan before the first access through pl.sec).
+// What is different per frame: no DbDev / DbRun / item_stats; stage 2 unrolled (pw_band_core_w<..., NR, CMQ>: two dependent LDS
+// round trips instead of three per round); the output row's base gf M as a scalar pair and 32-bit lane offsets; the 32-bit scalar
+// frame test; the ticket drawn with one LDS instruction on lane 0 (the wrapping increment: hipcc turns an atomic ADD of a uniform
+// value into its wave-aggregated form -- mbcnt, bcnt, a second exec switch -- even under a one-lane mask).  Every floating-point
+// operation and its order are those of k_mel_pw: the two give the same bits (tests/test_mel_pw_plain.py).
+// Prologue, fetch (scalar fast path, general path for edge frames, zeros without a ticket), HDR_LATE, tail_prio and the stamps are
+// k_mel_pw's, spelled out for G = 1 (see there for the why of every step).
+// (The name keeps "k_mel_pw" out of the symbol: the ISA audit counts the general kernel's instances by that substring.)
+template <int NC, int W, int NR, int CMQ>
+__global__ __launch_bounds__(W * 64, 4) void k_mel_plain_pw(const float* __restrict__ x, Geom g, const float* __restrict__ window,
+                                                            const float2* __restrict__ twtab, PwPlan pl, float* __restrict__ out,
+                                                            int run_q, int run_r, long long* __restrict__ dbg) {
+    constexpr int L = NC / kPts;
+    static_assert(L == 64, "one frame per wave and ticket");
+    constexpr int THREADS = W * 64;
+    constexpr int RWD = pw_row_words(NC);
+    typedef typename WsSwzFor<NC>::type WsSwz;
+    static_assert(IsWide<WsSwz>::value, "the n_fft 2048 transform");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef KPR_DEV_STAMPS    /* development: s_memtime stamps of the workgroup dbg[16 * 32] names (tools/stamps_pw.py) */
+    int dbi = 0;
+    const bool stamp_me = dbg && (long long)blockIdx.x == dbg[16 * 32];
+#define PW_STAMP() do { if (stamp_me && lane0 == 0 && dbi < 32) dbg[wave * 32 + dbi++] = (long long)__builtin_readcyclecounter(); } while (0)
+    const unsigned long long wg_r0 = __builtin_amdgcn_s_memrealtime(), wg_c0 = __builtin_readcyclecounter();
+#else
+#define PW_STAMP() do { (void)dbg; } while (0)
+#endif
+    PW_STAMP();
+    typedef const unsigned __attribute__((address_space(4)))* ConstU32;
+    unsigned long long hdra = (unsigned long long)pl.hdr;
+    asm volatile("" : "+s"(hdra));
+
+    float* rows = smem;                                                   // [W][RWD]
+    float* tab = smem + W * RWD;                                          // P | WN | T2
+    f2* winl = reinterpret_cast<f2*>(tab + pw_lds_table_words(L, NR, CMQ));
+    int* ctr = reinterpret_cast<int*>(winl + NC);                         // the workgroup's ticket counter
+
+    const int bx = (int)blockIdx.x;
+    const int t_wg0 = run_q * bx + min(bx, run_r);
+    const int n_wg = run_q + (bx < run_r ? 1 : 0);
+
+    auto fetch_ticket = [&](int tk, int lane_, f2 (&dst)[kPts]) {         // tk = ticket of this workgroup, wave-uniform
+        if (tk < n_wg) {
+            const unsigned gf = (unsigned)(t_wg0 + tk);
+            const unsigned bc = magic_div(gf, g.mF, g.sF);
+            const int s0 = (int)(gf - bc * (unsigned)g.F) * g.hop - g.pad_left;
+            if (gf < (unsigned)g.total_frames && s0 >= 0 && s0 + 2 * NC <= (int)g.T) {
+                typedef const char __attribute__((address_space(1)))* GlobalB;
+                typedef const float __attribute__((address_space(1)))* GlobalF;
+                unsigned long long b0 = (unsigned long long)(x + ((long long)bc * g.T + s0));
+                unsigned long long b1 = b0 + 8 * (kPts / 2) * L;
+                asm volatile("" : "+s"(b0), "+s"(b1));               // (two scalar bases: the offsets stay immediates)
+                const unsigned lo = 8u * (unsigned)(lane_ & (L - 1));
+#pragma unroll
+                for (int m = 0; m < kPts; ++m) {
+                    const GlobalB p = (GlobalB)(m < kPts / 2 ? b0 : b1) + lo + 8 * L * (m % (kPts / 2));
+                    dst[m] = f2{((GlobalF)p)[0], ((GlobalF)p)[1]};       // (one dwordx2)
+                }
+                return;
+            }
+            const bool v = gf < (unsigned)g.total_frames;                 // edge frames: the zero-filling fetch
+            FramePos p = frame_pos32(g, v ? gf : 0u);
+            fetch_frame_z<NC>(x, g, p, v, lane_ & (L - 1), dst);
+        } else {
+#pragma unroll
+            for (int m = 0; m < kPts; ++m) asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(dst[m].x), "=v"(dst[m].y));
+        }
+    };
+    f2 nz[kPts];
+    int cur = wave;                                                       // the first ticket of every wave is static
+    fetch_ticket(cur, lane0, nz);
+    asm volatile("" : "+s"(hdra) :: "memory");                           // (HDR_LATE: behind the sample requests)
+    const unsigned l6 = ((ConstU32)hdra)[6], l7 = ((ConstU32)hdra)[7], l8 = ((ConstU32)hdra)[8], l9 = ((ConstU32)hdra)[9],
+                   l10 = ((ConstU32)hdra)[10];
+    PW_STAMP();
+    constexpr int WPT = (NC + THREADS - 1) / THREADS;
+    float wa[WPT], wb[WPT];
+#pragma unroll
+    for (int u = 0; u < WPT; ++u) {
+        const int n = 2 * min(tid + u * THREADS, NC - 1);
+        wa[u] = window[min(n, g.win - 1)];
+        wb[u] = window[min(n + 1, g.win - 1)];
+    }
+    static_assert(FftTw<NC, WsSwz>::kNumTw <= kPwTwRegs, "LDS staging area of the twiddle set");
+    f2* twl = reinterpret_cast<f2*>(ctr + 4);                             // [kNumTw][64]
+    if (wave == 0) {
+        FftTw<NC, WsSwz> t0;
+        t0.load(twtab, lane0);
+        t0.for_each_tw([&](f2& v, int i) { twl[i * 64 + lane0] = v; });
+    }
+    PW_STAMP();
+    // (compared BEFORE the first access through pl.sec; the instance's NR / CMQ size the LDS tables, so they are compared too)
+    if (l6 != pl.band_off || l7 != (unsigned)pl.L || l8 != (unsigned)pl.NR || l9 != (unsigned)pl.CMQ || l10 != (unsigned)pl.nlist ||
+        pl.L != L || pl.NR != NR || pl.CMQ != CMQ) {
+        if (tid == 0) status_raise(kStStalePlan);
+        return;
+    }
+    {
+        const int nt = pw_lds_table_words(L, NR, CMQ);                   // multiple of 4
+        const uint4* src = reinterpret_cast<const uint4*>(pl.sec + kPwEmaskWords + 32 * L);
+        uint4* dst = reinterpret_cast<uint4*>(tab);
+        for (int i = tid; i < nt / 4; i += THREADS) dst[i] = src[i];
+    }
+#pragma unroll
+    for (int u = 0; u < WPT; ++u) {
+        const int i = tid + u * THREADS, n = 2 * i;
+        if (i < NC) winl[i] = f2{(n < g.win) ? 0.5f * wa[u] : 0.0f, (n + 1 < g.win) ? 0.5f * wb[u] : 0.0f};
+    }
+    if (lane0 < 4) rows[wave * RWD + pw_zero_word(NC) + lane0] = 0.0f;   // the zero words
+    if (tid == 0) *ctr = W;
+    PW_STAMP();
+    lds_barrier();
+    FftTw<NC, WsSwz> tw;
+    tw.for_each_tw([&](f2& v, int i) { v = twl[i * 64 + lane0]; });
+    tw.set_addresses(lane0);
+    PW_STAMP();
+
+    const bool tail_prio = n_wg < 8 * W;                                  // (k_mel_pw: the end of a short run)
+    if (tail_prio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll 1
+    while (cur < n_wg) {
+        int nxt = 0;
+        int lane_f = lane0;
+        asm volatile("" : "+v"(lane_f));
+        const int lane = lane_f, fl = lane & (L - 1);
+        float* row = rows + wave * RWD;
+        f4 wq[8];
+        {
+            // ---- samples -> window -> rFFT -> |X| row -------------------------------------------------------------------
+            f2 z[kPts];
+#pragma unroll
+            for (int m = 0; m < kPts; ++m) z[m] = pmul(nz[m], winl[fl + L * m]);
+            tw.refresh();
+            cfft_forward_wide_planar(z, tw, row);
+            pw_load_weights<NC>(pl.sec, fl, wq);
+            float mk[kPts / 2], mp[kPts / 2];
+            float mid = 0.0f;
+            rfft_pair<NC>(z, tw, fl, lane, [&](int k, f2 xk, int kp, f2 xp) {
+                const float a = __builtin_amdgcn_sqrtf(xk.x * xk.x + xk.y * xk.y);
+                if (kp >= 0) {
+                    const int m = (k - fl) / L;                           // compile-time after unrolling
+                    mk[m] = a;
+                    mp[m] = __builtin_amdgcn_sqrtf(xp.x * xp.x + xp.y * xp.y);
+                } else mid = a;                                           // k = NC / 2 (lane 0 only)
+            });
+            float* lo = row + fl;
+            float* hi = row + (NC - fl);
+            float* hi0 = hi + ((fl == 0) ? 4 : 0);
+            KPR_LDS_FENCE_W();
+#pragma unroll
+            for (int m = 0; m < kPts / 2; ++m) lo[L * m + 4 * ((L * m) >> 6)] = mk[m];
+#pragma unroll
+            for (int m = 0; m < kPts / 2; ++m) {
+                const int off = -L * m + 4 * ((L * (15 - m)) >> 6);
+                if ((L * (16 - m)) % 64 == 0) hi0[off] = mp[m]; else hi[off] = mp[m];
+            }
+            if (fl == 0) row[pw_mag_word(NC / 2)] = mid;
+        }
+        {   // the next ticket: drawn now, its samples requested now -- they land under this frame's sums and stores
+            unsigned drawn = 0;
+            int lane_p = lane0;
+            asm volatile("" : "+v"(lane_p) :: "memory");                 // nothing of the fetch is computed above here
+            if (lane_p == 0)                                              // one ds_inc_rtn_u32: old + 1 below the wrap value
+                drawn = __builtin_amdgcn_atomic_inc32(reinterpret_cast<unsigned*>(ctr), 0xffffffffu, __ATOMIC_RELAXED, "workgroup");
+#pragma unroll
+            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(wq[j]));   // (the weights have landed: waited for HERE)
+            nxt = __builtin_amdgcn_readfirstlane((int)drawn);
+            fetch_ticket(nxt, lane_p, nz);
+            if (tail_prio && nxt >= n_wg) __builtin_amdgcn_s_setprio(0);  // (see tail_prio)
+        }
+        PW_STAMP();
+        // ---- banded mel sums of the row, stores: row gf of the (total_frames, M) output ------------------------------------
+        {
+            const unsigned gf = (unsigned)(t_wg0 + cur);
+            const bool fvalid = gf < (unsigned)g.total_frames;            // scalar
+            typedef char __attribute__((address_space(1)))* GlobalWB;
+            typedef float __attribute__((address_space(1)))* GlobalWF;
+            unsigned long long ob = (unsigned long long)(out + (long long)gf * pl.M);
+            asm volatile("" : "+s"(ob));                                  // (a scalar base: the rounds' offsets stay immediates)
+            const PwMasks em = pw_load_masks(pl.sec);
+            const unsigned rowb = (unsigned)(size_t)row;
+            KPR_LDS_FENCE_R();
+            const f4a* mq = reinterpret_cast<const f4a*>(row + 16 * fl + 4 * (fl >> 2));
+            const f4 mm[4] = {mq[0], mq[1], mq[2], mq[3]};
+            const float magn = row[pw_mag_word(NC)];                      // |X[Nyquist]| (one address: a broadcast)
+            const unsigned ptr = rowb + reinterpret_cast<const unsigned*>(tab)[fl];
+            KPR_LDS_FENCE_X();
+            const unsigned fo = 4u * (unsigned)fl;
+            pw_band_core_w<NC, false, true, 0, 4, false, NR, CMQ>(row, fl, em, [&](int j) { return wq[j]; }, tab, NR, CMQ, mm, magn, ptr,
+                                                                  [&](int r, float v) {
+                if (fvalid && fl + L * r < pl.M) ((GlobalWF)((GlobalWB)ob + fo))[L * r] = v;
+            });
+        }
+        PW_STAMP();
+        cur = nxt;
+    }
 #ifdef KPR_DEV_STAMPS    /* every workgroup: start / end on the constant 100 MHz clock and on the shader clock (dbg[1024 + 4 bx ..]) */
     if (dbg && tid == 0 && blockIdx.x < 4096) {
         long long* e = dbg + 1024 + 4 * (long long)blockIdx.x;
