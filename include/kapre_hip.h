@@ -149,6 +149,9 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *                  channel, or channels_first in and out) and a band plan of two rounds / one offset quad (the 128-filter mel bank
  *                  at 44.1 kHz) run k_mel_plain_pw, the plain-output instance of k_mel_pw | 0 = k_mel_pw for those too (A/B runs,
  *                  tests; bit-identical results)
+ *   "cmvn_variant" 0 = automatic (default: kpr_cmvn_f32 / kpr_cmvn_bwd_f32 keep a series of up to resident_frames frames
+ *                  (kpr_cmvn_plan) in registers -- one read, one write) | 1 = the streamed form, two sweeps, for every frame count
+ *                  (A/B runs, tests; bit-identical results)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -517,6 +520,40 @@ int kpr_pcen_bwd_params_f32(const float* x, const float* smooth, const float* gy
                             int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r,
                             float eps, float* gx /* may be NULL */, float* gparams /* (4, n_bands) */, void* workspace,
                             size_t workspace_bytes, kpr_stream_t stream);
+
+/* ---- CMVN: per-utterance mean / variance normalisation along time, kapre_amd.time_frequency.CMVN --------------------
+ * x: a float32 block seen as contiguous (outer, frames, inner), normalised along `frames`; every (outer, inner) pair is a column
+ * of its own (Kaldi's apply-cmvn --norm-vars per utterance, ESPnet's UtteranceMVN):
+ *   (batch, ch, frames, mel) [channels_first]: outer = batch * ch, inner = mel
+ *   (batch, frames, mel, ch) [channels_last] : outer = batch,      inner = mel * ch
+ * Per column, n = frames:
+ *   d[t] = x[t] - x[0];  m = (1/n) sum d[t];  c[t] = d[t] - m;  v = (1/n) sum c[t]^2 (population variance);  rstd = (v + eps)^-1/2
+ *   out[t] = c[t] rstd (norm_vars = 1)   or   out[t] = c[t] (norm_vars = 0)
+ * The shift by x[0] is part of the contract (decibel values sit far from 0: without it the sums lose five digits).  The sums
+ * are taken per chunk of *rows_per_wave frames, two-pass (mean, then sum (d - mean)^2), and the chunks are merged in time order
+ * with the pairwise update delta = mean_b - mean, mean += delta n_b / (n + n_b), M2 += M2_b + delta^2 n n_b / (n + n_b).
+ * A constant column (frames == 1 included) gives +0.0 bit for bit for eps > 0.  A NaN or Inf anywhere in a column makes that
+ * whole column non-finite and touches no other column.  The same inputs give the same bits on every call: no atomics; the order
+ * of every sum is a function of the shape.
+ * eps >= 0 and finite, norm_vars 0 or 1 (KPR_E_BADARG otherwise).
+ * rstd_out (may be NULL): receives rstd per column, (outer, inner) values, which kpr_cmvn_bwd_f32 takes as `rstd`; with
+ * norm_vars == 0 there is none: KPR_E_BADARG.
+ * _bwd: gx = d sum(gy * out) / dx from the forward pass's OUTPUT y, one launch (the means run over the frames of a column):
+ *   gx[t] = rstd (gy[t] - mean(gy) - y[t] mean(gy y))  (norm_vars = 1);   gx[t] = gy[t] - mean(gy)  (norm_vars = 0: y and rstd
+ *   are not read and may be NULL).
+ * Up to *resident_frames frames the series stays in registers (every input byte read once, every output byte written once);
+ * beyond, or with option "cmvn_variant" = 1, the input is read twice -- same chunks, same order: the same bits.  Pointers are
+ * 4-byte aligned; 16-byte accesses are used when inner % 4 == 0 and every pointer is 16-byte aligned.  Outputs must not overlap
+ * inputs or each other (x == out is KPR_E_BADARG).  frames * inner < 2^31 (KPR_E_UNSUPPORTED beyond).  outer, frames or
+ * inner == 0: returns 0, launches nothing.
+ * kpr_cmvn_plan (host only): the time tiling of the dispatch, the same for every shape -- a workgroup of *waves_per_group waves
+ * covers *waves_per_group * *rows_per_wave consecutive frames per step, *rows_per_wave per wave; *resident_frames is their
+ * product; chunk boundaries for tests. */
+int kpr_cmvn_plan(int64_t frames, int64_t inner, int* rows_per_wave, int* waves_per_group, int* resident_frames);
+int kpr_cmvn_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, int norm_vars, float eps,
+                 float* out, float* rstd_out /* may be NULL; outer*inner values */, kpr_stream_t stream);
+int kpr_cmvn_bwd_f32(const float* y, const float* rstd, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                     int norm_vars, float* gx, kpr_stream_t stream);
 
 /* ---- Resample: rational sample-rate conversion, kapre_amd.signal.Resample -------------------------------------------
  * Band-limited interpolation with a Hann-windowed sinc ("sinc_interp_hann").  With g = gcd(orig_freq, new_freq),

@@ -22,6 +22,7 @@ from .time_frequency import (
     Delta,
     ConcatenateFrequencyMap,
     PCEN,
+    CMVN,
 )
 
 from . import signal
@@ -88,6 +89,7 @@ __all__ = [
     'Delta',
     'ConcatenateFrequencyMap',
     'PCEN',
+    'CMVN',
     'Frame',
     'Energy',
     'MuLawEncoding',

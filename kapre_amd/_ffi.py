@@ -171,6 +171,13 @@ EXPORTS = {
                                                ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # CMVN (kapre_amd/time_frequency.py)
+    "kpr_cmvn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int)]),
+    "kpr_cmvn_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_cmvn_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     # Resample (kapre_amd/signal.py)
     "kpr_resample_table_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
@@ -694,6 +701,46 @@ def pcen_bwd_params(x, smooth, g, fmt, params, eps: float, want_gx: bool = True)
     _call("kpr_pcen_bwd_params_f32", x.device, ptr(x), ptr(smooth), ptr(g), *geom, *(ptr(p) for p in params), float(eps),
           ptr(gx), ptr(gparams), ptr(ws), ws_bytes)
     return gx, gparams
+
+
+# CMVN (kapre_amd/time_frequency.py)
+def cmvn_plan(frames: int, inner: int):
+    """(rows_per_wave, waves_per_group, resident_frames): the time tiling kpr_cmvn_f32 uses and the longest series it keeps in
+    registers (host only)."""
+    rows, waves, resident = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().kpr_cmvn_plan(int(frames), int(inner), ctypes.byref(rows), ctypes.byref(waves), ctypes.byref(resident)),
+          "kpr_cmvn_plan")
+    return rows.value, waves.value, resident.value
+
+
+def _cmvn_geometry(x, fmt):
+    """(outer, frames, inner) of the rank-4 ``x``; the shape of the per-column statistics"""
+    b, c, t, m = dims_of(x.shape, fmt)
+    if fmt in ("channels_last", CHANNELS_LAST):
+        return (b, t, m * c), (b, m, c)
+    return (b * c, t, m), (b, c, m)
+
+
+def cmvn(x, fmt, norm_vars: bool, eps: float, want_rstd: bool = False):
+    """Mean (and with ``norm_vars`` variance) normalisation along time of the rank-4 float32 ``x``.  With ``want_rstd``
+    (``norm_vars`` only) returns (out, rstd), rstd per column being what ``cmvn_bwd`` needs."""
+    import torch
+    geom, stats = _cmvn_geometry(x, fmt)
+    out = torch.empty_like(x)
+    rstd = torch.empty(stats, dtype=torch.float32, device=x.device) if want_rstd else None
+    _call("kpr_cmvn_f32", x.device, ptr(x), *geom, int(bool(norm_vars)), float(eps), ptr(out), ptr(rstd))
+    return (out, rstd) if want_rstd else out
+
+
+def cmvn_bwd(y, rstd, g, fmt, norm_vars: bool):
+    """Cotangent of ``x`` from the cotangent ``g`` of ``y = cmvn(x, ...)`` and the ``rstd`` of that call (without ``norm_vars``:
+    from ``g`` alone, ``y`` and ``rstd`` may be None)."""
+    import torch
+    g = g.contiguous().to(torch.float32)
+    gx = torch.empty_like(g)
+    geom, _ = _cmvn_geometry(g, fmt)
+    _call("kpr_cmvn_bwd_f32", g.device, ptr(y), ptr(rstd), ptr(g), *geom, int(bool(norm_vars)), ptr(gx))
+    return gx
 
 
 # Resample (kapre_amd/signal.py)

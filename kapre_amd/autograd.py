@@ -12,6 +12,7 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   of the cotangent (one kernel); mu-law decoding of float codes has an elementwise backward kernel, mu-law encoding
   returns integers and ends the tape; ``PCEN`` keeps its smoother ``S`` (the forward kernel's second output) and runs
   one backward kernel, the forward scan in reversed time (input gradient only: its parameters are constants);
+  ``CMVN`` keeps its output and ``rstd`` per column and runs one backward kernel, two sums along time and a sweep;
   ``Resample^T`` is the forward's polyphase kernel with the adjoint table;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
@@ -349,6 +350,25 @@ def _functions():
             gx, gp = _ffi.pcen_bwd_params(x, smooth, g, ctx.data_format, params, ctx.eps, want_gx=need[0])
             return (gx, None) + tuple(gp[i] if need[2 + i] else None for i in range(4)) + (None,)
 
+    class CmvnFn(torch.autograd.Function):
+        """y = (x - mean) rstd along time.  The forward launch leaves rstd per column; backward is one launch over the saved
+        output y, the cotangent and rstd (without ``norm_vars``: over the cotangent alone, nothing is saved)."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, norm_vars, eps):
+            ctx.data_format, ctx.norm_vars = data_format, norm_vars
+            x = x.detach()
+            if not norm_vars:
+                return _ffi.cmvn(x, data_format, False, eps)
+            y, rstd = _ffi.cmvn(x, data_format, True, eps, want_rstd=True)
+            ctx.save_for_backward(y, rstd)
+            return y
+
+        @staticmethod
+        def backward(ctx, g):
+            y, rstd = ctx.saved_tensors if ctx.norm_vars else (None, None)
+            return _ffi.cmvn_bwd(y, rstd, g, ctx.data_format, ctx.norm_vars), None, None, None
+
     class ResampleFn(torch.autograd.Function):
         """y = R x, a linear map: backward = the same polyphase kernel with the adjoint table (one launch)."""
 
@@ -365,7 +385,7 @@ def _functions():
 
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
-               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, resample=ResampleFn)
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn)
     return _FN
 
 
@@ -430,6 +450,10 @@ def freq_map_concat(x, data_format):
 
 def pcen(x, data_format, params, eps):
     return _functions()['pcen'].apply(x, data_format, *params, eps)
+
+
+def cmvn(x, data_format, norm_vars, eps):
+    return _functions()['cmvn'].apply(x, data_format, norm_vars, eps)
 
 
 def resample(x, data_format, forward_plan, adjoint_plan, out_len):

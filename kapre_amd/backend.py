@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen`` and ``resample`` have no counterpart there.
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn`` and ``resample`` have no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -418,6 +418,51 @@ def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='defaul
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt,
                      tensors if any(t is not None for t in tensors) else None)
+
+
+# --------------------------------------------------------------------------------------
+# CMVN
+# --------------------------------------------------------------------------------------
+def cmvn_parameters(norm_vars, eps):
+    """Validated (norm_vars, eps): a bool and a finite float >= 0 (``ValueError``)."""
+    if not isinstance(norm_vars, (bool, np.bool_)):
+        raise ValueError('CMVN: norm_vars must be a bool, got %r' % (norm_vars,))
+    if isinstance(eps, bool) or np.ndim(eps) != 0 or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError('CMVN: eps must be a scalar >= 0, got %r' % (eps,))
+    e32 = float(np.float32(eps))
+    if not (np.isfinite(e32) and e32 >= 0 and float(eps) >= 0):
+        raise ValueError('CMVN: eps must be finite and >= 0, got %r' % (eps,))
+    return bool(norm_vars), float(eps)
+
+
+def _cmvn_run(x, norm_vars, eps, data_format):
+    """CMVN of ``x`` (rank 4) in the resolved ``data_format``; recorded for autograd when ``x`` requires grad."""
+    import torch
+
+    from . import autograd
+    if len(x.shape) != 4:
+        raise ValueError('CMVN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise NotImplementedError('CMVN has float32 kernels only; got a float64 input (cast it to float32)')
+    if autograd.needs_grad(x):
+        return autograd.cmvn(autograd.prep(x, 'float32'), data_format, norm_vars, eps)
+    return _ffi.cmvn(_ffi.as_device(x, torch.float32), data_format, norm_vars, eps)
+
+
+def cmvn(x, norm_vars=True, eps=1e-5, data_format='default'):
+    """Per-utterance mean and variance normalisation along time (Kaldi's ``apply-cmvn --norm-vars``, ESPnet's ``UtteranceMVN``)
+    of a spectrogram batch on the GPU: (b, time, freq, ch) for ``channels_last``, (b, ch, time, freq) for ``channels_first``;
+    float32 out, same shape.  For every (batch item, channel, band), over its n frames:
+
+        d[t] = x[t] - x[0];  m = mean(d);  c[t] = d[t] - m;  y[t] = c[t] / sqrt(mean(c^2) + eps)    (``norm_vars``)
+                                                                y[t] = c[t]                            (else)
+
+    The variance is the population variance.  A constant series gives exactly +0.0.  One kernel, one pass over ``x`` up to
+    ``_ffi.cmvn_plan``'s resident frame count (128), two reads beyond.  A tensor that ``requires_grad`` gets a ``grad_fn``."""
+    validate_data_format_str(data_format)
+    norm_vars, eps = cmvn_parameters(norm_vars, eps)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return _cmvn_run(x, norm_vars, eps, fmt)
 
 
 # --------------------------------------------------------------------------------------

@@ -31,6 +31,9 @@
 //                             forward and backward: output-driven streaming kernels
 //   kpr_pcen_kernels.h        per-channel energy normalisation and its input gradient: a recurrence along time, tiled over
 //                             the waves of a workgroup (chunk end values through LDS, one barrier per super-block)
+//   kpr_cmvn_kernels.h        per-utterance mean / variance normalisation and its input gradient: a reduction along time in
+//                             k_pcen's geometry (chunk statistics through LDS, merged pairwise in a fixed order), resident in
+//                             registers up to 128 frames, two sweeps beyond
 //   kpr_resample_kernels.h    rational sample-rate conversion (signal.Resample): a polyphase gather over a staged input span,
 //                             forward and adjoint in one kernel
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
@@ -75,6 +78,7 @@
 #include "kpr_augment_kernels.h"
 #include "kpr_companding_kernels.h"
 #include "kpr_pcen_kernels.h"
+#include "kpr_cmvn_kernels.h"
 #include "kpr_resample_kernels.h"
 
 #include "kpr_host.h"
@@ -125,7 +129,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -970,6 +974,24 @@ int kpr_pcen_bwd_params_f32(const float* x, const float* smooth, const float* gy
                             float eps, float* gx, float* gparams, void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
     return run_pcen(true, x, smooth, gy, outer, frames, inner, band_div, n_bands, s, alpha, delta, r, eps, gx, nullptr, stream, true,
                     gparams, workspace, workspace_bytes);
+}
+
+/* ---- CMVN (kpr_cmvn_kernels.h) ---------------------------------------------------------------- */
+int kpr_cmvn_plan(int64_t frames, int64_t inner, int* rows_per_wave, int* waves_per_group, int* resident_frames) {
+    if (frames < 0 || inner < 0 || !rows_per_wave || !waves_per_group || !resident_frames)
+        return fail(KPR_E_BADARG, "bad frames/inner or NULL result");
+    *rows_per_wave = kCmvnRows;
+    *waves_per_group = kCmvnWaves;
+    *resident_frames = kCmvnRows * kCmvnWaves;
+    return 0;
+}
+int kpr_cmvn_f32(const float* x, int64_t outer, int64_t frames, int64_t inner, int norm_vars, float eps, float* out, float* rstd_out,
+                 kpr_stream_t stream) {
+    return run_cmvn(false, x, nullptr, nullptr, outer, frames, inner, norm_vars, eps, out, rstd_out, stream);
+}
+int kpr_cmvn_bwd_f32(const float* y, const float* rstd, const float* gy, int64_t outer, int64_t frames, int64_t inner, int norm_vars,
+                     float* gx, kpr_stream_t stream) {
+    return run_cmvn(true, y, rstd, gy, outer, frames, inner, norm_vars, 0.0f, gx, nullptr, stream);
 }
 
 /* ---- Resample (kpr_resample_kernels.h) ---------------------------------------------------------- */

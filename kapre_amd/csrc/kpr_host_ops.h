@@ -1,6 +1,6 @@
-// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN and
+// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN and
 // Resample entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h, kpr_augment_kernels.h,
-// kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_resample_kernels.h).
+// kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
 
@@ -235,6 +235,75 @@ static int run_pcen(bool bwd, const float* x, const float* smooth, const float* 
         else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD>), grid, block, 0, st, a);
     }
     return launch_check(bwd ? "k_pcen_bwd" : "k_pcen", v4 ? 4 : 1);
+}
+
+// ---- CMVN (kpr_cmvn_kernels.h): argument checks and launch of the forward / backward C entry points ----
+// forward: x -> out (and rstd_out, may be NULL).  backward: x is y of the forward pass; (y, rstd, gy) -> out = gx with norm_vars,
+// gy alone -> gx without (y and rstd are then not read and may be NULL)
+template <int V, int FORM>
+static void launch_cmvn(int mode, dim3 grid, dim3 block, hipStream_t st, const CmvnArgs& a) {
+    switch (mode) {
+        case CMVN_FWD: hipLaunchKernelGGL((k_cmvn<V, FORM, CMVN_FWD>), grid, block, 0, st, a); break;
+        case CMVN_FWD_RSTD: hipLaunchKernelGGL((k_cmvn<V, FORM, CMVN_FWD_RSTD>), grid, block, 0, st, a); break;
+        case CMVN_FWD_MEAN: hipLaunchKernelGGL((k_cmvn<V, FORM, CMVN_FWD_MEAN>), grid, block, 0, st, a); break;
+        case CMVN_BWD: hipLaunchKernelGGL((k_cmvn<V, FORM, CMVN_BWD>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_cmvn<V, FORM, CMVN_BWD_MEAN>), grid, block, 0, st, a); break;
+    }
+}
+
+static int run_cmvn(bool bwd, const float* x, const float* rstd, const float* gy, int64_t outer, int64_t frames, int64_t inner,
+                    int norm_vars, float eps, float* out, float* rstd_out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (outer < 0 || frames < 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/frames/inner");
+    if (norm_vars != 0 && norm_vars != 1) return fail(KPR_E_BADARG, "norm_vars must be 0 or 1, got %d", norm_vars);
+    if (!bwd && !(eps >= 0.0f && std::isfinite(eps))) return fail(KPR_E_BADARG, "eps must be finite and not negative");
+    if (rstd_out && !norm_vars) return fail(KPR_E_BADARG, "rstd_out needs norm_vars = 1 (there is no rstd without the variance)");
+    if (outer == 0 || frames == 0 || inner == 0) return 0;
+    if (!norm_vars && bwd) x = rstd = nullptr;                       // not read
+    if (!out || (!bwd && !x) || (bwd && (!gy || (norm_vars && (!x || !rstd)))))
+        return fail(KPR_E_BADARG, !bwd ? "x / out must not be NULL" : norm_vars ? "y / rstd / gy / gx must not be NULL"
+                                                                                : "gy / gx must not be NULL");
+    if (frames * inner > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "frames * inner = %lld elements per outer item: 2^31 or more is not supported",
+                    (long long)(frames * inner));
+    const uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)rstd | (uintptr_t)gy | (uintptr_t)rstd_out;
+    if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    {
+        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4, ns = (uintptr_t)outer * inner * 4;
+        auto clash = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+        };
+        bool bad = clash(out, nb, rstd_out, ns) || clash(out, nb, rstd, ns) || clash(rstd_out, ns, rstd, ns);
+        for (const float* in : {x, gy}) bad = bad || clash(out, nb, in, nb) || clash(rstd_out, ns, in, nb);
+        if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
+    }
+    const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
+    const bool res = frames <= kCmvnRows * kCmvnWaves && opt(OPT_CMVN_VARIANT) == 0;
+    CmvnArgs a;
+    a.x = x; a.gy = gy; a.rstd = rstd; a.out = out; a.rstd_out = rstd_out;
+    a.eps = eps;
+    a.frames = (int)frames;
+    a.inner = (unsigned)inner;
+    a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
+    a.n_groups = (long long)outer * a.groups_per_item;
+    const long long blocks = (a.n_groups + 63) / 64;
+    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
+    const dim3 grid((unsigned)blocks), block(64 * kCmvnWaves);
+    const int mode = bwd ? (norm_vars ? CMVN_BWD : CMVN_BWD_MEAN) : !norm_vars ? CMVN_FWD_MEAN : rstd_out ? CMVN_FWD_RSTD : CMVN_FWD;
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_cmvn%s<%d,%s>: grid %lld x %d lanes, %d rows per wave, %d waves per workgroup, resident up to %d "
+                "frames; %lld frames = %lld super-block(s), norm_vars %d%s\n", bwd ? "_bwd" : "", v4 ? 4 : 1, res ? "res" : "str", blocks,
+                64 * kCmvnWaves, kCmvnRows, kCmvnWaves, kCmvnRows * kCmvnWaves, (long long)frames,
+                (long long)((frames + kCmvnRows * kCmvnWaves - 1) / (kCmvnRows * kCmvnWaves)), norm_vars, rstd_out ? ", rstd kept" : "");
+    const hipStream_t st = (hipStream_t)stream;
+    if (v4) {
+        if (res) launch_cmvn<4, CMVN_RES>(mode, grid, block, st, a);
+        else launch_cmvn<4, CMVN_STR>(mode, grid, block, st, a);
+    } else {
+        if (res) launch_cmvn<1, CMVN_RES>(mode, grid, block, st, a);
+        else launch_cmvn<1, CMVN_STR>(mode, grid, block, st, a);
+    }
+    return launch_check(bwd ? "k_cmvn_bwd" : "k_cmvn", v4 ? 4 : 1, res ? "res" : "str");
 }
 
 // ---- Resample (kpr_resample_kernels.h): the windowed-sinc tables of both directions, the tile plan, the launch ----

@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN`` is this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN`` and ``CMVN`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -34,6 +34,7 @@ __all__ = [
     'Delta',
     'ConcatenateFrequencyMap',
     'PCEN',
+    'CMVN',
 ]
 
 
@@ -791,6 +792,45 @@ class PCEN(Layer):
         config.update({'eps': self.eps, 'data_format': self.data_format_original})
         if self._trainable_names:
             config['trainable_params'] = self.trainable_params
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class CMVN(Layer):
+    """Per-utterance mean and variance normalisation along time (Kaldi's ``apply-cmvn --norm-vars``, ESPnet's
+    ``UtteranceMVN``; instance normalisation over time), the step behind a log-mel spectrogram.  Per batch item, channel and
+    frequency band, over its n frames:
+
+        d[t] = x[t] - x[0];  m = mean(d);  c[t] = d[t] - m
+        y[t] = c[t] / sqrt(mean(c^2) + eps)    (``norm_vars=True``: population variance)
+        y[t] = c[t]                            (``norm_vars=False``: mean normalisation only)
+
+    ``norm_vars`` must be a bool and ``eps`` a finite number >= 0 (``ValueError`` at construction).  A constant series -- a band
+    clamped to the decibel floor -- gives exactly +0.0.  (b, t, f, ch) for ``channels_last``, (b, ch, t, f) for
+    ``channels_first``, same shape out; float32 (a float64 layer raises ``NotImplementedError``); one kernel
+    (kpr_cmvn_f32), one pass up to 128 frames, two reads of the input beyond.  No frames: an empty tensor, nothing is
+    launched.  No parameters; differentiable with respect to its input (one backward launch, kpr_cmvn_bwd_f32)."""
+
+    def __init__(self, norm_vars=True, eps=1e-5, data_format='default', **kwargs):
+        super(CMVN, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):
+            data_format = data_format['config']
+        self.norm_vars, self.eps = backend.cmvn_parameters(norm_vars, eps)
+        self.data_format_original = data_format
+        self.data_format = _resolve_format(data_format)
+
+    def compute_output_shape(self, input_shape):
+        return tuple(input_shape)
+
+    def call(self, x):
+        if self._f64:
+            raise NotImplementedError('CMVN has float32 kernels only; build the layer with dtype float32')
+        return backend._cmvn_run(x, self.norm_vars, self.eps, self.data_format)
+
+    def get_config(self):
+        config = super(CMVN, self).get_config()
+        config.update({'norm_vars': self.norm_vars, 'eps': self.eps, 'data_format': self.data_format_original})
         return config
 
 
