@@ -585,6 +585,55 @@ int kpr_resample_plan(int n_phases, int n_taps, int step, int* outputs_per_tile)
 int kpr_resample_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table_dev,
                      const int32_t* first_dev, int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream);
 
+/* ---- Griffin-Lim: magnitude spectrogram -> waveform, kapre_amd.time_frequency.GriffinLim ------------------------------
+ * Phase reconstruction by alternating projections (Griffin & Lim 1984) with the momentum term of the fast variant (Perraudin,
+ * Balazs & Sondergaard 2013), as librosa.griffinlim and torchaudio's GriffinLim run it, on this library's own transforms:
+ * A = kpr_stft_f32 without padding, A+ = kpr_istft_f32 (untrimmed: (F - 1) hop + win samples, whose analysis has F frames again).
+ * M: float32 (batch, frame, n_fft/2+1, ch) [LAST] or (batch, ch, frame, n_fft/2+1) [FIRST]; c = momentum / (1 + momentum):
+ *   mag = M^(1/power)  (power == 1: M itself, bit for bit);   S_0 = mag e^{i phi};   T_0 = 0
+ *   n = 1 .. n_iter:  R_n = A(A+(S_{n-1}));  sc_n = || |R_n| - mag || / || mag ||  per batch item;
+ *                     a = R_n - c T_{n-1};   S_n = mag a / (|a| + 1e-16);   T_n = R_n
+ *   y = A+(S_{n_iter})
+ * momentum == 0 is the classical algorithm: T is neither read nor stored.  mag == 0 gives S == 0.  A NaN stays inside its batch
+ * item, whose sc_n is NaN; an item with mag == 0 everywhere has sc_n = 0 / 0 = NaN too.  No float atomics: every sum has an order
+ * fixed by the shape, the same inputs give the same bits.
+ *
+ * kpr_griffin_lim_plan (host only): the tiling of the step -- an item of item_size elements (complex bins) is cut into
+ *   *chunks_per_item = ceil(item_size / *chunk_elems) equal parts, one workgroup each; seams for tests.
+ * kpr_gl_project_f32: the step alone.  R, T, S_out: complex64, mag: float32, n_items x item_size elements each, contiguous; T may
+ *   be NULL when c == 0 (it is then not read; c != 0 needs it); 0 <= c < 1.  S_out must not overlap an input.  sc_out (may be
+ *   NULL): n_items float32, sc of R against mag; it needs the workspace: 8 bytes per item and chunk, 8-byte aligned
+ *   (KPR_E_WORKSPACE).  R / T / S_out 8-byte, mag 4-byte aligned; 16-byte accesses when all four are 16-byte aligned.  One launch,
+ *   two with sc_out.  item_size < 2^31.
+ * kpr_gl_init_f32: mag and S_0 alone.  plane = frames * bins; M as above.  init_mode 0: phi = 0; 1: phi = 2 pi r 2^-32 with r
+ *   word (e mod 4) of Philox4x32-10 under key seed and counter (e div 4, calls), e being the element's index in the FIRST order
+ *   whatever the layout, and rng_state the 16-byte device state (uint64 seed, uint64 calls) of kpr_spec_augment_draw; a second
+ *   launch then stores calls + 1.  mag_out: receives mag when power != 1, NULL when power == 1 (KPR_E_BADARG otherwise).
+ *   S_out may be NULL (mag only; nothing is drawn).
+ * kpr_griffin_lim_workspace_bytes: the scratch of kpr_griffin_lim_f32 for that geometry (-1: bad geometry).  It holds S, one
+ *   buffer for R (two with momentum, alternating as R and T: T_n = R_n is a swap of pointers), mag when power != 1, the chunk sums
+ *   and the scratch of the two transforms.
+ * kpr_griffin_lim_f32: the whole run on `stream`: the init launch, per iteration the inverse transform, the forward transform,
+ *   the step and the convergence figure, then one last inverse -- the dispatch and the bits of the transforms are those of
+ *   kpr_istft_f32 / kpr_stft_f32 on the same tensors.  It never synchronises and copies nothing to the host.  g: batch, channels,
+ *   n_fft, win_length, hop_length; in_layout = layout of the waveform, out_layout = layout of M; time is ignored, pad_begin and
+ *   pad_end must be 0.  window / synth_window: win_length device floats, the forward window and its inverse_stft_window_fn
+ *   companion.  n_iter == 0: y = A+(S_0).  init_mode 0 / 1 as above; 2: S_0 = init, complex64 in M's layout, used as it is.
+ *   wave_out: (batch, (F-1) hop + win, ch) / (batch, ch, ...) float32; it also carries the waveform between the transforms.
+ *   sc_out (may be NULL): n_iter x batch float32 on the device.  workspace 16-byte aligned.  KPR_E_BADARG: n_iter < 0, momentum
+ *   outside [0, 1), power <= 0, bad init_mode or a missing init / rng_state, padding flags; a geometry that the transforms
+ *   refuse gives their error.  batch == 0 or n_frames == 0: returns 0, launches nothing. */
+int kpr_griffin_lim_plan(int64_t item_size, int* chunk_elems, int* chunks_per_item);
+int kpr_gl_project_f32(const void* R, const void* T /* may be NULL */, const float* mag, int64_t n_items, int64_t item_size, float c,
+                       void* S_out, float* sc_out /* may be NULL */, void* workspace, size_t workspace_bytes, kpr_stream_t stream);
+int kpr_gl_init_f32(const float* M, int64_t batch, int channels, int64_t plane, int layout, double power, int init_mode,
+                    void* rng_state, float* mag_out, void* S_out, kpr_stream_t stream);
+int64_t kpr_griffin_lim_workspace_bytes(const kpr_stft_geom* g, int64_t n_frames, int with_momentum, int with_power);
+int kpr_griffin_lim_f32(const float* mag, const kpr_stft_geom* g, int64_t n_frames, const float* window, const float* synth_window,
+                        int n_iter, double momentum, double power, int init_mode, const void* init /* init_mode 2 */,
+                        void* rng_state /* init_mode 1 */, float* wave_out, float* sc_out /* may be NULL; n_iter x batch */,
+                        void* workspace, size_t workspace_bytes, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

@@ -23,6 +23,7 @@ from .time_frequency import (
     ConcatenateFrequencyMap,
     PCEN,
     CMVN,
+    GriffinLim,
 )
 
 from . import signal
@@ -90,6 +91,7 @@ __all__ = [
     'ConcatenateFrequencyMap',
     'PCEN',
     'CMVN',
+    'GriffinLim',
     'Frame',
     'Energy',
     'MuLawEncoding',

@@ -188,6 +188,19 @@ EXPORTS = {
     "kpr_resample_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    # Griffin-Lim (kapre_amd/time_frequency.py)
+    "kpr_griffin_lim_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "kpr_gl_project_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]),
+    "kpr_gl_init_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "kpr_griffin_lim_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(StftGeom), ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "kpr_griffin_lim_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(StftGeom), ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -816,3 +829,68 @@ def resample(x, fmt, plan: ResamplePlan, out_len: int):
     _call("kpr_resample_f32", x.device, ptr(x), b, c, t, layout(fmt), ptr(plan.table), ptr(plan.first), plan.n_phases,
           plan.n_taps, plan.step, int(out_len), ptr(out))
     return out
+
+
+# Griffin-Lim (kapre_amd/time_frequency.py)
+GL_INIT_ZERO, GL_INIT_RANDOM, GL_INIT_GIVEN = 0, 1, 2
+
+
+def griffin_lim_plan(item_size: int):
+    """(chunk_elems, chunks_per_item): how kpr_gl_project_f32 cuts an item of ``item_size`` complex bins into workgroup
+    ranges (host only)."""
+    ch, n = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().kpr_griffin_lim_plan(int(item_size), ctypes.byref(ch), ctypes.byref(n)), "kpr_griffin_lim_plan")
+    return ch.value, n.value
+
+
+def gl_project(R, T, mag, c: float, want_sc: bool = False):
+    """One Griffin-Lim projection: S = mag a / (|a| + 1e-16) with a = R - c T (``T`` None: a = R, ``c`` must be 0).
+    ``R`` / ``T``: complex64, ``mag``: float32, the same shape, whose leading axis holds the items.  With ``want_sc``
+    returns (S, sc), sc per item being || |R| - mag || / || mag ||."""
+    import torch
+    n_items = int(R.shape[0]) if R.dim() > 0 else 1
+    item = R.numel() // max(n_items, 1)
+    S = torch.empty_like(R)
+    sc = torch.empty((n_items,), dtype=torch.float32, device=R.device) if want_sc else None
+    ws_bytes = 8 * n_items * griffin_lim_plan(item)[1] if want_sc else 0
+    ws = workspace(ws_bytes, R.device)
+    _call("kpr_gl_project_f32", R.device, ptr(R), ptr(T), ptr(mag), n_items, item, float(c), ptr(S), ptr(sc), ptr(ws), ws_bytes)
+    return (S, sc) if want_sc else S
+
+
+def gl_init(M, fmt, power: float, init_mode: int, state=None):
+    """(mag, S_0) of a Griffin-Lim run from the rank-4 float32 magnitude ``M``: mag = M^(1/power) (``M`` itself for power 1),
+    S_0 = mag with zero phase (GL_INIT_ZERO) or with the Philox phase drawn from the device generator ``state``
+    (GL_INIT_RANDOM; its ``calls`` advances by one)."""
+    import torch
+    b, c, f, k = dims_of(M.shape, fmt)
+    mag = torch.empty_like(M) if float(power) != 1.0 else None
+    S = torch.empty(M.shape, dtype=torch.complex64, device=M.device)
+    _call("kpr_gl_init_f32", M.device, ptr(M), b, c, f * k, layout(fmt), float(power), int(init_mode), ptr(state), ptr(mag), ptr(S))
+    return (M if mag is None else mag), S
+
+
+def griffin_lim_workspace_bytes(geom: StftGeom, n_frames: int, momentum: float, power: float) -> int:
+    n = int(lib().kpr_griffin_lim_workspace_bytes(ctypes.byref(geom), int(n_frames), int(momentum != 0), int(power != 1)))
+    if n < 0:
+        check(-1, "kpr_griffin_lim_workspace_bytes")
+    return n
+
+
+def griffin_lim(mag, window, synth_window, n_fft: int, win_length: int, hop_length: int, wave_fmt, spec_fmt, n_iter: int,
+                momentum: float, power: float, init_mode: int, init=None, state=None, want_sc: bool = True, ws=None):
+    """The whole Griffin-Lim run (kpr_griffin_lim_f32) on the rank-4 float32 magnitude ``mag``: (waveform, sc) with the
+    untrimmed waveform of (n_frames - 1) hop + win samples and sc the (n_iter, batch) device tensor of the convergence
+    figures (None without ``want_sc``).  ``ws``: a uint8 device tensor to use as scratch when it is large enough."""
+    import torch
+    b, c, f, _ = dims_of(mag.shape, spec_fmt)
+    g = StftGeom(b, c, 0, int(n_fft), int(win_length), int(hop_length), 0, 0, layout(wave_fmt), layout(spec_fmt))
+    t_out = (f - 1) * int(hop_length) + int(win_length) if f > 0 else 0
+    out = torch.empty(shape_of(wave_fmt, b, c, t_out), dtype=torch.float32, device=mag.device)
+    sc = torch.empty((int(n_iter), b), dtype=torch.float32, device=mag.device) if want_sc else None
+    ws_bytes = griffin_lim_workspace_bytes(g, f, momentum, power)
+    if ws is None or ws.numel() < ws_bytes:
+        ws = workspace(ws_bytes, mag.device)
+    _call("kpr_griffin_lim_f32", mag.device, ptr(mag), ctypes.byref(g), f, ptr(window), ptr(synth_window), int(n_iter),
+          float(momentum), float(power), int(init_mode), ptr(init), ptr(state), ptr(out), ptr(sc), ptr(ws), ws.numel())
+    return out, sc

@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn`` and ``resample`` have no counterpart there.
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn``, ``resample`` and ``griffin_lim`` have no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -535,3 +535,46 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_
         _RESAMPLE_SUPPORTED.add(params)
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return _resample_run(x, params, fmt)
+
+
+# --------------------------------------------------------------------------------------
+# Griffin-Lim
+# --------------------------------------------------------------------------------------
+def griffin_lim_parameters(n_iter, momentum, power):
+    """Validated (n_iter, momentum, power): an integer >= 0, 0 <= momentum < 1, power > 0 and finite (``ValueError``)."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError('GriffinLim: n_iter must be an integer >= 0, got %r' % (n_iter,))
+    for name, v in (('momentum', momentum), ('power', power)):
+        if isinstance(v, bool) or np.ndim(v) != 0 or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError('GriffinLim: %s must be a number, got %r' % (name, v))
+    if not 0.0 <= float(momentum) < 1.0:
+        raise ValueError('GriffinLim: 0 <= momentum < 1 is required, got %r' % (momentum,))
+    if not (float(power) > 0.0 and np.isfinite(float(power))):
+        raise ValueError('GriffinLim: power must be positive and finite, got %r' % (power,))
+    return int(n_iter), float(momentum), float(power)
+
+
+def griffin_lim(mag, n_fft=2048, win_length=None, hop_length=None, window_name=None, n_iter=32, momentum=0.99, power=1.0,
+                rand_init=True, length=None, input_data_format='default', output_data_format='default', init=None,
+                return_convergence=False):
+    """Griffin-Lim phase reconstruction of a magnitude spectrogram batch on the GPU (``kapre_amd.GriffinLim`` as a function):
+    (b, frame, n_fft // 2 + 1, ch) for ``channels_last``, (b, ch, frame, n_fft // 2 + 1) for ``channels_first``, float32 ->
+    the waveform (b, time, ch) / (b, ch, time) of (frame - 1) hop + win samples, or of ``length``.
+
+    ``init``: a complex64 spectrogram in ``mag``'s layout to start from instead of the zero or random phase (it is used as it
+    is, not projected).  With ``return_convergence`` returns (waveform, sc), sc being the (n_iter, batch) device tensor of
+    || |R_n| - mag || / || mag ||.  The result carries no ``grad_fn``: an input that requires grad is detached."""
+    from . import time_frequency
+
+    for data_format in (input_data_format, output_data_format):
+        validate_data_format_str(data_format)
+    n_iter, momentum, power = griffin_lim_parameters(n_iter, momentum, power)
+    if win_length is None:
+        win_length = n_fft
+    if hop_length is None:
+        hop_length = win_length // 4
+    resolve = lambda fmt: image_data_format() if fmt == _CH_DEFAULT_STR else fmt
+    wave, sc = time_frequency._griffin_lim_run(
+        mag, time_frequency._GL_CONSTS, int(n_fft), int(win_length), int(hop_length), window_name, get_window_fn(window_name),
+        n_iter, momentum, power, bool(rand_init), length, resolve(input_data_format), resolve(output_data_format), init)
+    return (wave, sc) if return_convergence else wave

@@ -36,8 +36,10 @@
 //                             registers up to 128 frames, two sweeps beyond
 //   kpr_resample_kernels.h    rational sample-rate conversion (signal.Resample): a polyphase gather over a staged input span,
 //                             forward and adjoint in one kernel
+//   kpr_griffin_lim_kernels.h Griffin-Lim phase reconstruction: the initial spectrum (zero or Philox phase), the projection onto the
+//                             given magnitude with the momentum term and the convergence sums, the per-item convergence figure
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
-// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h next to their kernel headers.
+// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h next to their kernel headers.
 // This file: the C ABI -- the extern "C" entry points, grouped as in include/kapre_hip.h.
 //
 // gfx950 only: wave64, v_mfma_f32_16x16x4_f32, 160 KiB LDS.  No CUDA/compat paths.
@@ -80,6 +82,7 @@
 #include "kpr_pcen_kernels.h"
 #include "kpr_cmvn_kernels.h"
 #include "kpr_resample_kernels.h"
+#include "kpr_griffin_lim_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -87,6 +90,7 @@
 #include "kpr_host_istft.h"
 #include "kpr_host_mel.h"
 #include "kpr_host_ops.h"
+#include "kpr_host_griffin_lim.h"
 
 // ==========================================================================================
 // C ABI
@@ -216,27 +220,7 @@ int64_t kpr_stft_workspace_bytes(const kpr_stft_geom* s, int mode) {
 int kpr_stft_f32(const float* x, const kpr_stft_geom* s, const float* window, void* out, int mode,
                  void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
     if (int e = api_enter()) return e;
-    if (int e = check_geom(s)) return e;
-    if (mode < 0 || mode > 2) return fail(KPR_E_BADARG, "bad output mode %d", mode);
-    const long long F = frames_of(s);
-    const kpr_stft_geom se = forward_geom(s);                    // win_length > n_fft: cropped frames (see forward_geom)
-    s = &se;
-    Geom g = make_geom(s, F);
-    if (g.total_frames == 0) return 0;
-    if (!x || !window || !out) return fail(KPR_E_BADARG, "x / window / out must not be NULL");
-    hipStream_t st = (hipStream_t)stream;
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
-    const StftRoute r = stft_route(s, g, mode, cus);
-    g.cfast = r.cfast;
-    if (r.fam != FAM_GEMM || mode == KPR_OUT_COMPLEX) return launch_stft(r, x, g, window, mode, out, cus, st);
-    if (!workspace || workspace_bytes < r.workspace)
-        return fail(KPR_E_WORKSPACE, "stft workspace: need %lld bytes", (long long)r.workspace);
-    if (int e = stft_gemm(x, g, window, (float*)workspace, st)) return e;
-    const long long n = g.total_frames * g.K;
-    hipLaunchKernelGGL(k_cplx_to_real, dim3(grid_1d(n, 256)), dim3(256), 0, st,
-                       (const float2*)workspace, n, mode == KPR_OUT_PHASE ? 1 : 0, (float*)out);
-    return launch_check("k_cplx_to_real");
+    return run_stft_f32(x, s, window, out, mode, workspace, workspace_bytes, stream);
 }
 
 int64_t kpr_mel_workspace_bytes(const kpr_stft_geom* s, int n_filt, const kpr_db_params* db) {
@@ -551,64 +535,7 @@ int kpr_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_frames,
                   const float* synth_window, float* out, void* workspace, int64_t workspace_bytes,
                   kpr_stream_t stream) {
     if (int e = api_enter()) return e;
-    if (int e = check_geom(s)) return e;
-    if (n_frames < 0) return fail(KPR_E_BADARG, "negative frame count");
-    Geom g = make_geom(s, n_frames);
-    g.pad_left = 0;
-    if (g.total_frames == 0) return 0;
-    if (!spec || !synth_window || !out) return fail(KPR_E_BADARG, "spec / window / out must not be NULL");
-    const int64_t need = kpr_istft_workspace_bytes(s, n_frames);
-    if (!workspace || workspace_bytes < need)
-        return fail(KPR_E_WORKSPACE, "istft workspace: need %lld bytes", (long long)need);
-    hipStream_t st = (hipStream_t)stream;
-    float* frames = reinterpret_cast<float*>(workspace);
-    int cus = 256;
-    if (int e = device_cus(&cus)) return e;
-    const IstftRoute r = istft_route(s, n_frames, g, out, cus);
-    const float2* sp = (const float2*)spec;
-    if (r.fam >= IST_PW) {
-        if (r.fam == IST_WS_MR) return launch_istft_ws_mr(sp, r, s->n_fft, synth_window, out, st);
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        return with_pow2(s->n_fft / 2, [&](auto nc) {
-            constexpr int NC = decltype(nc)::value;
-            if (r.fam == IST_WS) return launch_istft_ws<NC>(sp, r, synth_window, tw, out, st);
-            if (r.fam == IST_FUSED) return launch_istft_fused<NC, NC == 1024 ? 8 : 4>(sp, r, synth_window, tw, out, st);
-            if constexpr (NC >= 256) return launch_istft_pw<NC>(sp, r, synth_window, tw, out, st);
-            else return no_instance("k_istft_pw");
-        });
-    }
-    // two-kernel path: irFFT + synthesis window into the workspace, then the overlap-add
-    if (r.fam == FAM_POW2) {
-        const float2* tw = nullptr;
-        if (int e = get_twiddles(s->n_fft, &tw)) return e;
-        if (int e = with_pow2(s->n_fft / 2, [&](auto nc) { return launch_irfft_fast<nc>(sp, g, synth_window, tw, frames, st); }))
-            return e;
-    } else if (r.fam == FAM_MR) {     // n_fft with a mixed-radix plan: one N-point inverse FFT per frame
-        if (int e = launch_irfft_mr(sp, g, synth_window, frames, st)) return e;
-    } else if (r.fam == FAM_BS) {     // even non-power-of-two n_fft: inverse chirp-z, then the gather
-        if (int e = launch_irfft_bs(sp, g, synth_window, frames, st)) return e;
-    } else if (r.fam == FAM_BIG) {    // 4096 / 8192: sub-FFT kernel, then the gather
-        if (int e = launch_irfft_big(sp, g, synth_window, frames, st)) return e;
-    } else if (r.fam == FAM_GEN) {    // small prime factors: run-time mixed-radix inverse FFT, then the gather
-        if (int e = launch_irfft_gen_f32(sp, g, synth_window, frames, st)) return e;
-    } else {
-        const float* idft = nullptr;
-        if (int e = get_dft_inv(s->n_fft, &idft)) return e;
-        GemmArgs ga{};
-        ga.in = frames_out_map(g, g.K);          // spectrum in the caller's layout (complex units)
-        ga.out = frames_contig_map(g, g.win);
-        ga.Kdim = 2 * g.K; ga.N = std::min(g.n_fft, g.win); ga.ldb = g.n_fft;
-        ga.window = synth_window; ga.win = g.win;
-        if (int e = run_gemm<A_CPLX, E_WINDOW>((const float*)spec, idft, ga, frames, st)) return e;
-        if (g.win > g.n_fft) {
-            hipLaunchKernelGGL(k_fill_cols, dim3(grid_1d(g.total_frames * (g.win - g.n_fft), 256)),
-                               dim3(256), 0, st, frames, g.total_frames, (long long)g.win, g.n_fft,
-                               g.win);
-            if (int e = launch_check("k_fill_cols")) return e;
-        }
-    }
-    return run_ola<float>(frames, s, n_frames, s->in_layout == KPR_CHANNELS_LAST, out, st);
+    return run_istft_f32(spec, s, n_frames, synth_window, out, workspace, workspace_bytes, stream);
 }
 
 /* ---- float64 / complex128 variants -------------------------------------------------------------- */
@@ -1038,6 +965,38 @@ int kpr_resample_plan(int n_phases, int n_taps, int step, int* outputs_per_tile)
 int kpr_resample_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table_dev,
                      const int32_t* first_dev, int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream) {
     return run_resample(x, batch, channels, in_len, layout, table_dev, first_dev, n_phases, n_taps, step, out_len, out, stream);
+}
+
+/* ---- Griffin-Lim (kpr_griffin_lim_kernels.h) ---------------------------------------------------- */
+int kpr_griffin_lim_plan(int64_t item_size, int* chunk_elems, int* chunks_per_item) {
+    if (item_size < 0 || !chunk_elems || !chunks_per_item) return fail(KPR_E_BADARG, "bad item_size or NULL result");
+    *chunk_elems = kGlChunk;
+    if (item_size > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "item_size = %lld elements: 2^31 or more is not supported", (long long)item_size);
+    *chunks_per_item = (int)gl_chunks(item_size);
+    return 0;
+}
+int kpr_gl_project_f32(const void* R, const void* T, const float* mag, int64_t n_items, int64_t item_size, float c, void* S_out,
+                       float* sc_out, void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_gl_project(R, T, mag, n_items, item_size, c, S_out, sc_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int kpr_gl_init_f32(const float* M, int64_t batch, int channels, int64_t plane, int layout, double power, int init_mode,
+                    void* rng_state, float* mag_out, void* S_out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_gl_init(M, batch, channels, plane, layout, power, init_mode, rng_state, mag_out, S_out, (hipStream_t)stream);
+}
+int64_t kpr_griffin_lim_workspace_bytes(const kpr_stft_geom* g, int64_t n_frames, int with_momentum, int with_power) {
+    kpr_stft_geom fwd;
+    GlLayout l;
+    if (gl_layout(g, n_frames, with_momentum != 0, with_power != 0, &fwd, &l)) return -1;
+    return (int64_t)l.total;
+}
+int kpr_griffin_lim_f32(const float* mag, const kpr_stft_geom* g, int64_t n_frames, const float* window, const float* synth_window,
+                        int n_iter, double momentum, double power, int init_mode, const void* init, void* rng_state, float* wave_out,
+                        float* sc_out, void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_griffin_lim(mag, g, n_frames, window, synth_window, n_iter, momentum, power, init_mode, init, rng_state, wave_out, sc_out,
+                           workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

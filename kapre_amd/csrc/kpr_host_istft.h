@@ -1,6 +1,6 @@
 // kpr_host_istft.h -- host side of kpr_istft_kernels.h / kpr_istft_pw_kernels.h (and of the inverse kernel of kpr_generic_kernels.h):
 // the plans and launchers of the one-launch inverse kernels, the inverse-FFT launchers of the two-kernel path, IstftRoute /
-// istft_route, the overlap-add tail.
+// istft_route, the overlap-add tail, and run_istft_f32, the body of kpr_istft_f32.
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_stft.h; not stand-alone).
 #pragma once
 
@@ -394,6 +394,69 @@ static IstftRoute istft_route(const kpr_stft_geom* s, long long F, const Geom& g
     if (!fast_nfft(s->n_fft) && path != 2 && istft_ws_mr_plan(s, F, out, cus, &r)) return r;
     r.fam = fft_family(s);
     return r;
+}
+
+// ---- kpr_istft_f32 behind api_enter: checks, route, launch (kpr_griffin_lim_f32 runs it once per iteration) ----
+static int run_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_frames, const float* synth_window, float* out,
+                         void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = check_geom(s)) return e;
+    if (n_frames < 0) return fail(KPR_E_BADARG, "negative frame count");
+    Geom g = make_geom(s, n_frames);
+    g.pad_left = 0;
+    if (g.total_frames == 0) return 0;
+    if (!spec || !synth_window || !out) return fail(KPR_E_BADARG, "spec / window / out must not be NULL");
+    const int64_t need = kpr_istft_workspace_bytes(s, n_frames);
+    if (!workspace || workspace_bytes < need)
+        return fail(KPR_E_WORKSPACE, "istft workspace: need %lld bytes", (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    float* frames = reinterpret_cast<float*>(workspace);
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const IstftRoute r = istft_route(s, n_frames, g, out, cus);
+    const float2* sp = (const float2*)spec;
+    if (r.fam >= IST_PW) {
+        if (r.fam == IST_WS_MR) return launch_istft_ws_mr(sp, r, s->n_fft, synth_window, out, st);
+        const float2* tw = nullptr;
+        if (int e = get_twiddles(s->n_fft, &tw)) return e;
+        return with_pow2(s->n_fft / 2, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            if (r.fam == IST_WS) return launch_istft_ws<NC>(sp, r, synth_window, tw, out, st);
+            if (r.fam == IST_FUSED) return launch_istft_fused<NC, NC == 1024 ? 8 : 4>(sp, r, synth_window, tw, out, st);
+            if constexpr (NC >= 256) return launch_istft_pw<NC>(sp, r, synth_window, tw, out, st);
+            else return no_instance("k_istft_pw");
+        });
+    }
+    // two-kernel path: irFFT + synthesis window into the workspace, then the overlap-add
+    if (r.fam == FAM_POW2) {
+        const float2* tw = nullptr;
+        if (int e = get_twiddles(s->n_fft, &tw)) return e;
+        if (int e = with_pow2(s->n_fft / 2, [&](auto nc) { return launch_irfft_fast<nc>(sp, g, synth_window, tw, frames, st); }))
+            return e;
+    } else if (r.fam == FAM_MR) {     // n_fft with a mixed-radix plan: one N-point inverse FFT per frame
+        if (int e = launch_irfft_mr(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_BS) {     // even non-power-of-two n_fft: inverse chirp-z, then the gather
+        if (int e = launch_irfft_bs(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_BIG) {    // 4096 / 8192: sub-FFT kernel, then the gather
+        if (int e = launch_irfft_big(sp, g, synth_window, frames, st)) return e;
+    } else if (r.fam == FAM_GEN) {    // small prime factors: run-time mixed-radix inverse FFT, then the gather
+        if (int e = launch_irfft_gen_f32(sp, g, synth_window, frames, st)) return e;
+    } else {
+        const float* idft = nullptr;
+        if (int e = get_dft_inv(s->n_fft, &idft)) return e;
+        GemmArgs ga{};
+        ga.in = frames_out_map(g, g.K);          // spectrum in the caller's layout (complex units)
+        ga.out = frames_contig_map(g, g.win);
+        ga.Kdim = 2 * g.K; ga.N = std::min(g.n_fft, g.win); ga.ldb = g.n_fft;
+        ga.window = synth_window; ga.win = g.win;
+        if (int e = run_gemm<A_CPLX, E_WINDOW>((const float*)spec, idft, ga, frames, st)) return e;
+        if (g.win > g.n_fft) {
+            hipLaunchKernelGGL(k_fill_cols, dim3(grid_1d(g.total_frames * (g.win - g.n_fft), 256)),
+                               dim3(256), 0, st, frames, g.total_frames, (long long)g.win, g.n_fft,
+                               g.win);
+            if (int e = launch_check("k_fill_cols")) return e;
+        }
+    }
+    return run_ola<float>(frames, s, n_frames, s->in_layout == KPR_CHANNELS_LAST, out, st);
 }
 
 }  // namespace kpr

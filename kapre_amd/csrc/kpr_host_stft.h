@@ -1,5 +1,6 @@
 // kpr_host_stft.h -- host side of kpr_stft_kernels.h (and of the forward kernel of kpr_generic_kernels.h): the DFT-as-GEMM forward
-// transform, the launchers of every forward FFT family, stft_pow2_kernel, StftRoute / stft_route, launch_stft.
+// transform, the launchers of every forward FFT family, stft_pow2_kernel, StftRoute / stft_route, launch_stft, and run_stft_f32,
+// the body of kpr_stft_f32.
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_fft.h; not stand-alone).
 #pragma once
 
@@ -215,6 +216,32 @@ static int launch_stft(const StftRoute& r, const float* x, const Geom& g, const 
         case FAM_GEN: return launch_stft_gen_f32(x, g, window, mode, out, st);
         default:      return stft_gemm(x, g, window, (float*)out, st);
     }
+}
+
+// ---- kpr_stft_f32 behind api_enter: checks, route, launch (kpr_griffin_lim_f32 runs it once per iteration) ----
+static int run_stft_f32(const float* x, const kpr_stft_geom* s, const float* window, void* out, int mode,
+                        void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = check_geom(s)) return e;
+    if (mode < 0 || mode > 2) return fail(KPR_E_BADARG, "bad output mode %d", mode);
+    const long long F = frames_of(s);
+    const kpr_stft_geom se = forward_geom(s);                    // win_length > n_fft: cropped frames (see forward_geom)
+    s = &se;
+    Geom g = make_geom(s, F);
+    if (g.total_frames == 0) return 0;
+    if (!x || !window || !out) return fail(KPR_E_BADARG, "x / window / out must not be NULL");
+    hipStream_t st = (hipStream_t)stream;
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const StftRoute r = stft_route(s, g, mode, cus);
+    g.cfast = r.cfast;
+    if (r.fam != FAM_GEMM || mode == KPR_OUT_COMPLEX) return launch_stft(r, x, g, window, mode, out, cus, st);
+    if (!workspace || workspace_bytes < r.workspace)
+        return fail(KPR_E_WORKSPACE, "stft workspace: need %lld bytes", (long long)r.workspace);
+    if (int e = stft_gemm(x, g, window, (float*)workspace, st)) return e;
+    const long long n = g.total_frames * g.K;
+    hipLaunchKernelGGL(k_cplx_to_real, dim3(grid_1d(n, 256)), dim3(256), 0, st,
+                       (const float2*)workspace, n, mode == KPR_OUT_PHASE ? 1 : 0, (float*)out);
+    return launch_check("k_cplx_to_real");
 }
 
 }  // namespace kpr

@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN`` and ``CMVN`` are this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN`` and ``GriffinLim`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -35,6 +35,7 @@ __all__ = [
     'ConcatenateFrequencyMap',
     'PCEN',
     'CMVN',
+    'GriffinLim',
 ]
 
 
@@ -831,6 +832,147 @@ class CMVN(Layer):
     def get_config(self):
         config = super(CMVN, self).get_config()
         config.update({'norm_vars': self.norm_vars, 'eps': self.eps, 'data_format': self.data_format_original})
+        return config
+
+
+_GL_CONSTS = _DeviceConstants()          # the windows of backend.griffin_lim (the layer keeps its own)
+
+
+def _griffin_lim_run(x, consts, n_fft, win_length, hop_length, window_name, window_fn, n_iter, momentum, power, rand_init,
+                     length, spec_fmt, wave_fmt, init=None):
+    """(waveform, sc) of one Griffin-Lim run on ``x`` in resolved data formats; the windows come from ``consts`` and the
+    scratch from the workspace pool of the current stream."""
+    import torch
+
+    from .augmentation import device_state
+    if len(x.shape) != 4:
+        raise ValueError('GriffinLim expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('GriffinLim has float32 kernels only; got a float64 input (cast it to float32)')
+    if isinstance(x, torch.Tensor):
+        x = x.detach()
+    x = _ffi.as_device(x, torch.float32)
+    k = _ffi.dims_of(x.shape, spec_fmt)[3]
+    if k != n_fft // 2 + 1:
+        raise ValueError('GriffinLim: the frequency axis has %d bins, n_fft = %d needs %d' % (k, n_fft, n_fft // 2 + 1))
+    if init is not None:
+        if isinstance(init, torch.Tensor):
+            init = init.detach()
+        init = _ffi.as_device(init, torch.complex64)
+        if tuple(init.shape) != tuple(x.shape) or init.device != x.device:
+            raise ValueError('GriffinLim: init must have the shape %s of the magnitude and live on its device, got %s on %s'
+                             % (tuple(x.shape), tuple(init.shape), init.device))
+    synth_fn = backend.inverse_stft_window_fn(frame_step=hop_length, forward_window_fn=window_fn)
+    key = (window_name if isinstance(window_name, str) or window_name is None else id(window_fn), win_length, hop_length)
+    win = consts.get(('gl_window',) + key, x.device, lambda: window_fn(win_length))
+    synth = consts.get(('gl_synth',) + key, x.device, lambda: synth_fn(win_length))
+    mode = _ffi.GL_INIT_GIVEN if init is not None else _ffi.GL_INIT_RANDOM if rand_init else _ffi.GL_INIT_ZERO
+    state = device_state(x.device) if mode == _ffi.GL_INIT_RANDOM and x.numel() > 0 else None
+    b, c, f, _ = _ffi.dims_of(x.shape, spec_fmt)
+    g = _ffi.StftGeom(b, c, 0, n_fft, win_length, hop_length, 0, 0, _ffi.layout(wave_fmt), _ffi.layout(spec_fmt))
+    ws_bytes = _ffi.griffin_lim_workspace_bytes(g, f, momentum, power)
+    ws = _PLAN_WORKSPACES.get(ws_bytes, x.device, torch.cuda.current_stream(x.device).cuda_stream)
+    wave, sc = _ffi.griffin_lim(x, win, synth, n_fft, win_length, hop_length, wave_fmt, spec_fmt, n_iter, momentum, power, mode,
+                                init, state, True, ws)
+    if length is not None:
+        axis = 1 if wave_fmt == _CH_LAST_STR else 2
+        t = wave.shape[axis]
+        if length < t:
+            wave = wave.narrow(axis, 0, int(length)).contiguous()
+        elif length > t:
+            wave = torch.nn.functional.pad(wave, [0, 0, 0, int(length) - t] if axis == 1 else [0, int(length) - t])
+    return wave, sc
+
+
+@register_keras_serializable(package='Kapre')
+class GriffinLim(Layer):
+    """Griffin-Lim phase reconstruction: a magnitude spectrogram back to a waveform (Griffin & Lim 1984, with the momentum
+    term of Perraudin, Balazs & Sondergaard 2013 -- the algorithm of ``librosa.griffinlim`` and torchaudio's ``GriffinLim``),
+    the inverse direction behind ``get_stft_magnitude_layer(return_decibel=False)``.  With A this package's ``STFT(n_fft,
+    win_length, hop_length, window_name)`` without padding, A+ its ``InverseSTFT(..., forward_window_name=window_name)`` and
+    c = momentum / (1 + momentum):
+
+        mag = x ** (1 / power);  S_0 = mag e^{i phi}  (phi random with ``rand_init``, else 0);  T_0 = 0
+        n = 1 .. n_iter:  R = A(A+(S));  a = R - c T;  S = mag a / (|a| + 1e-16);  T = R
+        y = A+(S)
+
+    Framing is tf.signal's (not centred), as in the two transforms.  Input (b, frame, n_fft // 2 + 1, ch) for
+    ``channels_last``, (b, ch, frame, n_fft // 2 + 1) for ``channels_first``, float32 and not negative; output (b, time, ch) /
+    (b, ch, time) with (frame - 1) hop + win samples, or exactly ``length`` (trimmed, or padded with zeros).  ``momentum = 0``
+    is the classical algorithm; ``n_iter = 0`` is one inverse transform of S_0.  ``n_iter < 0``, ``momentum`` outside [0, 1)
+    and ``power <= 0`` raise ``ValueError``, a float64 input ``TypeError``.
+
+    The whole run stays on the device: one call of kpr_griffin_lim_f32 queues every launch on the current stream, waits for
+    nothing and copies nothing to the host.  The random phase comes from SpecAugment's device generator
+    (``augmentation.set_seed`` makes runs repeatable; every call with ``rand_init`` advances it by one).  After a call
+    ``last_convergence`` is the device tensor (n_iter, batch) of || |R_n| - mag || / || mag || per batch item.
+
+    The output carries no ``grad_fn``: the layer is not differentiable, and an input that requires grad is detached."""
+
+    def __init__(self, n_fft=2048, win_length=None, hop_length=None, window_name=None, n_iter=32, momentum=0.99, power=1.0,
+                 rand_init=True, length=None, input_data_format='default', output_data_format='default', **kwargs):
+        super(GriffinLim, self).__init__(**kwargs)
+        for data_format in (input_data_format, output_data_format):
+            backend.validate_data_format_str(data_format)
+        if isinstance(input_data_format, dict):
+            input_data_format = input_data_format['config']
+        if isinstance(output_data_format, dict):
+            output_data_format = output_data_format['config']
+        if win_length is None:
+            win_length = n_fft
+        if hop_length is None:
+            hop_length = win_length // 4
+        self.n_iter, self.momentum, self.power = backend.griffin_lim_parameters(n_iter, momentum, power)
+        if length is not None and (isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0):
+            raise ValueError('GriffinLim: length must be None or an integer >= 0, got %r' % (length,))
+        self.n_fft = n_fft
+        self.win_length = win_length
+        self.hop_length = hop_length
+        self.window_name = window_name
+        self.window_fn = backend.get_window_fn(window_name)   # NotImplementedError if unknown
+        self.rand_init = bool(rand_init)
+        self.length = None if length is None else int(length)
+        self.input_data_format_original = input_data_format
+        self.output_data_format_original = output_data_format
+        self.input_data_format = _resolve_format(input_data_format)
+        self.output_data_format = _resolve_format(output_data_format)
+        self._consts = _DeviceConstants()
+        self.last_convergence = None
+
+    def compute_output_shape(self, input_shape):
+        """(b, frame, freq, ch) / (b, ch, frame, freq) -> (b, t, ch) / (b, ch, t), t = ``length`` or (frame - 1) hop + win"""
+        b, c, f, _ = _ffi.dims_of(input_shape, self.input_data_format)
+        if self.length is not None:
+            t = self.length
+        else:
+            t = None if f is None else ((int(f) - 1) * int(self.hop_length) + int(self.win_length) if int(f) > 0 else 0)
+        return _ffi.shape_of(self.output_data_format, b, c, t)
+
+    def call(self, x):
+        if self._f64:
+            raise TypeError('GriffinLim has float32 kernels only; build the layer with dtype float32')
+        wave, self.last_convergence = _griffin_lim_run(
+            x, self._consts, int(self.n_fft), int(self.win_length), int(self.hop_length), self.window_name, self.window_fn,
+            self.n_iter, self.momentum, self.power, self.rand_init, self.length, self.input_data_format, self.output_data_format)
+        return wave
+
+    def get_config(self):
+        config = super(GriffinLim, self).get_config()
+        config.update(
+            {
+                'n_fft': self.n_fft,
+                'win_length': self.win_length,
+                'hop_length': self.hop_length,
+                'window_name': self.window_name,
+                'n_iter': self.n_iter,
+                'momentum': self.momentum,
+                'power': self.power,
+                'rand_init': self.rand_init,
+                'length': self.length,
+                'input_data_format': self.input_data_format_original,
+                'output_data_format': self.output_data_format_original,
+            }
+        )
         return config
 
 
