@@ -634,6 +634,34 @@ int kpr_griffin_lim_f32(const float* mag, const kpr_stft_geom* g, int64_t n_fram
                         void* rng_state /* init_mode 1 */, float* wave_out, float* sc_out /* may be NULL; n_iter x batch */,
                         void* workspace, size_t workspace_bytes, kpr_stream_t stream);
 
+/* ---- TimeStretch: phase-vocoder time stretching of a complex spectrogram, kapre_amd.time_frequency.TimeStretch ---------
+ * x: complex64 (outer, frames_in, inner), contiguous -> out: (outer, frames_out, inner).  channels_first: outer = batch * ch,
+ * inner = freq; channels_last: outer = batch, inner = freq * ch.  idx (int32) and alpha (float32): frames_out DEVICE entries, the
+ * floor and the fraction of t * rate (the caller computes them in float64; the library never reads them on the host).  Output
+ * frame t reads the rows i = idx[t] and i + 1; a row >= frames_in (the two padding frames; any index that is no row) reads as
+ * zero, so idx[t] + 1 <= frames_in + 1 is the caller's contract and nothing outside x is touched whatever the table holds.
+ *   Theta(x) = 2 rint(atan2f(im, re) c) as a uint32, 2^32 = one turn, c = float32(2^30 / pi); 0 for re == im == 0 (any signs),
+ *              for a padding row and for a non-finite bin
+ *   P[0] = Theta(X[0]);   P[t + 1] = P[t] + Theta(X[i + 1]) - Theta(X[i])      (uint32: the sum wraps by itself and is exact)
+ *   m[t] = alpha[t] |X[i + 1]| + (1 - alpha[t]) |X[i]|,   |x| = sqrtf(re re + im im)
+ *   out[t] = m[t] (cos, sin)(pi h),   h = (float)(int32)P[t] 2^-31
+ * This is the phase vocoder of torchaudio.functional.phase_vocoder / librosa.phase_vocoder: the expected phase advance of a bin
+ * enters the accumulated phase as a whole number of turns, so there is no hop length here.  With idx[t] = t and alpha = 0
+ * P[t] = Theta(X[t]): the input comes back up to rounding.  A non-finite bin makes non-finite only the frames that read it; every
+ * other frame is bit for bit what it would be with that bin set to 0.  The same inputs give the same bits: no atomics, and
+ * integer addition does not care about the order.
+ * phase_out (may be NULL): receives P, (outer, frames_out, inner) uint32.  x / out 8-byte, idx / alpha / phase_out 4-byte aligned;
+ * 16-byte accesses when inner is even, x and out are 16-byte and phase_out is 8-byte aligned.  x == out or any overlap of an
+ * output with an input: KPR_E_BADARG.  frames_in * inner or frames_out * inner >= 2^30: KPR_E_UNSUPPORTED.  outer, frames_out or
+ * inner == 0: returns 0, launches nothing.  One launch, no host reads: capturable.
+ * kpr_time_stretch_plan (host only): the time tiling of the dispatch, the same for every shape -- a workgroup of
+ * *waves_per_group waves covers *waves_per_group * *rows_per_wave consecutive output frames per step, *rows_per_wave per wave;
+ * chunk boundaries for tests. */
+int kpr_time_stretch_plan(int64_t frames_out, int64_t inner, int* rows_per_wave, int* waves_per_group);
+int kpr_time_stretch_c64(const void* x, int64_t outer, int64_t frames_in, int64_t frames_out, int64_t inner, const int32_t* idx,
+                         const float* alpha, void* out, uint32_t* phase_out /* may be NULL: (outer, frames_out, inner) phase words */,
+                         kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

@@ -24,6 +24,7 @@ from .time_frequency import (
     PCEN,
     CMVN,
     GriffinLim,
+    TimeStretch,
 )
 
 from . import signal
@@ -38,6 +39,7 @@ from .composed import (
     get_log_frequency_spectrogram_layer,
     get_perfectly_reconstructing_stft_istft,
     get_stft_mag_phase,
+    get_time_stretch_layer,
 )
 
 
@@ -92,6 +94,7 @@ __all__ = [
     'PCEN',
     'CMVN',
     'GriffinLim',
+    'TimeStretch',
     'Frame',
     'Energy',
     'MuLawEncoding',
@@ -105,6 +108,7 @@ __all__ = [
     'get_log_frequency_spectrogram_layer',
     'get_perfectly_reconstructing_stft_istft',
     'get_stft_mag_phase',
+    'get_time_stretch_layer',
     'Layer',
     'Sequential',
     'Model',

@@ -201,6 +201,11 @@ EXPORTS = {
                                            ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_size_t, ctypes.c_void_p]),
+    # TimeStretch (kapre_amd/time_frequency.py)
+    "kpr_time_stretch_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
+                                             ctypes.POINTER(ctypes.c_int)]),
+    "kpr_time_stretch_c64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -894,3 +899,26 @@ def griffin_lim(mag, window, synth_window, n_fft: int, win_length: int, hop_leng
     _call("kpr_griffin_lim_f32", mag.device, ptr(mag), ctypes.byref(g), f, ptr(window), ptr(synth_window), int(n_iter),
           float(momentum), float(power), int(init_mode), ptr(init), ptr(state), ptr(out), ptr(sc), ptr(ws), ws.numel())
     return out, sc
+
+
+# TimeStretch (kapre_amd/time_frequency.py)
+def time_stretch_plan(frames_out: int, inner: int):
+    """(rows_per_wave, waves_per_group): the time tiling kpr_time_stretch_c64 uses (host only)."""
+    rows, waves = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().kpr_time_stretch_plan(int(frames_out), int(inner), ctypes.byref(rows), ctypes.byref(waves)),
+          "kpr_time_stretch_plan")
+    return rows.value, waves.value
+
+
+def time_stretch(x, fmt, idx, alpha, frames_out: int, want_phase: bool = False):
+    """Phase-vocoder time stretch of the rank-4 complex64 ``x`` along its frame axis: ``frames_out`` frames, output frame t read
+    from the input rows idx[t] and idx[t] + 1 with the weight alpha[t] (int32 / float32 device tensors of ``frames_out``
+    entries).  With ``want_phase`` returns (out, phase), phase being the uint32 phase words in out's layout (as an int32
+    tensor)."""
+    import torch
+    b, c, t, m = dims_of(x.shape, fmt)
+    outer, inner = (b, m * c) if fmt in ("channels_last", CHANNELS_LAST) else (b * c, m)
+    out = torch.empty(shape_of(fmt, b, c, int(frames_out), m), dtype=torch.complex64, device=x.device)
+    phase = torch.empty(out.shape, dtype=torch.int32, device=x.device) if want_phase else None
+    _call("kpr_time_stretch_c64", x.device, ptr(x), outer, t, int(frames_out), inner, ptr(idx), ptr(alpha), ptr(out), ptr(phase))
+    return (out, phase) if want_phase else out

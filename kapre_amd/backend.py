@@ -578,3 +578,60 @@ def griffin_lim(mag, n_fft=2048, win_length=None, hop_length=None, window_name=N
         mag, time_frequency._GL_CONSTS, int(n_fft), int(win_length), int(hop_length), window_name, get_window_fn(window_name),
         n_iter, momentum, power, bool(rand_init), length, resolve(input_data_format), resolve(output_data_format), init)
     return (wave, sc) if return_convergence else wave
+
+
+# --------------------------------------------------------------------------------------
+# time stretching (phase vocoder)
+# --------------------------------------------------------------------------------------
+def time_stretch_parameters(rate):
+    """Validated rate: a finite number > 0, not a bool (``ValueError``); returned as a float."""
+    if isinstance(rate, (bool, np.bool_)) or np.ndim(rate) != 0 or not isinstance(rate, (int, float, np.integer, np.floating)):
+        raise ValueError('TimeStretch: rate must be a number > 0, got %r' % (rate,))
+    if not (np.isfinite(float(rate)) and float(rate) > 0.0):
+        raise ValueError('TimeStretch: rate must be finite and > 0, got %r' % (rate,))
+    return float(rate)
+
+
+def time_stretch_length(frames, rate: float):
+    """Output frames of ``frames`` input frames at ``rate``: ceil(frames / rate), taken as the number of t >= 0 whose float64
+    product t * rate is below ``frames`` -- the last output frame then starts at an input frame that exists, whatever the
+    division would round to.  ``None`` stays ``None``."""
+    if frames is None:
+        return None
+    frames, rate = int(frames), float(rate)
+    if frames <= 0:
+        return 0
+    n = max(int(np.ceil(frames / rate)), 1)
+    while n > 1 and np.floor((n - 1) * rate) > frames - 1:
+        n -= 1
+    while np.floor(n * rate) <= frames - 1:
+        n += 1
+    return n
+
+
+def time_stretch_table(frames, rate):
+    """(idx, alpha) of a time stretch of ``frames`` input frames: for output frame t, s = t * float64(rate), idx[t] = floor(s)
+    (int32) and alpha[t] = s - idx[t] (float32, kept below 1); ``time_stretch_length(frames, rate)`` entries."""
+    rate = time_stretch_parameters(rate)
+    n = time_stretch_length(frames, rate)
+    s = np.arange(n, dtype=np.float64) * rate
+    fl = np.floor(s)
+    if n and fl[-1] >= 2.0 ** 31 - 2:
+        raise ValueError('TimeStretch: %d frames at rate %r: frame indices of 2^31 and more are not supported' % (frames, rate))
+    alpha = np.minimum((s - fl).astype(np.float32), np.nextafter(np.float32(1.0), np.float32(0.0)))
+    return fl.astype(np.int32), alpha
+
+
+def phase_vocoder(x, rate, data_format='default'):
+    """Phase-vocoder time stretch of a complex spectrogram batch on the GPU (``kapre_amd.TimeStretch`` as a function; the
+    operation of ``torchaudio.functional.phase_vocoder`` and ``librosa.phase_vocoder``): (b, frame, freq, ch) for
+    ``channels_last``, (b, ch, frame, freq) for ``channels_first``, complex64 in and out, ceil(frame / rate) frames.  ``rate`` < 1
+    slows the signal down, > 1 speeds it up.  There is no ``hop_length``: the expected phase advance of a bin changes the
+    accumulated phase by whole turns only (see ``TimeStretch``).  One kernel launch.  The result carries no ``grad_fn``: an
+    input that requires grad is detached."""
+    from . import time_frequency
+
+    validate_data_format_str(data_format)
+    rate = time_stretch_parameters(rate)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return time_frequency._time_stretch_run(x, rate, fmt, time_frequency._TS_CONSTS)

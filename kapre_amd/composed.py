@@ -3,7 +3,7 @@
 ``get_stft_magnitude_layer`` (composed.py:32-135), ``get_melspectrogram_layer`` (:138-261),
 ``get_log_frequency_spectrogram_layer`` (:264-385), ``get_perfectly_reconstructing_stft_istft``
 (:388-417), ``get_stft_mag_phase`` (:420-511): same signatures, defaults and layer order as the
-reference.  The returned ``Sequential`` exposes the individual layers through ``.layers`` (users
+reference; ``get_time_stretch_layer`` is this package's own.  The returned ``Sequential`` exposes the individual layers through ``.layers`` (users
 may re-add them to their own model, composed.py:1-13) and, when called, runs the whole chain as a
 single fused HIP launch (kapre_amd.time_frequency.fuse_and_run).
 
@@ -19,6 +19,7 @@ from .time_frequency import (
     Phase,
     MagnitudeToDecibel,
     ApplyFilterbank,
+    TimeStretch,
 )
 from . import backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
@@ -167,6 +168,35 @@ def get_perfectly_reconstructing_stft_istft(
     synthesis = InverseSTFT(forward_window_name='hann_window', input_data_format=stft_data_format,
                             output_data_format=waveform_data_format, name=istft_name, **shared)
     return analysis, synthesis
+
+
+def get_time_stretch_layer(
+    rate,
+    n_fft=2048,
+    hop_length=None,
+    input_shape=None,
+    input_data_format='default',
+    name='time_stretch',
+):
+    """``Sequential([STFT, TimeStretch, InverseSTFT])``: a waveform batch in, the waveform at 1 / ``rate`` of its duration and
+    the same pitch out, in ``input_data_format`` (this package's own; the chain of ``torchaudio.transforms.TimeStretch``).  Hann
+    window, ``win_length = n_fft``, ``hop_length`` defaulting to ``n_fft // 4``, no padding, the matched synthesis window.
+    F analysis frames give ``(ceil(F / rate) - 1) * hop_length + n_fft`` samples."""
+    backend.validate_data_format_str(input_data_format)
+    rate = backend.time_stretch_parameters(rate)
+    if hop_length is None:
+        hop_length = n_fft // 4
+    shared = dict(n_fft=n_fft, win_length=n_fft, hop_length=hop_length)
+    stft_args = dict(shared, window_name='hann_window', pad_begin=False, pad_end=False, input_data_format=input_data_format,
+                     output_data_format=input_data_format)
+    if input_shape is not None:
+        stft_args['input_shape'] = input_shape
+    chain = Sequential(name=name)
+    chain.add(STFT(**stft_args))
+    chain.add(TimeStretch(rate, data_format=input_data_format))
+    chain.add(InverseSTFT(forward_window_name='hann_window', input_data_format=input_data_format,
+                          output_data_format=input_data_format, **shared))
+    return chain
 
 
 @register_keras_serializable(package='Kapre', name='StftMagPhase')

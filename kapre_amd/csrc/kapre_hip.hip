@@ -38,6 +38,8 @@
 //                             forward and adjoint in one kernel
 //   kpr_griffin_lim_kernels.h Griffin-Lim phase reconstruction: the initial spectrum (zero or Philox phase), the projection onto the
 //                             given magnitude with the momentum term and the convergence sums, the per-item convergence figure
+//   kpr_time_stretch_kernels.h phase-vocoder time stretching of a complex spectrogram: a running sum of 32-bit angle words along time
+//                             in k_pcen's geometry (chunk sums through LDS, one barrier per super-block)
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
 // then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h next to their kernel headers.
 // This file: the C ABI -- the extern "C" entry points, grouped as in include/kapre_hip.h.
@@ -83,6 +85,7 @@
 #include "kpr_cmvn_kernels.h"
 #include "kpr_resample_kernels.h"
 #include "kpr_griffin_lim_kernels.h"
+#include "kpr_time_stretch_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -997,6 +1000,18 @@ int kpr_griffin_lim_f32(const float* mag, const kpr_stft_geom* g, int64_t n_fram
     if (int e = api_enter()) return e;
     return run_griffin_lim(mag, g, n_frames, window, synth_window, n_iter, momentum, power, init_mode, init, rng_state, wave_out, sc_out,
                            workspace, workspace_bytes, stream);
+}
+
+/* ---- TimeStretch (kpr_time_stretch_kernels.h) -------------------------------------------------- */
+int kpr_time_stretch_plan(int64_t frames_out, int64_t inner, int* rows_per_wave, int* waves_per_group) {
+    if (frames_out < 0 || inner < 0 || !rows_per_wave || !waves_per_group) return fail(KPR_E_BADARG, "bad frames_out/inner or NULL result");
+    *rows_per_wave = kPvRows;
+    *waves_per_group = kPvWaves;
+    return 0;
+}
+int kpr_time_stretch_c64(const void* x, int64_t outer, int64_t frames_in, int64_t frames_out, int64_t inner, const int32_t* idx,
+                         const float* alpha, void* out, uint32_t* phase_out, kpr_stream_t stream) {
+    return run_time_stretch(x, outer, frames_in, frames_out, inner, idx, alpha, out, phase_out, stream);
 }
 
 }  // extern "C"

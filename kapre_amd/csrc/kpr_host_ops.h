@@ -1,6 +1,7 @@
-// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN and
-// Resample entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h, kpr_augment_kernels.h,
-// kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h).
+// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN,
+// Resample and TimeStretch entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
+// kpr_augment_kernels.h, kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h,
+// kpr_time_stretch_kernels.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
 
@@ -478,6 +479,55 @@ static int run_resample(const float* x, int64_t batch, int channels, int64_t in_
     if (nch == 2) hipLaunchKernelGGL(k_resample<2>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_resample<1>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
     return launch_check("k_resample", nch);
+}
+
+// ---- TimeStretch (kpr_time_stretch_kernels.h): argument checks and the one launch of the phase vocoder ----
+// x: (outer, frames_in, inner) complex64 -> out: (outer, frames_out, inner); idx / alpha: frames_out device entries, never read here
+static int run_time_stretch(const void* x, int64_t outer, int64_t frames_in, int64_t frames_out, int64_t inner, const int32_t* idx,
+                            const float* alpha, void* out, uint32_t* phase_out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (outer < 0 || frames_in < 0 || frames_out < 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/frames_in/frames_out/inner");
+    const long long lim = 1LL << 30;
+    if (inner > 0 && (frames_in > (lim - 1) / inner || frames_out > (lim - 1) / inner))
+        return fail(KPR_E_UNSUPPORTED, "time stretch: %lld -> %lld frames x %lld columns: 2^30 elements or more per outer item are not "
+                    "supported", (long long)frames_in, (long long)frames_out, (long long)inner);
+    if (outer == 0 || frames_out == 0 || inner == 0) return 0;
+    if ((!x && frames_in > 0) || !out || !idx || !alpha) return fail(KPR_E_BADARG, "x / out / idx / alpha must not be NULL");
+    if ((((uintptr_t)x) | ((uintptr_t)out)) & 7) return fail(KPR_E_BADARG, "x / out must be 8-byte aligned");
+    if ((((uintptr_t)idx) | ((uintptr_t)alpha) | ((uintptr_t)phase_out)) & 3)
+        return fail(KPR_E_BADARG, "idx / alpha / phase_out must be 4-byte aligned");
+    if (outer > (1LL << 59) / (std::max(frames_in, frames_out) * inner))                     // (the byte counts below stay in 64 bits)
+        return fail(KPR_E_UNSUPPORTED, "time stretch: outer = %lld items of that size are not supported", (long long)outer);
+    {
+        const uintptr_t nx = (uintptr_t)outer * frames_in * inner * 8, no = (uintptr_t)outer * frames_out * inner * 8, nt = (uintptr_t)frames_out * 4;
+        auto clash = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
+            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+        };
+        if (clash(out, no, x, nx)) return fail(KPR_E_BADARG, "x and out overlap (there is no in-place form)");
+        if (clash(phase_out, no / 2, x, nx) || clash(phase_out, no / 2, out, no))
+            return fail(KPR_E_BADARG, "phase_out overlaps x or out");
+        for (const void* t : {(const void*)idx, (const void*)alpha})
+            if (clash(t, nt, out, no) || clash(t, nt, phase_out, no / 2)) return fail(KPR_E_BADARG, "idx / alpha overlap an output");
+    }
+    const bool v2 = inner % 2 == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)phase_out) & 7) == 0;
+    PvArgs a;
+    a.x = (const float2*)x; a.out = (float2*)out; a.phase = phase_out;
+    a.idx = idx; a.alpha = alpha;
+    a.frames_in = (int)frames_in; a.frames_out = (int)frames_out;
+    a.inner = (unsigned)inner;
+    a.groups_per_item = (unsigned)(v2 ? inner / 2 : inner);
+    a.n_groups = (long long)outer * a.groups_per_item;
+    const long long blocks = (a.n_groups + 63) / 64;
+    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
+    const dim3 grid((unsigned)blocks), block(64 * kPvWaves);
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_time_stretch<%d>: grid %lld x %d lanes, %d frames per wave, %d waves per workgroup; %lld -> %lld "
+                "frames = %lld super-block(s)%s\n", v2 ? 2 : 1, blocks, 64 * kPvWaves, kPvRows, kPvWaves, (long long)frames_in,
+                (long long)frames_out, (long long)((frames_out + kPvRows * kPvWaves - 1) / (kPvRows * kPvWaves)),
+                phase_out ? ", phase words kept" : "");
+    if (v2) hipLaunchKernelGGL(k_time_stretch<2>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_time_stretch<1>, grid, block, 0, (hipStream_t)stream, a);
+    return launch_check("k_time_stretch", v2 ? 2 : 1);
 }
 
 static int frame_args(int64_t batch, int channels, int64_t time, int layout, int frame_length,

@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN`` and ``GriffinLim`` are this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim`` and ``TimeStretch`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -36,6 +36,7 @@ __all__ = [
     'PCEN',
     'CMVN',
     'GriffinLim',
+    'TimeStretch',
 ]
 
 
@@ -973,6 +974,87 @@ class GriffinLim(Layer):
                 'output_data_format': self.output_data_format_original,
             }
         )
+        return config
+
+
+_TS_CONSTS = _DeviceConstants()          # the tables of backend.phase_vocoder (the layer keeps its own)
+
+
+def _time_stretch_run(x, rate, fmt, consts):
+    """``x`` through the phase vocoder at the validated ``rate`` in the resolved data format ``fmt``; the tables come from
+    ``consts``, one pair per (frames, rate, device)."""
+    import torch
+
+    if len(x.shape) != 4:
+        raise ValueError('TimeStretch expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+    cplx = x.is_complex() if isinstance(x, torch.Tensor) else np.iscomplexobj(x)
+    if not cplx:
+        raise TypeError('TimeStretch expects a complex spectrogram (the output of STFT), got dtype %s' % (x.dtype,))
+    if _ffi.is_f64(x):
+        raise TypeError('TimeStretch has float32 kernels only; got a complex128 input (cast it to complex64)')
+    if isinstance(x, torch.Tensor):
+        x = x.detach()
+    x = _ffi.as_device(x, torch.complex64)
+    frames = int(_ffi.dims_of(x.shape, fmt)[2])
+    frames_out = backend.time_stretch_length(frames, rate)
+    table = lambda which: (lambda: backend.time_stretch_table(frames, rate)[which])
+    idx = consts.get(('ts_idx', frames, rate), x.device, table(0))
+    alpha = consts.get(('ts_alpha', frames, rate), x.device, table(1))
+    return _ffi.time_stretch(x, fmt, idx, alpha, frames_out)
+
+
+@register_keras_serializable(package='Kapre')
+class TimeStretch(Layer):
+    """Phase-vocoder time stretching of a complex spectrogram: the speed of the signal changes, its pitch does not
+    (``torchaudio.transforms.TimeStretch``, ``librosa.phase_vocoder``).  It sits between ``STFT`` and ``InverseSTFT``
+    (``composed.get_time_stretch_layer``).  ``rate`` < 1 slows the signal down, ``rate`` > 1 speeds it up: T input frames give
+    T' = ceil(T / rate) output frames.  For output frame t, with s = t * rate (float64), i = floor(s), a = s - i, and the frames
+    X[T] and X[T + 1] taken as zero, per bin:
+
+        Theta(x) = 2 rint(atan2f(im, re) c) as a uint32 word, 2^32 = one turn, c = float32(2^30 / pi);
+                   0 for a bin that is zero (whatever the signs of the zeros) or not finite
+        P[0] = Theta(X[0]);   P[t + 1] = P[t] + Theta(X[i + 1]) - Theta(X[i])     (uint32 arithmetic)
+        m[t] = a |X[i + 1]| + (1 - a) |X[i]|
+        Y[t] = m[t] (cos, sin)(pi h),   h = (float)(int32)P[t] 2^-31
+
+    There is no ``hop_length`` argument.  The textbook recurrence adds wrap(angle X[i + 1] - angle X[i] - adv) + adv per step,
+    adv being the phase a bin's centre frequency advances in one hop; wrap() changes its argument by a whole number of turns, so
+    the accumulated phase equals angle X[0] + sum (angle X[i + 1] - angle X[i]) modulo 2 pi, and Y depends on it only modulo
+    2 pi: adv, and with it the hop length, drops out.  Kept as 32-bit fixed-point words the sum is integer addition -- it wraps by
+    itself and loses no precision however long the clip, where a float32 running sum of radians drifts.
+
+    ``rate = 1`` gives P[t] = Theta(X[t]) and returns the input up to rounding.  A non-finite bin makes non-finite only the
+    output frames that read it; every other frame is bit for bit what it would be with that bin set to 0.  The same inputs give
+    the same bits.  (b, frame, freq, ch) for ``channels_last``, (b, ch, frame, freq) for ``channels_first``; complex64 in and
+    out, one kernel launch (kpr_time_stretch_c64); the index tables are computed on the host in float64 once per
+    (frames, device) and kept.  ``rate`` must be a finite number > 0 and not a bool (``ValueError``), the input rank 4
+    (``ValueError``) and complex (``TypeError``); a complex128 input or a float64 layer raises ``TypeError``.
+
+    The output carries no ``grad_fn``: the layer is not differentiable, and an input that requires grad is detached."""
+
+    def __init__(self, rate, data_format='default', **kwargs):
+        super(TimeStretch, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):
+            data_format = data_format['config']
+        self.rate = backend.time_stretch_parameters(rate)
+        self.data_format_original = data_format
+        self.data_format = _resolve_format(data_format)
+        self._consts = _DeviceConstants()
+
+    def compute_output_shape(self, input_shape):
+        """frames -> ceil(frames / rate); ``None`` stays ``None``"""
+        b, c, f, k = _ffi.dims_of(input_shape, self.data_format)
+        return _ffi.shape_of(self.data_format, b, c, backend.time_stretch_length(f, self.rate), k)
+
+    def call(self, x):
+        if self._f64:
+            raise TypeError('TimeStretch has float32 kernels only; build the layer with dtype float32')
+        return _time_stretch_run(x, self.rate, self.data_format, self._consts)
+
+    def get_config(self):
+        config = super(TimeStretch, self).get_config()
+        config.update({'rate': self.rate, 'data_format': self.data_format_original})
         return config
 
 
