@@ -677,9 +677,10 @@ def pcen_plan(frames: int, inner: int):
     return rows.value, waves.value
 
 
-def _pcen_geometry(x, fmt):
-    """(outer, frames, inner, band_div, n_bands) of the rank-4 ``x``"""
-    b, c, t, m = dims_of(x.shape, fmt)
+def _time_geometry(shape, fmt):
+    """(outer, frames, inner, band_div, n_bands) of a rank-4 ``shape``: the contiguous (outer, frames, inner) problem that the
+    time-tiled launchers (PCEN, CMVN, TimeStretch) hand to the library; the band of inner index i is i // band_div"""
+    b, c, t, m = dims_of(shape, fmt)
     if fmt in ("channels_last", CHANNELS_LAST):
         return b, t, m * c, c, m
     return b * c, t, m, 1, m
@@ -691,7 +692,7 @@ def pcen(x, fmt, params, eps: float, want_smooth: bool = False):
     import torch
     out = torch.empty_like(x)
     smooth = torch.empty_like(x) if want_smooth else None
-    _call("kpr_pcen_f32", x.device, ptr(x), *_pcen_geometry(x, fmt), *(ptr(p) for p in params), float(eps), ptr(out),
+    _call("kpr_pcen_f32", x.device, ptr(x), *_time_geometry(x.shape, fmt), *(ptr(p) for p in params), float(eps), ptr(out),
           ptr(smooth))
     return (out, smooth) if want_smooth else out
 
@@ -701,7 +702,7 @@ def pcen_bwd(x, smooth, g, fmt, params, eps: float):
     import torch
     g = g.contiguous().to(torch.float32)
     gx = torch.empty_like(x)
-    _call("kpr_pcen_bwd_f32", x.device, ptr(x), ptr(smooth), ptr(g), *_pcen_geometry(x, fmt), *(ptr(p) for p in params),
+    _call("kpr_pcen_bwd_f32", x.device, ptr(x), ptr(smooth), ptr(g), *_time_geometry(x.shape, fmt), *(ptr(p) for p in params),
           float(eps), ptr(gx))
     return gx
 
@@ -711,7 +712,7 @@ def pcen_bwd_params(x, smooth, g, fmt, params, eps: float, want_gx: bool = True)
     (4, n_bands) float32 tensor with rows s, alpha, delta, r.  Two launches; the same inputs give the same bits."""
     import torch
     g = g.contiguous().to(torch.float32)
-    geom = _pcen_geometry(x, fmt)
+    geom = _time_geometry(x.shape, fmt)
     gx = torch.empty_like(x) if want_gx else None
     gparams = torch.empty((4, geom[4]), dtype=torch.float32, device=x.device)
     ws_bytes = int(lib().kpr_pcen_bwd_params_workspace_bytes(*geom[:3]))
@@ -731,22 +732,16 @@ def cmvn_plan(frames: int, inner: int):
     return rows.value, waves.value, resident.value
 
 
-def _cmvn_geometry(x, fmt):
-    """(outer, frames, inner) of the rank-4 ``x``; the shape of the per-column statistics"""
-    b, c, t, m = dims_of(x.shape, fmt)
-    if fmt in ("channels_last", CHANNELS_LAST):
-        return (b, t, m * c), (b, m, c)
-    return (b * c, t, m), (b, c, m)
-
-
 def cmvn(x, fmt, norm_vars: bool, eps: float, want_rstd: bool = False):
     """Mean (and with ``norm_vars`` variance) normalisation along time of the rank-4 float32 ``x``.  With ``want_rstd``
     (``norm_vars`` only) returns (out, rstd), rstd per column being what ``cmvn_bwd`` needs."""
     import torch
-    geom, stats = _cmvn_geometry(x, fmt)
+    b, c, _, m = dims_of(x.shape, fmt)
     out = torch.empty_like(x)
-    rstd = torch.empty(stats, dtype=torch.float32, device=x.device) if want_rstd else None
-    _call("kpr_cmvn_f32", x.device, ptr(x), *geom, int(bool(norm_vars)), float(eps), ptr(out), ptr(rstd))
+    # (one value per column: x's shape without the time axis)
+    rstd = torch.empty(shape_of(fmt, b, c, m), dtype=torch.float32, device=x.device) if want_rstd else None
+    _call("kpr_cmvn_f32", x.device, ptr(x), *_time_geometry(x.shape, fmt)[:3], int(bool(norm_vars)), float(eps), ptr(out),
+          ptr(rstd))
     return (out, rstd) if want_rstd else out
 
 
@@ -756,8 +751,8 @@ def cmvn_bwd(y, rstd, g, fmt, norm_vars: bool):
     import torch
     g = g.contiguous().to(torch.float32)
     gx = torch.empty_like(g)
-    geom, _ = _cmvn_geometry(g, fmt)
-    _call("kpr_cmvn_bwd_f32", g.device, ptr(y), ptr(rstd), ptr(g), *geom, int(bool(norm_vars)), ptr(gx))
+    _call("kpr_cmvn_bwd_f32", g.device, ptr(y), ptr(rstd), ptr(g), *_time_geometry(g.shape, fmt)[:3], int(bool(norm_vars)),
+          ptr(gx))
     return gx
 
 
@@ -916,8 +911,8 @@ def time_stretch(x, fmt, idx, alpha, frames_out: int, want_phase: bool = False):
     entries).  With ``want_phase`` returns (out, phase), phase being the uint32 phase words in out's layout (as an int32
     tensor)."""
     import torch
-    b, c, t, m = dims_of(x.shape, fmt)
-    outer, inner = (b, m * c) if fmt in ("channels_last", CHANNELS_LAST) else (b * c, m)
+    b, c, _, m = dims_of(x.shape, fmt)
+    outer, t, inner = _time_geometry(x.shape, fmt)[:3]
     out = torch.empty(shape_of(fmt, b, c, int(frames_out), m), dtype=torch.complex64, device=x.device)
     phase = torch.empty(out.shape, dtype=torch.int32, device=x.device) if want_phase else None
     _call("kpr_time_stretch_c64", x.device, ptr(x), outer, t, int(frames_out), inner, ptr(idx), ptr(alpha), ptr(out), ptr(phase))

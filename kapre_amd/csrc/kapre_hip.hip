@@ -6,7 +6,8 @@
 //                             (2^a 5^b) passes, real-FFT pairing
 //   kpr_common.h              errors, frame geometry, sample fetch, and the wave-protocol pieces every kernel family shares:
 //                             ticket draw, bounded waits, window pairs into LDS
-//   kpr_mel_kernels.h         k_mel_ws: waveform -> [frame + window + rFFT -> |X| -> (K x M)
+//   kpr_cols.h                the column groups of the time-tiled kernels (k_pcen, k_cmvn, k_time_stretch): ColGroup, ColVec
+//   kpr_mel_kernels.h        k_mel_ws: waveform -> [frame + window + rFFT -> |X| -> (K x M)
 //                             filterbank on fp32 MFMA -> optional 10 log10], the whole Sequential of
 //                             composed.py:138-261 in one launch; FROM_MAG: stand-alone ApplyFilterbank
 //   kpr_mel_ts_kernels.h      k_mel_ts: the same Sequential, tile-synchronous (16 equal waves, two barriers per round) --
@@ -32,14 +33,14 @@
 //   kpr_pcen_kernels.h        per-channel energy normalisation and its input gradient: a recurrence along time, tiled over
 //                             the waves of a workgroup (chunk end values through LDS, one barrier per super-block)
 //   kpr_cmvn_kernels.h        per-utterance mean / variance normalisation and its input gradient: a reduction along time in
-//                             k_pcen's geometry (chunk statistics through LDS, merged pairwise in a fixed order), resident in
+//                             the same geometry (chunk statistics through LDS, merged pairwise in a fixed order), resident in
 //                             registers up to 128 frames, two sweeps beyond
 //   kpr_resample_kernels.h    rational sample-rate conversion (signal.Resample): a polyphase gather over a staged input span,
 //                             forward and adjoint in one kernel
 //   kpr_griffin_lim_kernels.h Griffin-Lim phase reconstruction: the initial spectrum (zero or Philox phase), the projection onto the
 //                             given magnitude with the momentum term and the convergence sums, the per-item convergence figure
 //   kpr_time_stretch_kernels.h phase-vocoder time stretching of a complex spectrogram: a running sum of 32-bit angle words along time
-//                             in k_pcen's geometry (chunk sums through LDS, one barrier per super-block)
+//                             in the same geometry (chunk sums through LDS, one barrier per super-block)
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
 // then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h next to their kernel headers.
 // This file: the C ABI -- the extern "C" entry points, grouped as in include/kapre_hip.h.
@@ -67,6 +68,7 @@
 #include "kpr_fft_mr.h"
 
 #include "kpr_common.h"
+#include "kpr_cols.h"
 #include "kpr_mel_kernels.h"
 #include "kpr_mel_ts_kernels.h"
 #include "kpr_mel_pw_kernels.h"
@@ -519,12 +521,10 @@ int kpr_mag_to_db_f32(const float* x, int64_t n_items, int64_t item_size, const 
     if (int e = launch_check("k_stats_init")) return e;
     int chunks = db_chunks(n_items, item_size);
     if (opt(OPT_DB_CHUNKS) > 0) chunks = opt(OPT_DB_CHUNKS);
-    if (((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0)   // 16-byte accesses on the aligned middle of every chunk
-        hipLaunchKernelGGL(k_db_log<4>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, st, x,
-                           (long long)item_size, chunks, dbd, stats, out);
-    else
-        hipLaunchKernelGGL(k_db_log<1>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, st, x,
-                           (long long)item_size, chunks, dbd, stats, out);
+    // (aligned bases: 16-byte accesses on the aligned middle of every chunk)
+    with_vec<4>(((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0, [&](auto v) {
+        hipLaunchKernelGGL(k_db_log<v>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, st, x, (long long)item_size, chunks, dbd, stats, out);
+    });
     if (int e = launch_check("k_db_log")) return e;
     return db_clamp(out, n_items, item_size, dbd.dyn, stats, st);
 }
@@ -678,12 +678,9 @@ int kpr_frame_f32(const float* x, int64_t batch, int channels, int64_t time, int
     const int rowlen = a.cl ? a.L * a.C : a.L;
     const bool vec = (rowlen & 3) == 0 && (((uintptr_t)out) & 15) == 0;
     const long long work = nrows * (vec ? rowlen / 4 : rowlen);
-    if (vec)
-        hipLaunchKernelGGL(k_frame<4>, dim3(grid_1d(work, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x,
-                           a, out, nrows);
-    else
-        hipLaunchKernelGGL(k_frame<1>, dim3(grid_1d(work, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x,
-                           a, out, nrows);
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_frame<v>, dim3(grid_1d(work, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, a, out, nrows);
+    });
     return launch_check("k_frame");
 }
 
@@ -722,12 +719,10 @@ int kpr_delta_f32(const float* x, int64_t batch, int channels, int64_t frames, i
     if (a.total == 0) return 0;
     if (!x || !out || x == out) return fail(KPR_E_BADARG, "x / out must not be NULL or aliased");
     const bool vec = (a.inner & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(k_delta<4>, dim3(grid_1d(a.total / 4, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
-                           x, a.outer, (long long)frames, a.inner, a.n, pad_mode, a.scale, out);
-    else
-        hipLaunchKernelGGL(k_delta<1>, dim3(grid_1d(a.total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x,
-                           a.outer, (long long)frames, a.inner, a.n, pad_mode, a.scale, out);
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_delta<v>, dim3(grid_1d(a.total / v, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, a.outer,
+                           (long long)frames, a.inner, a.n, pad_mode, a.scale, out);
+    });
     return launch_check("k_delta");
 }
 
@@ -804,18 +799,15 @@ int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table,
     const bool vec = ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
     if (n_freq > kAugMaxFreq)
         return fail(KPR_E_UNSUPPORTED, "n_freq = %d: the copy form holds at most %d bins per row", n_freq, kAugMaxFreq);
-    if (x != out) {   // partial overlap would let a workgroup read what another has already masked (out == x: in place)
-        const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, nb = (uintptr_t)(n_items * isz * 4);
-        if (xa < oa + nb && oa < xa + nb) return fail(KPR_E_BADARG, "x and out overlap (only out == x, in place, is allowed)");
-    }
+    // partial overlap would let a workgroup read what another has already masked (out == x: in place)
+    const uintptr_t nb = (uintptr_t)(n_items * isz * 4);
+    if (x != out && ranges_overlap(x, nb, out, nb)) return fail(KPR_E_BADARG, "x and out overlap (only out == x, in place, is allowed)");
     const long long chunks = (isz + kAugChunk - 1) / kAugChunk;
     if (n_items * chunks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many items");
-    if (vec)
-        hipLaunchKernelGGL(k_specaug_apply<4>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_specaug_apply<v>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
                            (int)chunks, mask_value, out);
-    else
-        hipLaunchKernelGGL(k_specaug_apply<1>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
-                           (int)chunks, mask_value, out);
+    });
     return launch_check("k_specaug_apply");
 }
 

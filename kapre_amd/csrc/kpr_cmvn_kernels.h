@@ -6,11 +6,8 @@
 //   y[t] = c[t] rstd (norm_vars) or c[t];   n = F
 //   backward: gx[t] = rstd (gy[t] - mean(gy) - y[t] mean(gy y))  (norm_vars),  gx[t] = gy[t] - mean(gy)  (else)
 //
-// The geometry is k_pcen's (kpr_pcen_kernels.h): a contiguous (outer, F, inner) block; a lane owns one column group -- four
-// consecutive inner indices of one outer item with 16-byte accesses (V = 4), or a single column (V = 1) --, column groups are
-// numbered through all outer items, a workgroup of W waves owns 64 of them, and time is tiled in super-blocks of W * R rows,
-// wave w holding the R rows (sb W + w) R ... of super-block sb in registers.  There is no band divisor: every inner index is a
-// column of its own.
+// Column groups (V = 4 or 1 floats), super-blocks of W * R rows and the one barrier are those of kpr_cols.h.  There is no band
+// divisor: every inner index is a column of its own.
 //
 // The chunk of a wave is its R rows (fewer at the end of the series).  A wave shifts its rows by x[0] (log-mel decibels sit at
 // -60 +- a few: the shift keeps the sums small), forms its chunk's mean and M2 = sum (d - mean)^2 two-pass in registers, each
@@ -51,38 +48,13 @@ struct CmvnArgs {
     long long n_groups;            // outer * groups_per_item
 };
 
-template <int V>
-struct CmvnVec {
-    float v[V];
-};
-
-template <int V>
-KPR_DEV CmvnVec<V> cmvn_load(const float* p) {
-    CmvnVec<V> r;
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-
-template <int V>
-KPR_DEV void cmvn_store(float* p, const CmvnVec<V>& r) {
-    if constexpr (V == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else
-        *p = r.v[0];
-}
-
 // rows of the chunk that starts at row tau0 of a series of `frames` rows
 KPR_DEV int cmvn_count(int tau0, int frames) { return min(max(frames - tau0, 0), kCmvnRows); }
 
 // One chunk of nb >= 1 rows, shifted in place (d = x - x0): its mean and, with M2, sum (d - mean)^2 -- two passes over the
 // registers, each sum sequential in row order.  nb is the same for every lane of the wave.
 template <int V, bool M2>
-KPR_DEV void cmvn_chunk(CmvnVec<V> (&d)[kCmvnRows], const float (&x0)[V], int nb, float (&mean)[V], float (&m2)[V]) {
+KPR_DEV void cmvn_chunk(ColVec<float, V> (&d)[kCmvnRows], const float (&x0)[V], int nb, float (&mean)[V], float (&m2)[V]) {
 #pragma clang fp contract(off)
     const float fnb = (float)nb;
     float s[V], q[V];
@@ -153,26 +125,22 @@ __global__ __launch_bounds__(64 * kCmvnWaves) void k_cmvn(CmvnArgs a) {
     // forward: the chunks' mean and M2.  backward: their sum gy and sum gy y
     __shared__ float slab[2][2][W][V][64];
 
-    // (the wave index as a scalar: a chunk's row count is then one too, and the guards below are scalar branches)
+    // (the wave index as a scalar: a chunk's row count is then one too, and the guards below are scalar branches; `lane` is taken
+    // ahead of it, not as cg.lane behind it: the order of the two instructions decides a register tie in one instance)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long group = (long long)blockIdx.x * 64 + lane;
-    const bool live = group < a.n_groups;
-    // (a lane past the last group runs along on group 0 with its stores masked: the barrier needs every wave)
-    const long long gsafe = live ? group : 0;
-    const long long item = gsafe / a.groups_per_item;
-    const unsigned i0 = (unsigned)(gsafe - item * a.groups_per_item) * V;
-    const long long base = item * (long long)a.frames * a.inner + i0;
-    const long long col = item * (long long)a.inner + i0;            // of the (outer, inner) statistics
+    const ColGroup cg = col_group<V>(a.n_groups, a.groups_per_item);
+    const long long base = cg.item * (long long)a.frames * a.inner + cg.i0;
+    const long long col = cg.item * (long long)a.inner + cg.i0;      // of the (outer, inner) statistics
 
-    CmvnVec<V> in[R];              // forward: x, shifted in place.  backward: gy
-    CmvnVec<V> yy[NEED_Y ? R : 1]; // backward: y
+    ColVec<float, V> in[R];               // forward: x, shifted in place.  backward: gy
+    ColVec<float, V> yy[NEED_Y ? R : 1];  // backward: y
     float x0[V], mean[V], m2[V];   // forward: the running mean and M2.  backward: the running sum gy and sum gy y
 #pragma unroll
     for (int v = 0; v < V; ++v) mean[v] = m2[v] = 0.0f;
     if constexpr (!BWD) {
         // the wave that holds row 0 takes x[0] from there (RES); every other wave loads it
         if (!RES || wave != 0) {
-            const CmvnVec<V> t = cmvn_load<V>(a.x + base);
+            const ColVec<float, V> t = col_load<V>(a.x + base);
 #pragma unroll
             for (int v = 0; v < V; ++v) x0[v] = t.v[v];
         }
@@ -187,8 +155,8 @@ __global__ __launch_bounds__(64 * kCmvnWaves) void k_cmvn(CmvnArgs a) {
         for (int k = 0; k < R; ++k)
             if (k < nb) {
                 const long long off = base + (long long)(tau0 + k) * a.inner;
-                in[k] = cmvn_load<V>((BWD ? a.gy : a.x) + off);
-                if constexpr (NEED_Y) yy[k] = cmvn_load<V>(a.x + off);
+                in[k] = col_load<V>((BWD ? a.gy : a.x) + off);
+                if constexpr (NEED_Y) yy[k] = col_load<V>(a.x + off);
             }
         float cm[V], cq[V];
         if constexpr (!BWD) {
@@ -250,11 +218,11 @@ __global__ __launch_bounds__(64 * kCmvnWaves) void k_cmvn(CmvnArgs a) {
         if constexpr (NORM) {
 #pragma unroll
             for (int v = 0; v < V; ++v) rstd[v] = __builtin_amdgcn_rsqf(m2[v] / fn + a.eps);
-            if (MODE == CMVN_FWD_RSTD && wave == 0 && live) {
-                CmvnVec<V> o;
+            if (MODE == CMVN_FWD_RSTD && wave == 0 && cg.live) {
+                ColVec<float, V> o;
 #pragma unroll
                 for (int v = 0; v < V; ++v) o.v[v] = rstd[v];
-                cmvn_store<V>(a.rstd_out + col, o);
+                col_store<V>(a.rstd_out + col, o);
             }
         }
     } else {
@@ -264,7 +232,7 @@ __global__ __launch_bounds__(64 * kCmvnWaves) void k_cmvn(CmvnArgs a) {
             if constexpr (NORM) mgy[v] = m2[v] / fn;                 // mean(gy y)
         }
         if constexpr (NORM) {
-            const CmvnVec<V> t = cmvn_load<V>(a.rstd + col);
+            const ColVec<float, V> t = col_load<V>(a.rstd + col);
 #pragma unroll
             for (int v = 0; v < V; ++v) rstd[v] = t.v[v];
         }
@@ -279,21 +247,21 @@ __global__ __launch_bounds__(64 * kCmvnWaves) void k_cmvn(CmvnArgs a) {
             if (k < nb) {
                 const long long off = base + (long long)(tau0 + k) * a.inner;
                 if constexpr (!RES) {
-                    in[k] = cmvn_load<V>((BWD ? a.gy : a.x) + off);
-                    if constexpr (NEED_Y) yy[k] = cmvn_load<V>(a.x + off);
+                    in[k] = col_load<V>((BWD ? a.gy : a.x) + off);
+                    if constexpr (NEED_Y) yy[k] = col_load<V>(a.x + off);
                     if constexpr (!BWD) {
 #pragma clang fp contract(off)
 #pragma unroll
                         for (int v = 0; v < V; ++v) in[k].v[v] = in[k].v[v] - x0[v];
                     }
                 }
-                CmvnVec<V> o;
+                ColVec<float, V> o;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
                     if constexpr (BWD) o.v[v] = cmvn_bwd_out<NORM>(in[k].v[v], NEED_Y ? yy[k].v[v] : 0.0f, mean[v], mgy[v], rstd[v]);
                     else o.v[v] = cmvn_out<NORM>(in[k].v[v], mean[v], rstd[v]);
                 }
-                if (live) cmvn_store<V>(a.out + off, o);
+                if (cg.live) col_store<V>(a.out + off, o);
             }
     }
 }

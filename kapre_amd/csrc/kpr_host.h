@@ -1,5 +1,6 @@
 // kpr_host.h -- host side shared by every kernel family: options, once-per-device state, launch log, device status word, LDS opt-in,
-// CU count, geometry checks, the GEMM launcher, the device-table cache, the launcher of the framewise FFT kernels.
+// CU count, with_vec, geometry checks (ranges_overlap, col_launch for the time-tiled kernels), the GEMM launcher, the device-table cache,
+// the launcher of the framewise FFT kernels.
 // Part of the single translation unit kapre_hip.hip (after the kernel headers, before kpr_host_fft.h / _stft.h / _istft.h / _mel.h / _ops.h).
 #pragma once
 
@@ -166,7 +167,41 @@ static long long* g_debug_stamps = nullptr;   // development aid: kpr_debug_stam
 // the branch of a with_pow2 / with_mr body that the route never selects
 static int no_instance(const char* what) { return fail(KPR_E_UNSUPPORTED, "no %s instance for this call", what); }
 
+// wide -> f(std::integral_constant<int, VMAX>), else f(std::integral_constant<int, 1>): the vector-width instance of a kernel,
+// picked at run time (with_pow2's idiom)
+template <int VMAX, class Fn>
+static auto with_vec(bool wide, Fn&& f) {
+    if (wide) return f(std::integral_constant<int, VMAX>{});
+    return f(std::integral_constant<int, 1>{});
+}
+
 // ---- geometry / validation ---------------------------------------------------------------------------------------------
+// do the byte ranges [p, p + np) and [q, q + nq) overlap?  A NULL pointer names no range; ranges that touch do not overlap
+static bool ranges_overlap(const void* p, uintptr_t np, const void* q, uintptr_t nq) {
+    return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+}
+
+// The launch shape of a time-tiled kernel (kpr_cols.h) over (outer, frames, inner): column groups of V columns where the caller's
+// pointers are aligned for it and inner % V == 0, of one column otherwise; 64 groups per workgroup of `waves` waves.  inner,
+// groups_per_item and n_groups go into the kernel's argument struct as they are.
+struct ColLaunch {
+    bool wide;
+    unsigned inner, groups_per_item;
+    long long n_groups;
+    dim3 grid, block;
+};
+static int col_launch(int64_t outer, int64_t inner, int V, int waves, bool aligned, ColLaunch* l) {
+    l->wide = aligned && inner % V == 0;
+    l->inner = (unsigned)inner;
+    l->groups_per_item = (unsigned)(l->wide ? inner / V : inner);
+    l->n_groups = (long long)outer * l->groups_per_item;
+    const long long blocks = (l->n_groups + 63) / 64;
+    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
+    l->grid = dim3((unsigned)blocks);
+    l->block = dim3(64 * waves);
+    return 0;
+}
+
 static long long frames_of(const kpr_stft_geom* s) {
     long long t = s->time + (s->pad_begin ? (s->n_fft - s->hop_length) : 0);
     if (s->pad_end) return (t + s->hop_length - 1) / s->hop_length;

@@ -14,10 +14,6 @@ static size_t gl_part_bytes(int64_t n_items, int64_t item_size) {
     return gl_align((size_t)8 * (size_t)n_items * (size_t)gl_chunks(item_size));
 }
 
-static bool gl_overlap(const void* p, size_t np, const void* q, size_t nq) {
-    return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
-}
-
 // the projection step and, with sc_out, the convergence figure of every item (two launches)
 static int run_gl_project(const void* R, const void* T, const float* mag, int64_t n_items, int64_t item_size, float c, void* S,
                           float* sc_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
@@ -33,7 +29,7 @@ static int run_gl_project(const void* R, const void* T, const float* mag, int64_
     if ((((uintptr_t)R) | ((uintptr_t)T) | ((uintptr_t)S)) & 7) return fail(KPR_E_BADARG, "R / T / S must be 8-byte aligned");
     if ((((uintptr_t)mag) | ((uintptr_t)sc_out)) & 3) return fail(KPR_E_BADARG, "mag / sc_out must be 4-byte aligned");
     const size_t n = (size_t)n_items * (size_t)item_size;
-    if (gl_overlap(S, n * 8, R, n * 8) || gl_overlap(S, n * 8, T, n * 8) || gl_overlap(S, n * 8, mag, n * 4))
+    if (ranges_overlap(S, n * 8, R, n * 8) || ranges_overlap(S, n * 8, T, n * 8) || ranges_overlap(S, n * 8, mag, n * 4))
         return fail(KPR_E_BADARG, "S overlaps an input (there is no in-place form)");
     float* part = nullptr;
     if (sc_out) {
@@ -41,21 +37,18 @@ static int run_gl_project(const void* R, const void* T, const float* mag, int64_
         if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
             return fail(KPR_E_WORKSPACE, "projection workspace: %zu bytes needed (8 per item and chunk, 8-byte aligned), got %zu", need,
                         workspace ? workspace_bytes : (size_t)0);
-        if (gl_overlap(workspace, need, S, n * 8) || gl_overlap(workspace, need, R, n * 8) || gl_overlap(workspace, need, T, n * 8) ||
-            gl_overlap(workspace, need, mag, n * 4) || gl_overlap(sc_out, (size_t)n_items * 4, S, n * 8))
+        if (ranges_overlap(workspace, need, S, n * 8) || ranges_overlap(workspace, need, R, n * 8) || ranges_overlap(workspace, need, T, n * 8) ||
+            ranges_overlap(workspace, need, mag, n * 4) || ranges_overlap(sc_out, (size_t)n_items * 4, S, n * 8))
             return fail(KPR_E_BADARG, "the workspace or sc_out overlaps another argument");
         part = (float*)workspace;
     }
     const bool v4 = ((((uintptr_t)R) | ((uintptr_t)T) | ((uintptr_t)S) | ((uintptr_t)mag)) & 15) == 0;
     const dim3 grid((unsigned)(n_items * chunks)), block(256);
     const float2 *r = (const float2*)R, *t = (const float2*)T;
-    if (T) {
-        if (v4) hipLaunchKernelGGL((k_gl_project<4, true>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
-        else hipLaunchKernelGGL((k_gl_project<1, true>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
-    } else {
-        if (v4) hipLaunchKernelGGL((k_gl_project<4, false>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
-        else hipLaunchKernelGGL((k_gl_project<1, false>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
-    }
+    with_vec<4>(v4, [&](auto v) {
+        if (T) hipLaunchKernelGGL((k_gl_project<v, true>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
+        else hipLaunchKernelGGL((k_gl_project<v, false>), grid, block, 0, st, r, t, mag, (long long)item_size, (int)chunks, c, (float2*)S, part);
+    });
     if (int e = launch_check("k_gl_project", v4 ? 4 : 1, T ? "mom" : "plain")) return e;
     if (!sc_out) return 0;
     hipLaunchKernelGGL(k_gl_finish, dim3((unsigned)n_items), dim3(64), 0, st, (const float*)part, (int)chunks, sc_out);
@@ -74,8 +67,8 @@ static int run_gl_init(const float* M, int64_t batch, int channels, int64_t plan
     if (n == 0) return 0;
     if (!M || (!S && !mag_out)) return fail(KPR_E_BADARG, "M and one of mag_out / S must not be NULL");
     if ((((uintptr_t)M) | ((uintptr_t)mag_out)) & 3 || ((uintptr_t)S & 7)) return fail(KPR_E_BADARG, "M / mag_out must be 4-byte, S 8-byte aligned");
-    if (gl_overlap(S, (size_t)n * 8, M, (size_t)n * 4) || gl_overlap(mag_out, (size_t)n * 4, M, (size_t)n * 4) ||
-        gl_overlap(S, (size_t)n * 8, mag_out, (size_t)n * 4))
+    if (ranges_overlap(S, (size_t)n * 8, M, (size_t)n * 4) || ranges_overlap(mag_out, (size_t)n * 4, M, (size_t)n * 4) ||
+        ranges_overlap(S, (size_t)n * 8, mag_out, (size_t)n * 4))
         return fail(KPR_E_BADARG, "M, mag_out and S must not overlap");
     GlInitArgs a;
     a.M = M; a.mag = mag_out; a.S = (float2*)S; a.state = (const unsigned long long*)rng_state;
@@ -85,13 +78,10 @@ static int run_gl_init(const float* M, int64_t batch, int channels, int64_t plan
     const bool v4 = ((((uintptr_t)M) | ((uintptr_t)mag_out) | ((uintptr_t)S)) & 15) == 0;
     const bool rnd = init_mode == 1 && S;
     const dim3 grid(grid_1d(v4 ? (n + 3) / 4 : n, 256, 1 << 16)), block(256);
-    if (rnd) {
-        if (v4) hipLaunchKernelGGL((k_gl_init<4, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_gl_init<1, true>), grid, block, 0, st, a);
-    } else {
-        if (v4) hipLaunchKernelGGL((k_gl_init<4, false>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_gl_init<1, false>), grid, block, 0, st, a);
-    }
+    with_vec<4>(v4, [&](auto v) {
+        if (rnd) hipLaunchKernelGGL((k_gl_init<v, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_gl_init<v, false>), grid, block, 0, st, a);
+    });
     if (int e = launch_check("k_gl_init", v4 ? 4 : 1, rnd ? "rand" : "zero")) return e;
     if (!rnd) return 0;
     hipLaunchKernelGGL(k_gl_advance, dim3(1), dim3(64), 0, st, (unsigned long long*)rng_state);

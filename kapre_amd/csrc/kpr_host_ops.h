@@ -1,7 +1,8 @@
 // kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN,
 // Resample and TimeStretch entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
 // kpr_augment_kernels.h, kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h,
-// kpr_time_stretch_kernels.h).
+// kpr_time_stretch_kernels.h).  The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch
+// (kpr_host.h; the device side is kpr_cols.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
 
@@ -84,11 +85,9 @@ static int mu_law_args(int64_t n, int quantization_channels, MuLawDev* p) {
 static int stream_ptrs(const void* in, const void* in2, const void* out, int64_t n, const char* names) {
     if (!in || !in2 || !out) return fail(KPR_E_BADARG, "%s must not be NULL", names);
     if ((((uintptr_t)in) | ((uintptr_t)in2) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "%s must be 4-byte aligned", names);
-    const uintptr_t nb = (uintptr_t)n * 4, oa = (uintptr_t)out;
-    for (const void* q : {in, in2}) {
-        const uintptr_t a = (uintptr_t)q;
-        if (a != oa && a < oa + nb && oa < a + nb) return fail(KPR_E_BADARG, "%s overlap (only out == in, in place, is allowed)", names);
-    }
+    const uintptr_t nb = (uintptr_t)n * 4;
+    for (const void* q : {in, in2})
+        if (q != out && ranges_overlap(q, nb, out, nb)) return fail(KPR_E_BADARG, "%s overlap (only out == in, in place, is allowed)", names);
     return 0;
 }
 
@@ -120,10 +119,7 @@ static int run_freq_map(const float* in, int64_t batch, int channels, int64_t fr
     const long long n_in = batch * plane * (channels + (DROP ? 1 : 0)), n_out = batch * plane * (channels + (DROP ? 0 : 1));
     if (!in || !out) return fail(KPR_E_BADARG, "%s must not be NULL", DROP ? "g / gx" : "x / out");
     if ((((uintptr_t)in) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
-    {
-        const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out;
-        if (ia < oa + (uintptr_t)n_out * 4 && oa < ia + (uintptr_t)n_in * 4) return fail(KPR_E_BADARG, "input and output overlap");
-    }
+    if (ranges_overlap(in, (uintptr_t)n_in * 4, out, (uintptr_t)n_out * 4)) return fail(KPR_E_BADARG, "input and output overlap");
     const bool cl = layout == KPR_CHANNELS_LAST;
     FmapArgs a;
     a.rin = (unsigned)(cl ? channels : plane * channels);
@@ -174,68 +170,52 @@ static int run_pcen(bool bwd, const float* x, const float* smooth, const float* 
                     (long long)(frames * inner));
     uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)smooth | (uintptr_t)gy | (uintptr_t)smooth_out | (uintptr_t)workspace;
     if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    const uintptr_t nb = (uintptr_t)outer * frames * inner * 4;
     {
-        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4;
-        auto clash = [nb](const void* p, const void* q) {
-            return p && q && (uintptr_t)p < (uintptr_t)q + nb && (uintptr_t)q < (uintptr_t)p + nb;
-        };
-        bool bad = clash(out, smooth_out);
-        for (const float* in : {x, smooth, gy}) bad = bad || clash(out, in) || clash(smooth_out, in);
+        bool bad = ranges_overlap(out, nb, smooth_out, nb);
+        for (const float* in : {x, smooth, gy}) bad = bad || ranges_overlap(out, nb, in, nb) || ranges_overlap(smooth_out, nb, in, nb);
         if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
     }
     if (with_params) {
         const size_t need = pcen_params_workspace(outer, frames, inner);
-        const uintptr_t nb = (uintptr_t)outer * frames * inner * 4, ng = (uintptr_t)n_bands * 16;
-        auto within = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
-            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
-        };
-        bool bad = within(gparams, ng, workspace, need);
-        for (const float* t : {x, smooth, gy, (const float*)out}) bad = bad || within(gparams, ng, t, nb) || within(workspace, need, t, nb);
-        for (const float* t : {s, alpha, delta, r}) bad = bad || within(gparams, ng, t, (uintptr_t)n_bands * 4);
+        const uintptr_t ng = (uintptr_t)n_bands * 16;
+        bool bad = ranges_overlap(gparams, ng, workspace, need);
+        for (const float* t : {x, smooth, gy, (const float*)out})
+            bad = bad || ranges_overlap(gparams, ng, t, nb) || ranges_overlap(workspace, need, t, nb);
+        for (const float* t : {s, alpha, delta, r}) bad = bad || ranges_overlap(gparams, ng, t, (uintptr_t)n_bands * 4);
         if (bad) return fail(KPR_E_BADARG, "gparams or the workspace overlaps another argument");
         if (!workspace || workspace_bytes < need)
             return fail(KPR_E_WORKSPACE, "workspace of %zu bytes needed (kpr_pcen_bwd_params_workspace_bytes), got %zu", need,
                         workspace ? workspace_bytes : (size_t)0);
     }
-    const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
+    ColLaunch l;
+    if (int e = col_launch(outer, inner, 4, kPcenWaves, (bits & 15) == 0, &l)) return e;
     PcenArgs a;
     a.x = x; a.smooth = smooth; a.gy = gy; a.out = out; a.smooth_out = smooth_out;
     a.s = s; a.alpha = alpha; a.delta = delta; a.r = r;
     a.eps = eps;
     a.frames = (int)frames;
-    a.inner = (unsigned)inner;
-    a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
+    a.inner = l.inner;
+    a.groups_per_item = l.groups_per_item;
     a.band_div = (unsigned)band_div;
-    a.n_groups = (long long)outer * a.groups_per_item;
+    a.n_groups = l.n_groups;
     a.partials = (float*)workspace;
-    const long long blocks = (a.n_groups + 63) / 64;
-    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
-    const dim3 grid((unsigned)blocks), block(64 * kPcenWaves);
     const hipStream_t st = (hipStream_t)stream;
-    if (with_params) {
-        if (out) {
-            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS>), grid, block, 0, st, a);
-        } else {
-            if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD_PARAMS_ONLY>), grid, block, 0, st, a);
+    const int mode = with_params ? (out ? PCEN_BWD_PARAMS : PCEN_BWD_PARAMS_ONLY) : bwd ? PCEN_BWD : smooth_out ? PCEN_FWD_SMOOTH : PCEN_FWD;
+    with_vec<4>(l.wide, [&](auto v) {
+        switch (mode) {
+            case PCEN_FWD: hipLaunchKernelGGL((k_pcen<v, PCEN_FWD>), l.grid, l.block, 0, st, a); break;
+            case PCEN_FWD_SMOOTH: hipLaunchKernelGGL((k_pcen<v, PCEN_FWD_SMOOTH>), l.grid, l.block, 0, st, a); break;
+            case PCEN_BWD: hipLaunchKernelGGL((k_pcen<v, PCEN_BWD>), l.grid, l.block, 0, st, a); break;
+            case PCEN_BWD_PARAMS: hipLaunchKernelGGL((k_pcen<v, PCEN_BWD_PARAMS>), l.grid, l.block, 0, st, a); break;
+            default: hipLaunchKernelGGL((k_pcen<v, PCEN_BWD_PARAMS_ONLY>), l.grid, l.block, 0, st, a); break;
         }
-        if (int e = launch_check(out ? "k_pcen_bwd_params" : "k_pcen_bwd_params_only", v4 ? 4 : 1)) return e;
-        hipLaunchKernelGGL(k_pcen_param_reduce, dim3(4u * (unsigned)n_bands), dim3(256), 0, st, (const float*)workspace, gparams,
-                           (long long)outer, (unsigned)inner, (unsigned)band_div, (unsigned)n_bands);
-        return launch_check("k_pcen_param_reduce");
-    }
-    if (bwd) {
-        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_BWD>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_pcen<1, PCEN_BWD>), grid, block, 0, st, a);
-    } else if (smooth_out) {
-        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD_SMOOTH>), grid, block, 0, st, a);
-    } else {
-        if (v4) hipLaunchKernelGGL((k_pcen<4, PCEN_FWD>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_pcen<1, PCEN_FWD>), grid, block, 0, st, a);
-    }
-    return launch_check(bwd ? "k_pcen_bwd" : "k_pcen", v4 ? 4 : 1);
+    });
+    if (!with_params) return launch_check(bwd ? "k_pcen_bwd" : "k_pcen", l.wide ? 4 : 1);
+    if (int e = launch_check(out ? "k_pcen_bwd_params" : "k_pcen_bwd_params_only", l.wide ? 4 : 1)) return e;
+    hipLaunchKernelGGL(k_pcen_param_reduce, dim3(4u * (unsigned)n_bands), dim3(256), 0, st, (const float*)workspace, gparams,
+                       (long long)outer, (unsigned)inner, (unsigned)band_div, (unsigned)n_bands);
+    return launch_check("k_pcen_param_reduce");
 }
 
 // ---- CMVN (kpr_cmvn_kernels.h): argument checks and launch of the forward / backward C entry points ----
@@ -271,40 +251,32 @@ static int run_cmvn(bool bwd, const float* x, const float* rstd, const float* gy
     if (bits & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
     {
         const uintptr_t nb = (uintptr_t)outer * frames * inner * 4, ns = (uintptr_t)outer * inner * 4;
-        auto clash = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
-            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
-        };
-        bool bad = clash(out, nb, rstd_out, ns) || clash(out, nb, rstd, ns) || clash(rstd_out, ns, rstd, ns);
-        for (const float* in : {x, gy}) bad = bad || clash(out, nb, in, nb) || clash(rstd_out, ns, in, nb);
+        bool bad = ranges_overlap(out, nb, rstd_out, ns) || ranges_overlap(out, nb, rstd, ns) || ranges_overlap(rstd_out, ns, rstd, ns);
+        for (const float* in : {x, gy}) bad = bad || ranges_overlap(out, nb, in, nb) || ranges_overlap(rstd_out, ns, in, nb);
         if (bad) return fail(KPR_E_BADARG, "an output overlaps an input or the other output (there is no in-place form)");
     }
-    const bool v4 = inner % 4 == 0 && (bits & 15) == 0;
     const bool res = frames <= kCmvnRows * kCmvnWaves && opt(OPT_CMVN_VARIANT) == 0;
+    ColLaunch l;
+    if (int e = col_launch(outer, inner, 4, kCmvnWaves, (bits & 15) == 0, &l)) return e;
     CmvnArgs a;
     a.x = x; a.gy = gy; a.rstd = rstd; a.out = out; a.rstd_out = rstd_out;
     a.eps = eps;
     a.frames = (int)frames;
-    a.inner = (unsigned)inner;
-    a.groups_per_item = (unsigned)(v4 ? inner / 4 : inner);
-    a.n_groups = (long long)outer * a.groups_per_item;
-    const long long blocks = (a.n_groups + 63) / 64;
-    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
-    const dim3 grid((unsigned)blocks), block(64 * kCmvnWaves);
+    a.inner = l.inner;
+    a.groups_per_item = l.groups_per_item;
+    a.n_groups = l.n_groups;
     const int mode = bwd ? (norm_vars ? CMVN_BWD : CMVN_BWD_MEAN) : !norm_vars ? CMVN_FWD_MEAN : rstd_out ? CMVN_FWD_RSTD : CMVN_FWD;
     if (opt(OPT_VERBOSE))
         fprintf(stderr, "[kapre_hip] k_cmvn%s<%d,%s>: grid %lld x %d lanes, %d rows per wave, %d waves per workgroup, resident up to %d "
-                "frames; %lld frames = %lld super-block(s), norm_vars %d%s\n", bwd ? "_bwd" : "", v4 ? 4 : 1, res ? "res" : "str", blocks,
+                "frames; %lld frames = %lld super-block(s), norm_vars %d%s\n", bwd ? "_bwd" : "", l.wide ? 4 : 1, res ? "res" : "str", (long long)l.grid.x,
                 64 * kCmvnWaves, kCmvnRows, kCmvnWaves, kCmvnRows * kCmvnWaves, (long long)frames,
                 (long long)((frames + kCmvnRows * kCmvnWaves - 1) / (kCmvnRows * kCmvnWaves)), norm_vars, rstd_out ? ", rstd kept" : "");
     const hipStream_t st = (hipStream_t)stream;
-    if (v4) {
-        if (res) launch_cmvn<4, CMVN_RES>(mode, grid, block, st, a);
-        else launch_cmvn<4, CMVN_STR>(mode, grid, block, st, a);
-    } else {
-        if (res) launch_cmvn<1, CMVN_RES>(mode, grid, block, st, a);
-        else launch_cmvn<1, CMVN_STR>(mode, grid, block, st, a);
-    }
-    return launch_check(bwd ? "k_cmvn_bwd" : "k_cmvn", v4 ? 4 : 1, res ? "res" : "str");
+    with_vec<4>(l.wide, [&](auto v) {
+        if (res) launch_cmvn<v, CMVN_RES>(mode, l.grid, l.block, st, a);
+        else launch_cmvn<v, CMVN_STR>(mode, l.grid, l.block, st, a);
+    });
+    return launch_check(bwd ? "k_cmvn_bwd" : "k_cmvn", l.wide ? 4 : 1, res ? "res" : "str");
 }
 
 // ---- Resample (kpr_resample_kernels.h): the windowed-sinc tables of both directions, the tile plan, the launch ----
@@ -446,11 +418,8 @@ static int run_resample(const float* x, int64_t batch, int channels, int64_t in_
     if ((!x && in_len > 0) || !out || !table || !first) return fail(KPR_E_BADARG, "x / out / table_dev / first_dev must not be NULL");
     if ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)table) | ((uintptr_t)first)) & 3)
         return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
-    {
-        const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out;
-        const uintptr_t nx = (uintptr_t)batch * channels * in_len * 4, no = (uintptr_t)batch * channels * out_len * 4;
-        if (x && xa < oa + no && oa < xa + nx) return fail(KPR_E_BADARG, "x and out overlap");
-    }
+    if (ranges_overlap(x, (uintptr_t)batch * channels * in_len * 4, out, (uintptr_t)batch * channels * out_len * 4))
+        return fail(KPR_E_BADARG, "x and out overlap");
     const ResamplePlan pl = resample_plan(n_phases, step, n_taps);
     const long long n_blocks = (out_len + n_phases - 1) / n_phases;
     if (n_blocks * step >= (1LL << 31) - (1LL << 26))
@@ -476,8 +445,7 @@ static int run_resample(const float* x, int64_t batch, int channels, int64_t in_
     if (opt(OPT_VERBOSE))
         fprintf(stderr, "[kapre_hip] k_resample<%d>: grid %lld, lds %zu B, %d phases x %d taps, step %d; tile %d phases x %d blocks "
                 "(%d outputs), %d block groups, %d lanes\n", nch, grid, lds, n_phases, n_taps, step, pl.pt, pl.nb, pl.nb * n_phases, pl.ng, pl.threads);
-    if (nch == 2) hipLaunchKernelGGL(k_resample<2>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_resample<1>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a);
+    with_vec<2>(nch == 2, [&](auto n) { hipLaunchKernelGGL(k_resample<n>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a); });
     return launch_check("k_resample", nch);
 }
 
@@ -500,34 +468,30 @@ static int run_time_stretch(const void* x, int64_t outer, int64_t frames_in, int
         return fail(KPR_E_UNSUPPORTED, "time stretch: outer = %lld items of that size are not supported", (long long)outer);
     {
         const uintptr_t nx = (uintptr_t)outer * frames_in * inner * 8, no = (uintptr_t)outer * frames_out * inner * 8, nt = (uintptr_t)frames_out * 4;
-        auto clash = [](const void* p, uintptr_t np, const void* q, uintptr_t nq) {
-            return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
-        };
-        if (clash(out, no, x, nx)) return fail(KPR_E_BADARG, "x and out overlap (there is no in-place form)");
-        if (clash(phase_out, no / 2, x, nx) || clash(phase_out, no / 2, out, no))
+        if (ranges_overlap(out, no, x, nx)) return fail(KPR_E_BADARG, "x and out overlap (there is no in-place form)");
+        if (ranges_overlap(phase_out, no / 2, x, nx) || ranges_overlap(phase_out, no / 2, out, no))
             return fail(KPR_E_BADARG, "phase_out overlaps x or out");
         for (const void* t : {(const void*)idx, (const void*)alpha})
-            if (clash(t, nt, out, no) || clash(t, nt, phase_out, no / 2)) return fail(KPR_E_BADARG, "idx / alpha overlap an output");
+            if (ranges_overlap(t, nt, out, no) || ranges_overlap(t, nt, phase_out, no / 2))
+                return fail(KPR_E_BADARG, "idx / alpha overlap an output");
     }
-    const bool v2 = inner % 2 == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)phase_out) & 7) == 0;
+    ColLaunch l;
+    if (int e = col_launch(outer, inner, 2, kPvWaves, ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)phase_out) & 7) == 0, &l))
+        return e;
     PvArgs a;
     a.x = (const float2*)x; a.out = (float2*)out; a.phase = phase_out;
     a.idx = idx; a.alpha = alpha;
     a.frames_in = (int)frames_in; a.frames_out = (int)frames_out;
-    a.inner = (unsigned)inner;
-    a.groups_per_item = (unsigned)(v2 ? inner / 2 : inner);
-    a.n_groups = (long long)outer * a.groups_per_item;
-    const long long blocks = (a.n_groups + 63) / 64;
-    if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
-    const dim3 grid((unsigned)blocks), block(64 * kPvWaves);
+    a.inner = l.inner;
+    a.groups_per_item = l.groups_per_item;
+    a.n_groups = l.n_groups;
     if (opt(OPT_VERBOSE))
         fprintf(stderr, "[kapre_hip] k_time_stretch<%d>: grid %lld x %d lanes, %d frames per wave, %d waves per workgroup; %lld -> %lld "
-                "frames = %lld super-block(s)%s\n", v2 ? 2 : 1, blocks, 64 * kPvWaves, kPvRows, kPvWaves, (long long)frames_in,
+                "frames = %lld super-block(s)%s\n", l.wide ? 2 : 1, (long long)l.grid.x, 64 * kPvWaves, kPvRows, kPvWaves, (long long)frames_in,
                 (long long)frames_out, (long long)((frames_out + kPvRows * kPvWaves - 1) / (kPvRows * kPvWaves)),
                 phase_out ? ", phase words kept" : "");
-    if (v2) hipLaunchKernelGGL(k_time_stretch<2>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_time_stretch<1>, grid, block, 0, (hipStream_t)stream, a);
-    return launch_check("k_time_stretch", v2 ? 2 : 1);
+    with_vec<2>(l.wide, [&](auto v) { hipLaunchKernelGGL(k_time_stretch<v>, l.grid, l.block, 0, (hipStream_t)stream, a); });
+    return launch_check("k_time_stretch", l.wide ? 2 : 1);
 }
 
 static int frame_args(int64_t batch, int channels, int64_t time, int layout, int frame_length,

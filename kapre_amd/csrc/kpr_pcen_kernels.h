@@ -6,14 +6,11 @@
 //             N[t] = q[t] + a N[t+1], N[F] = 0;  gE[t] = p G + s N[t] (t >= 1), gE[0] = p G + N[0]
 //
 // Both layouts are one problem: a contiguous (outer, F, inner) tensor scanned along F; the band of inner index i is
-// i / band_div (channels_first: band_div 1, channels_last: band_div C).  A lane owns one column group -- four consecutive
-// inner indices of one outer item, loaded and stored with 16-byte accesses (V = 4; inner % 4 == 0 and 16-byte aligned
-// bases), or a single column (V = 1) -- and column groups are numbered through all outer items, so 64 consecutive groups
-// fill a wave whatever `inner` is.
+// i / band_div (channels_first: band_div 1, channels_last: band_div C).  Column groups (V = 4 or 1 floats), super-blocks of
+// W * R rows and the one barrier are those of kpr_cols.h.
 //
-// Time is tiled.  A workgroup of W waves owns 64 column groups; one step covers a super-block of W * R rows: wave w
-// loads its R rows (R independent 16-byte loads per lane in flight), runs the recurrence over them from a ZERO carry-in
-// and leaves the end value L_w in LDS.  After one barrier every wave walks the W end values in order,
+// Wave w loads its R rows (R independent 16-byte loads per lane in flight), runs the recurrence over them from a ZERO carry-in
+// and leaves the end value L_w in LDS.  After the barrier every wave walks the W end values in order,
 // c_(w+1) = a^R c_w + L_w from the state the previous super-block left -- the recurrence is linear, so the carry-in of a
 // chunk only adds a^k carry -- and thereby holds both its own carry-in and, redundantly, the state after the super-block.
 // It then runs the recurrence a second time over its registers from the true carry-in: each S[t] is produced by exactly
@@ -95,31 +92,6 @@ KPR_DEV void pcen_param_terms(float e, float g, float gr, float G, float p, floa
     s_r = s_r + g * (u * pw * pcen_ln(lu) - cr);
 }
 
-template <int V>
-struct PcenVec {
-    float v[V];
-};
-
-template <int V>
-KPR_DEV PcenVec<V> pcen_load(const float* p) {
-    PcenVec<V> r;
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-
-template <int V>
-KPR_DEV void pcen_store(float* p, const PcenVec<V>& r) {
-    if constexpr (V == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else
-        *p = r.v[0];
-}
-
 template <int V, int MODE>
 __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
     constexpr int R = kPcenRows, W = kPcenWaves;
@@ -129,19 +101,14 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
     // PARAMS: four slabs, which after the time loop hold the W waves' sums of the four parameters
     __shared__ float ends[PARAMS ? 4 : 2][W][V][64];
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long group = (long long)blockIdx.x * 64 + lane;
-    const bool live = group < a.n_groups;
-    // (a lane past the last group runs along on group 0 with its stores masked: the barrier needs every wave)
-    const long long gsafe = live ? group : 0;
-    const long long item = gsafe / a.groups_per_item;
-    const unsigned i0 = (unsigned)(gsafe - item * a.groups_per_item) * V;
-    const long long base = item * (long long)a.frames * a.inner + i0;
+    const ColGroup cg = col_group<V>(a.n_groups, a.groups_per_item);
+    const int lane = cg.lane, wave = threadIdx.x >> 6;
+    const long long base = cg.item * (long long)a.frames * a.inner + cg.i0;
 
     float ps[V], pa[V], palpha[V], pdelta[V], pr[V], pdr[V], paR[V], state[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-        const unsigned band = (i0 + v) / a.band_div;
+        const unsigned band = (cg.i0 + v) / a.band_div;
         ps[v] = a.s[band];
         palpha[v] = a.alpha[band];
         pdelta[v] = a.delta[band];
@@ -171,16 +138,16 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
     for (int sb = 0; sb < n_super; ++sb) {
         // scan position tau runs forward in time (FWD) or backward (BWD); row(tau) is the frame it names
         const int tau0 = (sb * W + wave) * R;
-        PcenVec<V> in[R];          // FWD: E.  BWD: q
-        PcenVec<V> dir[R];         // BWD: gy r u^(r-1) G, the part of gE that does not pass through S
+        ColVec<float, V> in[R];          // FWD: E.  BWD: q
+        ColVec<float, V> dir[R];         // BWD: gy r u^(r-1) G, the part of gE that does not pass through S
         // PARAMS: E[t] - S[t-1], which waits for N[t] behind the barrier.  S[t-1] is the next row of the scan: the wave's own
         // rows, and one more row of `smooth` behind the chunk (never (E - S) / a: 0 / 0 at s = 1)
-        PcenVec<V> step[PARAMS ? R : 1], srow[PARAMS ? R + 1 : 1];
+        ColVec<float, V> step[PARAMS ? R : 1], srow[PARAMS ? R + 1 : 1];
         if constexpr (PARAMS) {
 #pragma unroll
             for (int k = 0; k <= R; ++k) {
                 const int tau = tau0 + k;
-                if (tau < a.frames) srow[k] = pcen_load<V>(a.smooth + base + (long long)(a.frames - 1 - tau) * a.inner);
+                if (tau < a.frames) srow[k] = col_load<V>(a.smooth + base + (long long)(a.frames - 1 - tau) * a.inner);
                 else
 #pragma unroll
                     for (int v = 0; v < V; ++v) srow[k].v[v] = 0.0f;
@@ -192,17 +159,17 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
             const bool ok = tau < a.frames;
             const long long off = base + (long long)(BWD ? a.frames - 1 - tau : tau) * a.inner;
             if (!BWD) {
-                if (ok) in[k] = pcen_load<V>(a.x + off);
+                if (ok) in[k] = col_load<V>(a.x + off);
                 else
 #pragma unroll
                     for (int v = 0; v < V; ++v) in[k].v[v] = 0.0f;
             } else {
-                PcenVec<V> e, sm, g;
+                ColVec<float, V> e, sm, g;
                 if (ok) {
-                    e = pcen_load<V>(a.x + off);
+                    e = col_load<V>(a.x + off);
                     if constexpr (PARAMS) sm = srow[k];
-                    else sm = pcen_load<V>(a.smooth + off);
-                    g = pcen_load<V>(a.gy + off);
+                    else sm = col_load<V>(a.smooth + off);
+                    g = col_load<V>(a.gy + off);
                 }
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
@@ -260,7 +227,7 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int tau = tau0 + k;
-            PcenVec<V> o, sm;
+            ColVec<float, V> o, sm;
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 if (BWD) {
@@ -276,10 +243,10 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
                     o.v[v] = pcen_pow(fmaf(in[k].v[v], G, pdelta[v]), pr[v]) - pdr[v];
                 }
             }
-            if (OUT && live && tau < a.frames) {
+            if (OUT && cg.live && tau < a.frames) {
                 const long long off = base + (long long)(BWD ? a.frames - 1 - tau : tau) * a.inner;
-                pcen_store<V>(a.out + off, o);
-                if (MODE == PCEN_FWD_SMOOTH) pcen_store<V>(a.smooth_out + off, sm);
+                col_store<V>(a.out + off, o);
+                if (MODE == PCEN_FWD_SMOOTH) col_store<V>(a.smooth_out + off, sm);
             }
         }
     }
@@ -291,8 +258,8 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
 #pragma unroll
             for (int v = 0; v < V; ++v) ends[q][wave][v][lane] = sums[q][v];
         __syncthreads();
-        if (wave < 4 && live) {
-            PcenVec<V> o;
+        if (wave < 4 && cg.live) {
+            ColVec<float, V> o;
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 float t = ends[wave][0][v][lane];
@@ -300,7 +267,7 @@ __global__ __launch_bounds__(64 * kPcenWaves) void k_pcen(PcenArgs a) {
                 for (int w = 1; w < W; ++w) t += ends[wave][w][v][lane];
                 o.v[v] = t;
             }
-            pcen_store<V>(a.partials + (long long)wave * a.n_groups * V + group * V, o);
+            col_store<V>(a.partials + (long long)wave * a.n_groups * V + cg.group * V, o);
         }
     }
 }

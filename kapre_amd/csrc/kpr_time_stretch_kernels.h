@@ -9,13 +9,10 @@
 // The expected phase advance of the textbook phase vocoder is absent: it enters the accumulated phase as a multiple of 2 pi
 // (DESIGN 4.15).  Integer addition is associative, so the chunked sum below IS the sequential one, bit for bit.
 //
-// Geometry: k_pcen's.  A contiguous (outer, frames, inner) problem of complex64 values; a lane owns one column group -- two
-// consecutive inner indices of one outer item moved with 16-byte accesses (V = 2: inner even, 16-byte aligned bases), or one
-// column (V = 1) -- and column groups are numbered through all outer items.  A workgroup of W waves owns 64 column groups; one
-// step covers a super-block of W * R output frames, R per wave.  A wave fetches the input rows its R frames need, forms Theta
-// and |x|, sums its R phase increments from zero and leaves the word in LDS; after one barrier every wave adds the words of the
-// waves before it to the state that the previous super-block left, and writes its rows.  The LDS slab is double-buffered, which
-// makes the one barrier per super-block sufficient.
+// Column groups (V = 2 or 1 complex64 values), super-blocks of W * R OUTPUT frames and the one barrier are those of kpr_cols.h.
+// A wave fetches the input rows its R frames need, forms Theta and |x|, sums its R phase increments from zero and leaves the word
+// in LDS; after the barrier every wave adds the words of the waves before it to the state that the previous super-block left, and
+// writes its rows.
 //
 // Row indices are the same for every lane, so they come from the table as scalar loads, and the wave picks one of two forms:
 //   span form     idx[] does not fall and the R frames read at most R + 1 consecutive input rows (every rate <= 1): each INPUT row
@@ -59,41 +56,21 @@ KPR_DEV float pv_mix(float a, float one_minus_a, float lo, float hi) {
     return a * hi + one_minus_a * lo;
 }
 
-template <int V>
-struct PvVec {
-    float2 v[V];
-};
-
-template <int V>
-KPR_DEV PvVec<V> pv_load(const float2* p) {
-    PvVec<V> r;
-    if constexpr (V == 2) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        r.v[0] = make_float2(t.x, t.y); r.v[1] = make_float2(t.z, t.w);
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-
 // one output row of a lane: Y = m (cos, sin)(pi h) and, when asked for, the phase words
 template <int V>
 KPR_DEV void pv_emit(const PvArgs& a, long long off, bool live, const unsigned (&P)[V], const float (&m)[V]) {
-    float2 o[V];
+    ColVec<float2, V> o;
+    ColVec<unsigned, V> p;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         float sn, cs;
         sincospif((float)(int)P[v] * 4.656612873077392578125e-10f, &sn, &cs);
-        o[v] = make_float2(m[v] * cs, m[v] * sn);
+        o.v[v] = make_float2(m[v] * cs, m[v] * sn);
+        p.v[v] = P[v];
     }
     if (!live) return;
-    if constexpr (V == 2) {
-        *reinterpret_cast<float4*>(a.out + off) = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
-        if (a.phase) *reinterpret_cast<uint2*>(a.phase + off) = make_uint2(P[0], P[1]);
-    } else {
-        a.out[off] = o[0];
-        if (a.phase) a.phase[off] = P[0];
-    }
+    col_store<V>(a.out + off, o);
+    if (a.phase) col_store<V>(a.phase + off, p);
 }
 
 template <int V>
@@ -101,23 +78,18 @@ __global__ __launch_bounds__(64 * kPvWaves) void k_time_stretch(PvArgs a) {
     constexpr int R = kPvRows, W = kPvWaves;
     __shared__ unsigned ends[2][W][V][64];
 
-    const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long group = (long long)blockIdx.x * 64 + lane;
-    const bool live = group < a.n_groups;
-    // (a lane past the last group runs along on group 0 with its stores masked: the barrier needs every wave)
-    const long long gsafe = live ? group : 0;
-    const long long item = gsafe / a.groups_per_item;
-    const unsigned i0 = (unsigned)(gsafe - item * a.groups_per_item) * V;
-    const float2* xin = a.x + item * (long long)a.frames_in * a.inner + i0;
-    const long long out_base = item * (long long)a.frames_out * a.inner + i0;
+    const ColGroup cg = col_group<V>(a.n_groups, a.groups_per_item);
+    const int lane = cg.lane;
+    const float2* xin = a.x + cg.item * (long long)a.frames_in * a.inner + cg.i0;
+    const long long out_base = cg.item * (long long)a.frames_out * a.inner + cg.i0;
 
     // input row r of the lane's columns; the rows from frames_in on (the two padding frames; any index that is no row) are zero
-    auto row = [&](unsigned r) -> PvVec<V> {
-        PvVec<V> z;
+    auto row = [&](unsigned r) -> ColVec<float2, V> {
+        ColVec<float2, V> z;
 #pragma unroll
         for (int v = 0; v < V; ++v) z.v[v] = make_float2(0.0f, 0.0f);
-        if (r < (unsigned)a.frames_in) z = pv_load<V>(xin + (long long)r * a.inner);
+        if (r < (unsigned)a.frames_in) z = col_load<V>(xin + (long long)r * a.inner);
         return z;
     };
 
@@ -128,7 +100,7 @@ __global__ __launch_bounds__(64 * kPvWaves) void k_time_stretch(PvArgs a) {
 
     unsigned state[V];             // P[first frame of the super-block]
     {
-        const PvVec<V> z = row(0u);
+        const ColVec<float2, V> z = row(0u);
 #pragma unroll
         for (int v = 0; v < V; ++v) state[v] = pv_angle(z.v[v]);
     }
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(64 * kPvWaves) void k_time_stretch(PvArgs a) {
         for (int v = 0; v < V; ++v) tot[v] = 0u;
 
         if (nk > 0 && span) {
-            PvVec<V> in[R + 1];
+            ColVec<float2, V> in[R + 1];
 #pragma unroll
             for (int j = 0; j <= R; ++j) in[j] = row(ia[0] + (unsigned)j);
 #pragma unroll
@@ -184,7 +156,7 @@ __global__ __launch_bounds__(64 * kPvWaves) void k_time_stretch(PvArgs a) {
                 for (int v = 0; v < V; ++v) tot[v] += (unsigned)c * (th[j + 1][v] - th[j][v]);
             }
         } else if (nk > 0) {
-            PvVec<V> lo[R], hi[R];
+            ColVec<float2, V> lo[R], hi[R];
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 lo[k] = row(ia[k]);
@@ -226,14 +198,14 @@ __global__ __launch_bounds__(64 * kPvWaves) void k_time_stretch(PvArgs a) {
                     float m[V];
 #pragma unroll
                     for (int v = 0; v < V; ++v) m[v] = pv_mix(ak, om, mg[j][v], mg[j + 1][v]);
-                    pv_emit<V>(a, out_base + (long long)(t0 + k) * a.inner, live, carry, m);
+                    pv_emit<V>(a, out_base + (long long)(t0 + k) * a.inner, cg.live, carry, m);
 #pragma unroll
                     for (int v = 0; v < V; ++v) carry[v] += th[j + 1][v] - th[j][v];
                 }
         } else if (nk > 0) {
 #pragma unroll
             for (int k = 0; k < R; ++k) {
-                if (k < nk) pv_emit<V>(a, out_base + (long long)(t0 + k) * a.inner, live, carry, mk[k]);
+                if (k < nk) pv_emit<V>(a, out_base + (long long)(t0 + k) * a.inner, cg.live, carry, mk[k]);
 #pragma unroll
                 for (int v = 0; v < V; ++v) carry[v] += inc[k][v];
             }

@@ -146,6 +146,11 @@ def test_host_only_argument_checks():
                 dict(gparams=ctypes.c_void_p(0x500010)), dict(ws=fake), dict(gparams=fake)):
         assert call(**bad) == -1, bad
     assert call(frames=1 << 21, inner=1 << 10, n_bands=1 << 9, ws_bytes=1 << 40) == -2 and b"2^31" in L.kpr_last_error()
+    # the overlap predicate at its boundary: gparams is 16 * n_bands bytes.  A range that ends exactly where x begins touches x
+    # and passes on to the workspace check; one that reaches 4 bytes into x is refused before it
+    x = 0x600000
+    assert call(x=ctypes.c_void_p(x), gparams=ctypes.c_void_p(x - 16 * 3)) == -4 and b"workspace" in L.kpr_last_error()
+    assert call(x=ctypes.c_void_p(x), gparams=ctypes.c_void_p(x - 16 * 3 + 4)) == -1 and b"overlaps" in L.kpr_last_error()
 
 
 # ------------------------------------------------------------------ the layer, on CPU tensors

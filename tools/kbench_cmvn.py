@@ -46,12 +46,12 @@ BLOCKS = [
 def make_step(kind, norm_vars, want_rstd, b, t, m, dev):
     """(step, tensors kept alive, streams of block size the operation has)"""
     x = torch.rand((b, 1, t, m), device=dev) * 6 - 60
-    geom, stats = _ffi._cmvn_geometry(x, FMT)
+    geom, stats = _ffi._time_geometry(x.shape, FMT)[:3], (b, 1, m)
     if kind == "pcen":
         x = torch.rand((b, 1, t, m), device=dev)
         params = tuple(torch.from_numpy(backend.pcen_band_table(backend.pcen_parameters(0.025, 0.98, 2.0, 0.5, 1e-6)[:4], m)).to(dev))
         out = torch.empty_like(x)
-        args = (_ffi.ptr(x), *_ffi._pcen_geometry(x, FMT), *(_ffi.ptr(p) for p in params), 1e-6, _ffi.ptr(out), _ffi.ptr(None))
+        args = (_ffi.ptr(x), *_ffi._time_geometry(x.shape, FMT), *(_ffi.ptr(p) for p in params), 1e-6, _ffi.ptr(out), _ffi.ptr(None))
         return (lambda: _ffi._call("kpr_pcen_f32", dev, *args)), (x, out, params), 2
     if kind == "fwd":
         out = torch.empty_like(x)

@@ -35,7 +35,7 @@ def variants(b, t, m, dev):
         def make():
             x = torch.rand((b, 1, t, m), device=dev)
             out, smooth = torch.empty_like(x), (torch.empty_like(x) if want_smooth else None)
-            args = (_ffi.ptr(x), *_ffi._pcen_geometry(x, FMT), *(_ffi.ptr(p) for p in params), 1e-6, _ffi.ptr(out), _ffi.ptr(smooth))
+            args = (_ffi.ptr(x), *_ffi._time_geometry(x.shape, FMT), *(_ffi.ptr(p) for p in params), 1e-6, _ffi.ptr(out), _ffi.ptr(smooth))
             return (lambda: _ffi._call("kpr_pcen_f32", dev, *args)), (x, out, smooth)
         return make, 3 if want_smooth else 2
 
@@ -44,7 +44,7 @@ def variants(b, t, m, dev):
             x = torch.rand((b, 1, t, m), device=dev)
             _, smooth = _ffi.pcen(x, FMT, params, 1e-6, want_smooth=True)
             gy, gx = torch.randn_like(x), torch.empty_like(x)
-            args = (_ffi.ptr(x), _ffi.ptr(smooth), _ffi.ptr(gy), *_ffi._pcen_geometry(x, FMT), *(_ffi.ptr(p) for p in params), 1e-6,
+            args = (_ffi.ptr(x), _ffi.ptr(smooth), _ffi.ptr(gy), *_ffi._time_geometry(x.shape, FMT), *(_ffi.ptr(p) for p in params), 1e-6,
                     _ffi.ptr(gx))
             return (lambda: _ffi._call("kpr_pcen_bwd_f32", dev, *args)), (x, smooth, gy, gx)
         return make, 4
@@ -54,7 +54,7 @@ def variants(b, t, m, dev):
             x = torch.rand((b, 1, t, m), device=dev)
             _, smooth = _ffi.pcen(x, FMT, params, 1e-6, want_smooth=True)
             gy, gx = torch.randn_like(x), (torch.empty_like(x) if want_gx else None)
-            geom = _ffi._pcen_geometry(x, FMT)
+            geom = _ffi._time_geometry(x.shape, FMT)
             gp = torch.empty((4, m), device=dev)
             ws_bytes = int(_ffi.lib().kpr_pcen_bwd_params_workspace_bytes(*geom[:3]))
             ws = _ffi.workspace(ws_bytes, dev)
