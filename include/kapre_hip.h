@@ -662,6 +662,32 @@ int kpr_time_stretch_c64(const void* x, int64_t outer, int64_t frames_in, int64_
                          const float* alpha, void* out, uint32_t* phase_out /* may be NULL: (outer, frames_out, inner) phase words */,
                          kpr_stream_t stream);
 
+/* ---- HPSS: median-filter harmonic-percussive separation of a spectrogram, kapre_amd.time_frequency.HPSS --------------------
+ * x: float32 (kpr_hpss_f32) or complex64 (kpr_hpss_c64) spectrogram, (batch, frames, freq, ch) [layout = LAST] or
+ * (batch, ch, frames, freq) [FIRST], contiguous; every (batch item, channel) plane on its own.  kh, kp: odd, 3 ... 31.
+ *   H[t, f] = median of S[r(t + d, frames), f], |d| <= (kh - 1) / 2        P[t, f] = median of S[t, r(f + d, freq)], |d| <= (kp - 1) / 2
+ *   r(i, n): j = i mod 2n (non-negative); j < n ? j : 2n - 1 - j           (half-sample symmetric, defined for every n >= 1)
+ *   S = x, or sqrtf(re re + im im) of a complex x.  The median is a selection: it equals one of the window's values bit for bit
+ *   (the sign of a zero is unspecified), with NaN ordered above +Inf as in numpy.sort.
+ *   soft(X, R): Z = max(X, R); bad = Z < 2^-126; a = X / Z, c = R / Z (Z := 1 where bad); m = a^power / (a^power + c^power);
+ *               where bad: m = 0.5 if margin_h == margin_p == 1, else 0.   power = inf: m = X > R ? 1 : 0
+ *   Mh = soft(H, P margin_h),  Mp = soft(P, H margin_p), in float32; power 1 and 2 without powf
+ *   want_mask 0: out_h = x Mh, out_p = x Mp (complex64 for a complex x);  1: out_h = Mh, out_p = Mp (float32 for either x);
+ *   2 (for tests): out_h = H, out_p = P (float32)
+ * out_h / out_p: tensors in x's layout with out_ch >= ch channels, of which the call fills the first ch (so out_p = out_h + the
+ * offset of channel ch of one tensor with out_ch = 2 ch stacks harmonic and percussive channels).  Either may be NULL, not both:
+ * that side's masks and stores are skipped.  power > 0 (inf allowed), margins finite and >= 1, else KPR_E_BADARG; so are an even
+ * kh / kp or one outside 3 ... 31, pointers not aligned to their element, an output that overlaps x, and outputs that overlap
+ * each other in any way but as disjoint channel ranges of one out_ch-channel tensor.  frames * freq >= 2^30: KPR_E_UNSUPPORTED.
+ * batch, ch, frames or freq == 0: returns 0, launches nothing.  One launch, no atomics, no host reads: capturable; the same
+ * inputs give the same bits.
+ * kpr_hpss_plan (host only): the tile of the dispatch, *tile_frames x *tile_freq outputs per workgroup; tile edges for tests. */
+int kpr_hpss_plan(int64_t frames, int64_t freq, int kh, int kp, int* tile_frames, int* tile_freq);
+int kpr_hpss_f32(const float* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
+                 double margin_h, double margin_p, int want_mask, float* out_h, float* out_p, int out_ch, kpr_stream_t stream);
+int kpr_hpss_c64(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
+                 double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream);
+
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix
  * M[n][k] = 2 cos(pi (2n+1) k / (2 n_mels)) / sqrt(2 n_mels) and fb_kranges_host = NULL. */

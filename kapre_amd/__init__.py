@@ -25,6 +25,7 @@ from .time_frequency import (
     CMVN,
     GriffinLim,
     TimeStretch,
+    HPSS,
 )
 
 from . import signal
@@ -40,6 +41,7 @@ from .composed import (
     get_perfectly_reconstructing_stft_istft,
     get_stft_mag_phase,
     get_time_stretch_layer,
+    get_hpss_layer,
 )
 
 
@@ -95,6 +97,7 @@ __all__ = [
     'CMVN',
     'GriffinLim',
     'TimeStretch',
+    'HPSS',
     'Frame',
     'Energy',
     'MuLawEncoding',
@@ -109,6 +112,7 @@ __all__ = [
     'get_perfectly_reconstructing_stft_istft',
     'get_stft_mag_phase',
     'get_time_stretch_layer',
+    'get_hpss_layer',
     'Layer',
     'Sequential',
     'Model',

@@ -206,6 +206,13 @@ EXPORTS = {
                                              ctypes.POINTER(ctypes.c_int)]),
     "kpr_time_stretch_c64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # HPSS (kapre_amd/time_frequency.py)
+    "kpr_hpss_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int)]),
+    **{name: (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                             ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+       for name in ("kpr_hpss_f32", "kpr_hpss_c64")},
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -917,3 +924,40 @@ def time_stretch(x, fmt, idx, alpha, frames_out: int, want_phase: bool = False):
     phase = torch.empty(out.shape, dtype=torch.int32, device=x.device) if want_phase else None
     _call("kpr_time_stretch_c64", x.device, ptr(x), outer, t, int(frames_out), inner, ptr(idx), ptr(alpha), ptr(out), ptr(phase))
     return (out, phase) if want_phase else out
+
+
+# HPSS (kapre_amd/time_frequency.py)
+HPSS_VALUES, HPSS_MASKS, HPSS_MEDIANS = 0, 1, 2
+
+
+def hpss_plan(frames: int, freq: int, kh: int = 31, kp: int = 31):
+    """(tile_frames, tile_freq): the tile of outputs a workgroup of kpr_hpss_* owns (host only)."""
+    tf, tq = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().kpr_hpss_plan(int(frames), int(freq), int(kh), int(kp), ctypes.byref(tf), ctypes.byref(tq)), "kpr_hpss_plan")
+    return tf.value, tq.value
+
+
+def hpss(x, fmt, kh: int, kp: int, power: float, margin_h: float, margin_p: float, mode: int = HPSS_VALUES, output: str = "pair"):
+    """Median-filter harmonic-percussive separation of the rank-4 float32 / complex64 spectrogram ``x`` in one launch.
+    ``mode``: HPSS_VALUES (x times the masks, x's dtype), HPSS_MASKS or HPSS_MEDIANS (the two median-filtered spectrograms, for
+    tests), both float32.  ``output``: 'pair' -> (harmonic, percussive) as two tensors; 'both' -> one tensor with the channel
+    axis doubled, harmonic channels first; 'harmonic' / 'percussive' -> that one alone (the other side's masks and stores are
+    skipped)."""
+    import torch
+    cplx = x.is_complex()
+    b, c, t, m = dims_of(x.shape, fmt)
+    odt = torch.complex64 if cplx and mode == HPSS_VALUES else torch.float32
+    new = lambda ch: torch.empty(shape_of(fmt, b, ch, t, m), dtype=odt, device=x.device)
+    at = lambda ten, off: ctypes.c_void_p(ten.data_ptr() + off * ten.element_size()) if ten.numel() else ctypes.c_void_p(0)
+    if output == "both":
+        res = new(2 * c)
+        out_ch, ph, pp = 2 * c, at(res, 0), at(res, c if fmt in ("channels_last", CHANNELS_LAST) else c * t * m)
+    elif output == "pair":
+        res = (new(c), new(c))
+        out_ch, ph, pp = c, ptr(res[0]), ptr(res[1])
+    else:
+        res = new(c)
+        out_ch, ph, pp = (c, ptr(res), ctypes.c_void_p(0)) if output == "harmonic" else (c, ctypes.c_void_p(0), ptr(res))
+    _call("kpr_hpss_c64" if cplx else "kpr_hpss_f32", x.device, ptr(x), b, c, t, m, layout(fmt) if isinstance(fmt, str) else int(fmt),
+          int(kh), int(kp), float(power), float(margin_h), float(margin_p), int(mode), ph, pp, out_ch)
+    return res

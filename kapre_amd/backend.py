@@ -635,3 +635,49 @@ def phase_vocoder(x, rate, data_format='default'):
     rate = time_stretch_parameters(rate)
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return time_frequency._time_stretch_run(x, rate, fmt, time_frequency._TS_CONSTS)
+
+
+# --------------------------------------------------------------------------------------
+# harmonic-percussive separation
+# --------------------------------------------------------------------------------------
+def _hpss_pair(value, what):
+    """A scalar, or a (harmonic, percussive) pair of scalars, as a pair of plain numbers (no bools, no arrays)."""
+    pair = tuple(value) if isinstance(value, (tuple, list)) else (value, value)
+    if len(pair) != 2:
+        raise ValueError('HPSS: %s must be a number or a (harmonic, percussive) pair, got %r' % (what, value))
+    for v in pair:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError('HPSS: %s must be a number or a (harmonic, percussive) pair of numbers, got %r' % (what, value))
+    return pair
+
+
+def hpss_parameters(kernel_size=31, power=2.0, margin=1.0):
+    """Validated ((kh, kp), power, (mh, mp)) of an HPSS: the window lengths odd integers in 3 ... 31, ``power`` > 0 (``inf``
+    allowed), the margins finite and >= 1; each of ``kernel_size`` and ``margin`` a scalar or a (harmonic, percussive) pair.
+    A bool, an even or out-of-range size, a margin < 1 or a power <= 0 raises ``ValueError``."""
+    sizes = _hpss_pair(kernel_size, 'kernel_size')
+    for k in sizes:
+        if float(k) != int(k) or int(k) % 2 == 0 or not 3 <= int(k) <= 31:
+            raise ValueError('HPSS: kernel_size must be odd and in 3 ... 31, got %r' % (kernel_size,))
+    margins = _hpss_pair(margin, 'margin')
+    for m in margins:
+        if not (np.isfinite(float(m)) and float(m) >= 1.0):
+            raise ValueError('HPSS: margin must be finite and >= 1, got %r' % (margin,))
+    if isinstance(power, (bool, np.bool_)) or np.ndim(power) != 0 or not isinstance(power, (int, float, np.integer, np.floating)) \
+            or not float(power) > 0.0:
+        raise ValueError('HPSS: power must be a number > 0 (inf for a hard mask), got %r' % (power,))
+    return (int(sizes[0]), int(sizes[1])), float(power), (float(margins[0]), float(margins[1]))
+
+
+def hpss(x, kernel_size=31, power=2.0, margin=1.0, mask=False, data_format='default'):
+    """Median-filter harmonic-percussive separation of a spectrogram batch on the GPU (``kapre_amd.HPSS`` as a function; the
+    operation of ``librosa.decompose.hpss``): returns ``(harmonic, percussive)``, each of x's shape -- (b, frame, freq, ch) for
+    ``channels_last``, (b, ch, frame, freq) for ``channels_first``.  ``x`` is a float32 spectrogram or the complex64 output of
+    ``STFT``, whose magnitude makes the masks, which then multiply it.  ``mask=True`` returns the two float32 masks.  One kernel
+    launch.  The results carry no ``grad_fn``: an input that requires grad is detached."""
+    from . import time_frequency
+
+    validate_data_format_str(data_format)
+    sizes, power, margins = hpss_parameters(kernel_size, power, margin)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return time_frequency._hpss_run(x, sizes, power, margins, bool(mask), fmt, 'pair')

@@ -3,7 +3,7 @@
 ``get_stft_magnitude_layer`` (composed.py:32-135), ``get_melspectrogram_layer`` (:138-261),
 ``get_log_frequency_spectrogram_layer`` (:264-385), ``get_perfectly_reconstructing_stft_istft``
 (:388-417), ``get_stft_mag_phase`` (:420-511): same signatures, defaults and layer order as the
-reference; ``get_time_stretch_layer`` is this package's own.  The returned ``Sequential`` exposes the individual layers through ``.layers`` (users
+reference; ``get_time_stretch_layer`` and ``get_hpss_layer`` are this package's own.  The returned ``Sequential`` exposes the individual layers through ``.layers`` (users
 may re-add them to their own model, composed.py:1-13) and, when called, runs the whole chain as a
 single fused HIP launch (kapre_amd.time_frequency.fuse_and_run).
 
@@ -20,6 +20,7 @@ from .time_frequency import (
     MagnitudeToDecibel,
     ApplyFilterbank,
     TimeStretch,
+    HPSS,
 )
 from . import backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
@@ -194,6 +195,42 @@ def get_time_stretch_layer(
     chain = Sequential(name=name)
     chain.add(STFT(**stft_args))
     chain.add(TimeStretch(rate, data_format=input_data_format))
+    chain.add(InverseSTFT(forward_window_name='hann_window', input_data_format=input_data_format,
+                          output_data_format=input_data_format, **shared))
+    return chain
+
+
+def get_hpss_layer(
+    n_fft=2048,
+    win_length=None,
+    hop_length=None,
+    output='harmonic',
+    kernel_size=31,
+    power=2.0,
+    margin=1.0,
+    input_shape=None,
+    input_data_format='default',
+    name='hpss',
+):
+    """``Sequential([STFT, HPSS, InverseSTFT])``: a waveform batch in, its harmonic or percussive part out, in
+    ``input_data_format`` (this package's own; ``librosa.effects.harmonic`` / ``percussive``).  ``output='both'`` doubles the
+    waveform channels: the harmonic ones first, then the percussive ones.  Hann window of ``win_length`` (default ``n_fft``),
+    ``hop_length`` defaulting to ``win_length // 4``, no padding, the matched synthesis window: F analysis frames give
+    ``(F - 1) * hop_length + win_length`` samples."""
+    backend.validate_data_format_str(input_data_format)
+    backend.hpss_parameters(kernel_size, power, margin)
+    if win_length is None:
+        win_length = n_fft
+    if hop_length is None:
+        hop_length = win_length // 4
+    shared = dict(n_fft=n_fft, win_length=win_length, hop_length=hop_length)
+    stft_args = dict(shared, window_name='hann_window', pad_begin=False, pad_end=False, input_data_format=input_data_format,
+                     output_data_format=input_data_format)
+    if input_shape is not None:
+        stft_args['input_shape'] = input_shape
+    chain = Sequential(name=name)
+    chain.add(STFT(**stft_args))
+    chain.add(HPSS(kernel_size=kernel_size, power=power, margin=margin, output=output, data_format=input_data_format))
     chain.add(InverseSTFT(forward_window_name='hann_window', input_data_format=input_data_format,
                           output_data_format=input_data_format, **shared))
     return chain

@@ -88,6 +88,7 @@
 #include "kpr_resample_kernels.h"
 #include "kpr_griffin_lim_kernels.h"
 #include "kpr_time_stretch_kernels.h"
+#include "kpr_hpss_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -1004,6 +1005,24 @@ int kpr_time_stretch_plan(int64_t frames_out, int64_t inner, int* rows_per_wave,
 int kpr_time_stretch_c64(const void* x, int64_t outer, int64_t frames_in, int64_t frames_out, int64_t inner, const int32_t* idx,
                          const float* alpha, void* out, uint32_t* phase_out, kpr_stream_t stream) {
     return run_time_stretch(x, outer, frames_in, frames_out, inner, idx, alpha, out, phase_out, stream);
+}
+
+/* ---- HPSS (kpr_hpss_kernels.h) ------------------------------------------------------------------ */
+int kpr_hpss_plan(int64_t frames, int64_t freq, int kh, int kp, int* tile_frames, int* tile_freq) {
+    int hh, hp;
+    if (frames < 0 || freq < 0 || !tile_frames || !tile_freq) return fail(KPR_E_BADARG, "bad frames/freq or NULL result");
+    if (int e = hpss_half_windows(kh, kp, &hh, &hp)) return e;
+    *tile_frames = kHpTile;
+    *tile_freq = kHpTile;
+    return 0;
+}
+int kpr_hpss_f32(const float* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
+                 double margin_h, double margin_p, int want_mask, float* out_h, float* out_p, int out_ch, kpr_stream_t stream) {
+    return run_hpss<false>(x, batch, ch, frames, freq, layout, kh, kp, power, margin_h, margin_p, want_mask, out_h, out_p, out_ch, stream);
+}
+int kpr_hpss_c64(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
+                 double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream) {
+    return run_hpss<true>(x, batch, ch, frames, freq, layout, kh, kp, power, margin_h, margin_p, want_mask, out_h, out_p, out_ch, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN,
-// Resample and TimeStretch entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
+// Resample, TimeStretch and HPSS entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
 // kpr_augment_kernels.h, kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h,
-// kpr_time_stretch_kernels.h).  The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch
+// kpr_time_stretch_kernels.h, kpr_hpss_kernels.h).  The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch
 // (kpr_host.h; the device side is kpr_cols.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
@@ -492,6 +492,85 @@ static int run_time_stretch(const void* x, int64_t outer, int64_t frames_in, int
                 phase_out ? ", phase words kept" : "");
     with_vec<2>(l.wide, [&](auto v) { hipLaunchKernelGGL(k_time_stretch<v>, l.grid, l.block, 0, (hipStream_t)stream, a); });
     return launch_check("k_time_stretch", l.wide ? 2 : 1);
+}
+
+// ---- HPSS (kpr_hpss_kernels.h): argument checks and the one launch of the harmonic-percussive separation ----
+// x: float32 (CPLX = false) or complex64 spectrogram of `ch` channels in `layout`; out_h / out_p: tensors of out_ch channels in
+// the same layout, of which each output fills the first ch.  The window instance: 15 slots when both windows fit, else 31.
+static int hpss_half_windows(int kh, int kp, int* hh, int* hp) {
+    if (kh < 3 || kh > 31 || kp < 3 || kp > 31 || kh % 2 == 0 || kp % 2 == 0)
+        return fail(KPR_E_BADARG, "hpss: window lengths must be odd and in 3 ... 31, got kh = %d, kp = %d", kh, kp);
+    *hh = (kh - 1) / 2;
+    *hp = (kp - 1) / 2;
+    return 0;
+}
+template <bool CPLX>
+static int run_hpss(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
+                    double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (batch < 0 || ch < 0 || frames < 0 || freq < 0 || (unsigned)layout > 1u) return fail(KPR_E_BADARG, "bad batch/ch/frames/freq/layout");
+    int hh, hp;
+    if (int e = hpss_half_windows(kh, kp, &hh, &hp)) return e;
+    if (!(power > 0.0) || !(margin_h >= 1.0) || !(margin_p >= 1.0) || std::isinf(margin_h) || std::isinf(margin_p))
+        return fail(KPR_E_BADARG, "hpss: power must be > 0 (inf allowed) and the margins finite and >= 1");
+    if ((unsigned)want_mask > 2u) return fail(KPR_E_BADARG, "hpss: want_mask must be 0 (values), 1 (masks) or 2 (medians)");
+    if (out_ch < ch) return fail(KPR_E_BADARG, "hpss: out_ch = %d is less than ch = %d", out_ch, ch);
+    const long long lim = 1LL << 30;
+    if (freq > 0 && frames > (lim - 1) / freq)
+        return fail(KPR_E_UNSUPPORTED, "hpss: %lld frames x %lld bins: planes of 2^30 elements or more are not supported",
+                    (long long)frames, (long long)freq);
+    if (batch == 0 || ch == 0 || frames == 0 || freq == 0) return 0;
+    if (!x) return fail(KPR_E_BADARG, "x must not be NULL");
+    if (!out_h && !out_p) return fail(KPR_E_BADARG, "hpss: out_h and out_p must not both be NULL");
+    const unsigned ein = CPLX ? 8 : 4, eout = (CPLX && !want_mask) ? 8 : 4;
+    if ((((uintptr_t)x) & (ein - 1)) || ((((uintptr_t)out_h) | ((uintptr_t)out_p)) & (eout - 1)))
+        return fail(KPR_E_BADARG, "x / out_h / out_p are not aligned to their element size");
+    const long long plane = frames * freq;
+    if (batch > (1LL << 59) / (plane * out_ch)) return fail(KPR_E_UNSUPPORTED, "hpss: batch = %lld items of that size are not supported", (long long)batch);
+    const bool cl = layout == KPR_CHANNELS_LAST;
+    {
+        // the bytes an output touches lie within [p, p + span): the first ch channels of a (batch, out_ch) tensor
+        const uintptr_t nx = (uintptr_t)batch * ch * plane * ein;
+        const uintptr_t slot = cl ? 1 : (uintptr_t)plane;                          // elements from one channel to the next
+        const uintptr_t span = ((uintptr_t)(batch - 1) * out_ch * plane + (cl ? (uintptr_t)(plane - 1) * out_ch + ch : (uintptr_t)ch * plane)) * eout;
+        if (ranges_overlap(out_h, span, x, nx) || ranges_overlap(out_p, span, x, nx))
+            return fail(KPR_E_BADARG, "hpss: an output overlaps x (there is no in-place form)");
+        if (ranges_overlap(out_h, span, out_p, span)) {
+            // the one allowed way to interleave: both fill channel ranges of ONE out_ch-channel tensor that do not meet
+            const uintptr_t lo = std::min((uintptr_t)out_h, (uintptr_t)out_p), hi = std::max((uintptr_t)out_h, (uintptr_t)out_p);
+            const uintptr_t d = (hi - lo) / eout;
+            if ((hi - lo) % eout || d % slot || d / slot < (uintptr_t)ch || d / slot + ch > (uintptr_t)out_ch)
+                return fail(KPR_E_BADARG, "hpss: out_h and out_p overlap");
+        }
+    }
+    const long long tiles_t = (frames + kHpTile - 1) / kHpTile, tiles_f = (freq + kHpTile - 1) / kHpTile;
+    const long long blocks = (long long)batch * ch * tiles_t * tiles_f;
+    if (blocks > 0x7fffffffLL || (long long)batch * ch > 0x7fffffffLL)
+        return fail(KPR_E_UNSUPPORTED, "hpss: too many tiles: %lld", blocks);
+    HpssArgs a;
+    a.x = x; a.out_h = out_h; a.out_p = out_p;
+    a.frames = (int)frames; a.freq = (int)freq; a.ch = ch;
+    a.hh = hh; a.hp = hp;
+    a.tiles_t = (int)tiles_t; a.tiles_f = (int)tiles_f;
+    if (cl) {
+        a.x_b = plane * ch; a.x_c = 1; a.x_t = freq * ch; a.x_f = ch;
+        a.o_b = plane * out_ch; a.o_c = 1; a.o_t = freq * out_ch; a.o_f = out_ch;
+    } else {
+        a.x_b = plane * ch; a.x_c = plane; a.x_t = freq; a.x_f = 1;
+        a.o_b = plane * out_ch; a.o_c = plane; a.o_t = freq; a.o_f = 1;
+    }
+    a.mode = want_mask;
+    a.pmode = std::isinf(power) ? 3 : power == 1.0 ? 1 : power == 2.0 ? 2 : 0;
+    a.power = (float)power; a.mh = (float)margin_h; a.mp = (float)margin_p;
+    a.bad_value = (margin_h == 1.0 && margin_p == 1.0) ? 0.5f : 0.0f;
+    const bool small = hh <= 7 && hp <= 7;
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_hpss<%d,%s>: %lld tiles of %d x %d, windows %d x %d, %s\n", small ? 15 : 31, CPLX ? "c64" : "f32",
+                blocks, kHpTile, kHpTile, kh, kp, want_mask == 2 ? "medians" : want_mask ? "masks" : "values");
+    const dim3 grid((unsigned)blocks), block(64 * kHpWaves);
+    if (small) hipLaunchKernelGGL((k_hpss<7, CPLX>), grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_hpss<15, CPLX>), grid, block, 0, (hipStream_t)stream, a);
+    return launch_check("k_hpss", small ? 15 : 31, CPLX ? "c64" : "f32");
 }
 
 static int frame_args(int64_t batch, int channels, int64_t time, int layout, int frame_length,

@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim`` and ``TimeStretch`` are this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim``, ``TimeStretch`` and ``HPSS`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -37,6 +37,7 @@ __all__ = [
     'CMVN',
     'GriffinLim',
     'TimeStretch',
+    'HPSS',
 ]
 
 
@@ -1055,6 +1056,82 @@ class TimeStretch(Layer):
     def get_config(self):
         config = super(TimeStretch, self).get_config()
         config.update({'rate': self.rate, 'data_format': self.data_format_original})
+        return config
+
+
+def _hpss_run(x, sizes, power, margins, mask, fmt, output):
+    """``x`` through the separation with validated parameters in the resolved data format ``fmt``; ``output`` as in
+    ``_ffi.hpss``."""
+    import torch
+
+    if len(x.shape) != 4:
+        raise ValueError('HPSS expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('HPSS has float32 kernels only; got a %s input (cast it to float32 / complex64)' % (x.dtype,))
+    cplx = x.is_complex() if isinstance(x, torch.Tensor) else np.iscomplexobj(x)
+    if isinstance(x, torch.Tensor):
+        x = x.detach()
+    x = _ffi.as_device(x, torch.complex64 if cplx else torch.float32)
+    return _ffi.hpss(x, fmt, sizes[0], sizes[1], power, margins[0], margins[1], _ffi.HPSS_MASKS if mask else _ffi.HPSS_VALUES, output)
+
+
+@register_keras_serializable(package='Kapre')
+class HPSS(Layer):
+    """Median-filter harmonic-percussive source separation of a spectrogram (Fitzgerald 2010 with Driedger's margins;
+    ``librosa.decompose.hpss``, ``librosa.effects.harmonic`` / ``percussive``).  Per (batch item, channel) plane S of T frames
+    and F bins, with the window lengths (kh, kp) = ``kernel_size`` and the margins (mh, mp) = ``margin``:
+
+        H[t, f] = median of S[r(t + d, T), f], |d| <= (kh - 1) / 2          (along time: what is steady is harmonic)
+        P[t, f] = median of S[t, r(f + d, F)], |d| <= (kp - 1) / 2          (along frequency: what is broadband is percussive)
+        r(i, n): j = i mod 2n; j if j < n else 2n - 1 - j                   (the edge repeats: d c b a | a b c d | d c b a)
+        soft(X, R) = (X / Z)^power / ((X / Z)^power + (R / Z)^power), Z = max(X, R);  where Z < 2^-126: 0.5 if both margins are 1,
+                     else 0;  power = inf: 1 where X > R, else 0
+        Mh = soft(H, P mh),  Mp = soft(P, H mp);   harmonic = S Mh,  percussive = S Mp
+
+    The median is a selection -- it equals one of its inputs bit for bit -- and NaN orders above +Inf as in ``numpy.sort``, so a
+    single NaN bin makes NaN only its own bin of the outputs; everything else is what it would be with +Inf there.  The same
+    inputs give the same bits.  A complex64 input (the output of ``STFT``) is separated by the masks of its magnitude: the
+    outputs are complex64 and go straight into ``InverseSTFT`` (``composed.get_hpss_layer``).
+
+    ``output``: 'harmonic', 'percussive', or 'both' -- one tensor with the channel axis doubled, the harmonic channels first,
+    then the percussive ones: two input planes for a CNN, twice the waveform channels behind ``InverseSTFT``.  ``mask=True``
+    returns the float32 masks instead.  ``kernel_size`` and ``margin`` are a scalar or a (harmonic, percussive) pair: sizes odd
+    and in 3 ... 31, margins >= 1, ``power`` > 0 or ``inf`` (``ValueError`` otherwise).  (b, frame, freq, ch) for
+    ``channels_last``, (b, ch, frame, freq) for ``channels_first``; one kernel launch (kpr_hpss_f32 / kpr_hpss_c64).  The input
+    must have rank 4 (``ValueError``); a float64 / complex128 input or a float64 layer raises ``TypeError``.
+
+    The output carries no ``grad_fn``: the layer is not differentiable (a median has no useful gradient), and an input that
+    requires grad is detached."""
+
+    def __init__(self, kernel_size=31, power=2.0, margin=1.0, output='both', mask=False, data_format='default', **kwargs):
+        super(HPSS, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):
+            data_format = data_format['config']
+        if output not in ('harmonic', 'percussive', 'both'):
+            raise ValueError("HPSS: output must be 'harmonic', 'percussive' or 'both', got %r" % (output,))
+        self.kernel_size, self.power, self.margin = backend.hpss_parameters(kernel_size, power, margin)
+        self.output = output
+        self.mask = bool(mask)
+        self.data_format_original = data_format
+        self.data_format = _resolve_format(data_format)
+
+    def compute_output_shape(self, input_shape):
+        """the input's shape; 'both' doubles the channel axis (``None`` stays ``None``)"""
+        b, c, f, k = _ffi.dims_of(input_shape, self.data_format)
+        if self.output == 'both' and c is not None:
+            c = 2 * c
+        return _ffi.shape_of(self.data_format, b, c, f, k)
+
+    def call(self, x):
+        if self._f64:
+            raise TypeError('HPSS has float32 kernels only; build the layer with dtype float32')
+        return _hpss_run(x, self.kernel_size, self.power, self.margin, self.mask, self.data_format, self.output)
+
+    def get_config(self):
+        config = super(HPSS, self).get_config()
+        config.update({'kernel_size': list(self.kernel_size), 'power': self.power, 'margin': list(self.margin),
+                       'output': self.output, 'mask': self.mask, 'data_format': self.data_format_original})
         return config
 
 
