@@ -152,6 +152,9 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *   "cmvn_variant" 0 = automatic (default: kpr_cmvn_f32 / kpr_cmvn_bwd_f32 keep a series of up to resident_frames frames
  *                  (kpr_cmvn_plan) in registers -- one read, one write) | 1 = the streamed form, two sweeps, for every frame count
  *                  (A/B runs, tests; bit-identical results)
+ *   "lfilter_variant" 0 = automatic (default: kpr_lfilter_f32 walks every series with one workgroup, or cuts the time axis into
+ *                  segments when batch * channels is too small to fill the device) | 1 = whole-signal for every shape | 2 = segmented
+ *                  for every shape (A/B runs, tests; results within the error bound of each other, not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -687,6 +690,35 @@ int kpr_hpss_f32(const float* x, int64_t batch, int ch, int64_t frames, int64_t 
                  double margin_h, double margin_p, int want_mask, float* out_h, float* out_p, int out_ch, kpr_stream_t stream);
 int kpr_hpss_c64(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
                  double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream);
+
+/* ---- LFilter: one biquad IIR section along time on a waveform, kapre_amd.signal.LFilter ------------------------------------
+ * x: float32 waveform, (batch, time, ch) [layout = LAST] or (batch, ch, time) [FIRST], contiguous; out: the same shape.
+ * coef = (b0, b1, b2, a1, a2), already divided by a0, passed as doubles and used as such.  Every (batch item, channel) series:
+ *   reverse 0:  y[t] = b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2],   x, y = 0 for t < 0
+ *   reverse 1:  y[t] = b0 x[t] + b1 x[t+1] + b2 x[t+2] - a1 y[t+1] - a2 y[t+2],   x, y = 0 for t >= len   (the adjoint of reverse 0)
+ * in float64 arithmetic on the float32 samples, rounded to float32 once at the store: for a stable filter the output is the
+ * float32 rounding of the float64 result up to the float64 error of the recurrence.  Required: every coefficient finite,
+ * |a2| < 1 and |a1| < 1 + a2 (the stability triangle), else KPR_E_BADARG.  a1 == a2 == 0 (a pure FIR section) runs without a scan.
+ * Two forms: whole-signal (one workgroup walks a series; one launch, one read, one write) and segmented (the time axis is cut into
+ * segments of kpr_lfilter_plan's size: three launches on the stream, two reads, one write; chosen when batch * channels is small).
+ * Option "lfilter_variant" forces one.  Each form gives the same bits from the same inputs; the two agree within the error
+ * bound, not bit for bit.  The segmented form needs `workspace`: kpr_lfilter_workspace_bytes(...) bytes, 8-byte aligned, clear of
+ * x and out (KPR_E_WORKSPACE when NULL or short; 0 bytes for a series of at most one segment; not read by the whole-signal form).
+ * Pointers 4-byte aligned; 16-byte accesses for contiguous series whose length is a multiple of four behind 16-byte aligned
+ * pointers.  x and out must not overlap (there is no in-place form).  2^30 elements or more per signal (per batch item for
+ * LAST): KPR_E_UNSUPPORTED.  batch == 0 or len == 0: returns 0, launches nothing.  No atomics, no host reads: capturable.
+ * Non-finite input: with t0 the first non-finite sample of a series in scan order, every output before t0 (after it for
+ * reverse 1) equals bit for bit the output of the call in which that sample is 0; from t0 on the series is unspecified when a1 or
+ * a2 is non-zero, and a pure FIR section is affected at t0 ... t0 + 2 (t0 - 2 ... t0) only.  Other series are never touched.
+ * kpr_lfilter_plan (host only): out[0 ... 4] = samples per lane, per wave, per workgroup step, per segment, and the form
+ * (1 whole-signal, 2 segmented) the dispatch uses for this shape under the current "lfilter_variant"; seams for tests.
+ * kpr_lfilter_carry (host only): M (row-major 2 x 2) with (y[n-1], y[n-2]) = M (y[-1], y[-2]) for zero input, 0 <= n <= 2^20,
+ * from the impulse response of 1 / A(z) in long double. */
+int kpr_lfilter_plan(int64_t batch, int channels, int64_t len, int layout, int* out /* 5 */);
+int kpr_lfilter_carry(const double coef[5], int64_t n, double M[4]);
+int64_t kpr_lfilter_workspace_bytes(int64_t batch, int channels, int64_t len, int layout);
+int kpr_lfilter_f32(const float* x, int64_t batch, int channels, int64_t len, int layout, const double coef[5] /* b0 b1 b2 a1 a2 */,
+                    int reverse, float* out, void* workspace, size_t workspace_bytes, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

@@ -29,7 +29,7 @@ from .time_frequency import (
 )
 
 from . import signal
-from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis
 
 from . import augmentation
 from .augmentation import SpecAugment, ChannelSwap
@@ -104,6 +104,9 @@ __all__ = [
     'MuLawDecoding',
     'LogmelToMFCC',
     'Resample',
+    'LFilter',
+    'Preemphasis',
+    'Deemphasis',
     'SpecAugment',
     'ChannelSwap',
     'get_stft_magnitude_layer',

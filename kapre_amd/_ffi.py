@@ -213,6 +213,13 @@ EXPORTS = {
                              ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
        for name in ("kpr_hpss_f32", "kpr_hpss_c64")},
+    # LFilter (kapre_amd/signal.py)
+    "kpr_lfilter_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "kpr_lfilter_carry": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]),
+    "kpr_lfilter_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "kpr_lfilter_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -835,6 +842,53 @@ def resample(x, fmt, plan: ResamplePlan, out_len: int):
     out = torch.empty(shape_of(fmt, b, c, int(out_len)), dtype=torch.float32, device=x.device)
     _call("kpr_resample_f32", x.device, ptr(x), b, c, t, layout(fmt), ptr(plan.table), ptr(plan.first), plan.n_phases,
           plan.n_taps, plan.step, int(out_len), ptr(out))
+    return out
+
+
+# LFilter (kapre_amd/signal.py)
+LFILTER_WHOLE, LFILTER_SEGMENTED = 1, 2
+E_BADARG = -1
+
+
+def _coef5(coef):
+    """(b0, b1, b2, a1, a2) as the five C doubles of the ABI."""
+    c = [float(v) for v in coef]
+    if len(c) != 5:
+        raise ValueError('a section is (b0, b1, b2, a1, a2), got %d values' % len(c))
+    return (ctypes.c_double * 5)(*c)
+
+
+def lfilter_plan(batch: int, channels: int, length: int, fmt):
+    """(samples_per_lane, samples_per_wave, samples_per_step, samples_per_segment, form) of kpr_lfilter_f32's dispatch for
+    this shape under the current ``lfilter_variant``; form is LFILTER_WHOLE or LFILTER_SEGMENTED (host only)."""
+    out = (ctypes.c_int * 5)()
+    check(lib().kpr_lfilter_plan(int(batch), int(channels), int(length), fmt if isinstance(fmt, int) else layout(fmt), out),
+          "kpr_lfilter_plan")
+    return tuple(int(v) for v in out)
+
+
+def lfilter_carry(coef, n: int) -> np.ndarray:
+    """The (2, 2) float64 matrix that carries the state (y[-1], y[-2]) over ``n`` samples of zero input (host only).
+    ``ValueError`` for coefficients outside the stability triangle or an ``n`` the library does not answer for."""
+    m = (ctypes.c_double * 4)()
+    rc = lib().kpr_lfilter_carry(_coef5(coef), int(n), m)
+    if rc == E_BADARG:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_lfilter_carry")
+    return np.array(list(m), dtype=np.float64).reshape(2, 2)
+
+
+def lfilter(x, fmt, coef, reverse: bool):
+    """One biquad section ``coef`` = (b0, b1, b2, a1, a2) along time over the float32 waveform ``x``, from the first sample to
+    the last or with ``reverse`` from the last to the first (the adjoint: the backward pass of the other direction)."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    out = torch.empty_like(x)
+    ws_bytes = int(lib().kpr_lfilter_workspace_bytes(b, c, t, layout(fmt)))
+    if ws_bytes < 0:
+        check(-1, "kpr_lfilter_workspace_bytes")
+    ws = workspace(ws_bytes, x.device)
+    _call("kpr_lfilter_f32", x.device, ptr(x), b, c, t, layout(fmt), _coef5(coef), int(bool(reverse)), ptr(out), ptr(ws), ws_bytes)
     return out
 
 

@@ -13,7 +13,8 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   returns integers and ends the tape; ``PCEN`` keeps its smoother ``S`` (the forward kernel's second output) and runs
   one backward kernel, the forward scan in reversed time (input gradient only: its parameters are constants);
   ``CMVN`` keeps its output and ``rstd`` per column and runs one backward kernel, two sums along time and a sweep;
-  ``Resample^T`` is the forward's polyphase kernel with the adjoint table;
+  ``Resample^T`` is the forward's polyphase kernel with the adjoint table; ``LFilter^T`` is its sections in reverse order,
+  each the forward kernel scanning in the other direction;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -383,9 +384,29 @@ def _functions():
             g = g.contiguous().to(torch.float32)
             return _ffi.resample(g, ctx.data_format, ctx.adjoint_plan, ctx.in_len), None, None, None, None
 
+    class LFilterFn(torch.autograd.Function):
+        """y = F x, a cascade of biquad sections, each a linear map whose adjoint is the same section run in the other
+        direction: backward = the sections in reverse order, each one launch sequence of the forward kernel with ``reverse``
+        flipped.  ``plan``: a tuple of (coef, reverse) per launch."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, plan):
+            ctx.data_format, ctx.plan = data_format, plan
+            y = x.detach()
+            for coef, reverse in plan:
+                y = _ffi.lfilter(y, data_format, coef, reverse)
+            return y
+
+        @staticmethod
+        def backward(ctx, g):
+            g = g.contiguous().to(torch.float32)
+            for coef, reverse in reversed(ctx.plan):
+                g = _ffi.lfilter(g, ctx.data_format, coef, not reverse)
+            return g, None, None
+
     _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
-               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn)
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn)
     return _FN
 
 
@@ -458,3 +479,7 @@ def cmvn(x, data_format, norm_vars, eps):
 
 def resample(x, data_format, forward_plan, adjoint_plan, out_len):
     return _functions()['resample'].apply(x, data_format, forward_plan, adjoint_plan, out_len)
+
+
+def lfilter(x, data_format, plan):
+    return _functions()['lfilter'].apply(x, data_format, tuple(plan))

@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn``, ``resample`` and ``griffin_lim`` have no counterpart there.
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn``, ``resample``, ``lfilter`` and ``griffin_lim`` have no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -535,6 +535,131 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_
         _RESAMPLE_SUPPORTED.add(params)
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return _resample_run(x, params, fmt)
+
+
+# --------------------------------------------------------------------------------------
+# biquad IIR filtering
+# --------------------------------------------------------------------------------------
+LFILTER_MAX_SECTIONS = 8
+BIQUAD_KINDS = ('lowpass', 'highpass', 'bandpass', 'notch', 'allpass', 'peaking', 'lowshelf', 'highshelf')
+
+
+def lfilter_sections(sos):
+    """Validated second-order sections: ``sos`` is array-like (n, 6) or (6,) in scipy's row convention (b0, b1, b2, a0, a1, a2)
+    with 1 <= n <= 8 -> a tuple of n tuples (b0, b1, b2, a1, a2) of Python floats, divided by a0 in float64.  ``ValueError``
+    for another shape, a value that is not finite, a0 == 0, or (a1, a2) outside the stability triangle |a2| < 1,
+    |a1| < 1 + a2."""
+    try:
+        s = np.array(sos, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('lfilter: sos must be array-like of shape (n, 6) or (6,), got %r' % (sos,))
+    if s.ndim == 1:
+        s = s[None, :]
+    if s.ndim != 2 or s.shape[1] != 6 or not 1 <= s.shape[0] <= LFILTER_MAX_SECTIONS:
+        raise ValueError('lfilter: sos must have shape (n, 6) or (6,) with 1 <= n <= %d, got shape %s'
+                         % (LFILTER_MAX_SECTIONS, tuple(np.shape(sos))))
+    if not np.all(np.isfinite(s)):
+        raise ValueError('lfilter: every coefficient must be finite, got %r' % (s.tolist(),))
+    out = []
+    for i, row in enumerate(s):
+        if row[3] == 0.0:
+            raise ValueError('lfilter: section %d has a0 = 0' % i)
+        b0, b1, b2, a1, a2 = (float(v) for v in np.concatenate([row[:3], row[4:]]) / row[3])
+        if not (abs(a2) < 1.0 and abs(a1) < 1.0 + a2):
+            raise ValueError('lfilter: section %d is not stable: a1 = %r, a2 = %r lie outside the triangle |a2| < 1, '
+                             '|a1| < 1 + a2' % (i, a1, a2))
+        out.append((b0, b1, b2, a1, a2))
+    return tuple(out)
+
+
+def sos_from_ba(b, a):
+    """One section (1, 6) in scipy's convention from transfer-function coefficients of order <= 2 (``b`` and ``a`` of one to
+    three values, padded with zeros), float64."""
+    b, a = np.atleast_1d(np.asarray(b, dtype=np.float64)), np.atleast_1d(np.asarray(a, dtype=np.float64))
+    if b.ndim != 1 or a.ndim != 1 or not 1 <= b.size <= 3 or not 1 <= a.size <= 3:
+        raise ValueError('sos_from_ba: b and a hold one to three coefficients each (order <= 2), got %d and %d'
+                         % (b.size, a.size))
+    row = np.zeros((1, 6), dtype=np.float64)
+    row[0, :b.size] = b
+    row[0, 3:3 + a.size] = a
+    return row
+
+
+def biquad_sos(kind, sample_rate, freq, q=0.7071067811865476, gain_db=0.0):
+    """One biquad section (1, 6) in scipy's convention, normalised to a0 = 1, from the RBJ audio-EQ-cookbook formulas, in float64 -- the formulas
+    behind ``torchaudio.functional.*_biquad``.  ``kind``: 'lowpass', 'highpass', 'bandpass' (constant 0 dB peak gain), 'notch',
+    'allpass', 'peaking', 'lowshelf', 'highshelf'; ``gain_db`` is read by the last three.  0 < freq < sample_rate / 2 and
+    q > 0 (``ValueError``)."""
+    if kind not in BIQUAD_KINDS:
+        raise ValueError('biquad_sos: kind must be one of %s, got %r' % (', '.join(BIQUAD_KINDS), kind))
+    for name, v in (('sample_rate', sample_rate), ('freq', freq), ('q', q), ('gain_db', gain_db)):
+        if isinstance(v, bool) or np.ndim(v) != 0 or not np.isfinite(float(v)):
+            raise ValueError('biquad_sos: %s must be a finite number, got %r' % (name, v))
+    fs, f, q, gain_db = float(sample_rate), float(freq), float(q), float(gain_db)
+    if not (fs > 0.0 and 0.0 < f < 0.5 * fs):
+        raise ValueError('biquad_sos: 0 < freq < sample_rate / 2 is required, got freq %r at %r' % (freq, sample_rate))
+    if not q > 0.0:
+        raise ValueError('biquad_sos: q must be positive, got %r' % (q,))
+    w0 = 2.0 * np.pi * f / fs
+    cw, alpha = float(np.cos(w0)), float(np.sin(w0)) / (2.0 * q)
+    A = 10.0 ** (gain_db / 40.0)
+    if kind == 'lowpass':
+        b, a = [(1 - cw) / 2, 1 - cw, (1 - cw) / 2], [1 + alpha, -2 * cw, 1 - alpha]
+    elif kind == 'highpass':
+        b, a = [(1 + cw) / 2, -(1 + cw), (1 + cw) / 2], [1 + alpha, -2 * cw, 1 - alpha]
+    elif kind == 'bandpass':
+        b, a = [alpha, 0.0, -alpha], [1 + alpha, -2 * cw, 1 - alpha]
+    elif kind == 'notch':
+        b, a = [1.0, -2 * cw, 1.0], [1 + alpha, -2 * cw, 1 - alpha]
+    elif kind == 'allpass':
+        b, a = [1 - alpha, -2 * cw, 1 + alpha], [1 + alpha, -2 * cw, 1 - alpha]
+    elif kind == 'peaking':
+        b, a = [1 + alpha * A, -2 * cw, 1 - alpha * A], [1 + alpha / A, -2 * cw, 1 - alpha / A]
+    else:
+        r = 2.0 * np.sqrt(A) * alpha
+        if kind == 'lowshelf':
+            b = [A * ((A + 1) - (A - 1) * cw + r), 2 * A * ((A - 1) - (A + 1) * cw), A * ((A + 1) - (A - 1) * cw - r)]
+            a = [(A + 1) + (A - 1) * cw + r, -2 * ((A - 1) + (A + 1) * cw), (A + 1) + (A - 1) * cw - r]
+        else:
+            b = [A * ((A + 1) + (A - 1) * cw + r), -2 * A * ((A - 1) + (A + 1) * cw), A * ((A + 1) + (A - 1) * cw - r)]
+            a = [(A + 1) - (A - 1) * cw + r, 2 * ((A - 1) - (A + 1) * cw), (A + 1) - (A - 1) * cw - r]
+    return np.array([b + a], dtype=np.float64) / a[0]                  # a0 = 1, as scipy.signal's designs
+
+
+def _lfilter_run(x, plan, fmt):
+    """``x`` (rank 3) through the launches ``plan`` = ((coef, reverse), ...); ``fmt`` is resolved."""
+    import torch
+
+    from . import autograd
+    if len(x.shape) != 3:
+        raise ValueError('lfilter expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('lfilter takes float32 waveforms (its arithmetic is float64 inside); got a float64 input '
+                        '(cast it to float32)')
+    if autograd.needs_grad(x):
+        return autograd.lfilter(autograd.prep(x, 'float32'), fmt, plan)
+    x = _ffi.as_device(x, torch.float32)
+    for coef, reverse in plan:
+        x = _ffi.lfilter(x, fmt, coef, reverse)
+    return x
+
+
+def lfilter(x, sos, data_format='default', reverse=False):
+    """A cascade of biquad sections along time over a waveform batch on the GPU.  (b, time, ch) for ``channels_last``,
+    (b, ch, time) for ``channels_first``; float32 in and out, the same shape.  ``sos``: (n, 6) or (6,) rows
+    (b0, b1, b2, a0, a1, a2) as in ``scipy.signal``, 1 <= n <= 8; every section, with zero initial state,
+
+        y[t] = (b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2]) / a0
+
+    in float64 arithmetic with the float64 coefficients, rounded to float32 once per section -- the float32 rounding of
+    ``scipy.signal.lfilter`` on the float64 copy of the input, section by section.  ``reverse`` runs every section from the
+    last sample to the first (the adjoint; forward then reverse is zero-phase filtering).  A tensor that ``requires_grad``
+    gets a ``grad_fn`` whose backward is the sections in reverse order in the other direction.  ``ValueError`` for a
+    malformed or unstable ``sos`` (``lfilter_sections``), ``TypeError`` for a float64 input."""
+    validate_data_format_str(data_format)
+    sections = lfilter_sections(sos)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return _lfilter_run(x, tuple((c, bool(reverse)) for c in sections), fmt)
 
 
 # --------------------------------------------------------------------------------------

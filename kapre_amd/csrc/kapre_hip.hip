@@ -41,14 +41,18 @@
 //                             given magnitude with the momentum term and the convergence sums, the per-item convergence figure
 //   kpr_time_stretch_kernels.h phase-vocoder time stretching of a complex spectrogram: a running sum of 32-bit angle words along time
 //                             in the same geometry (chunk sums through LDS, one barrier per super-block)
+//   kpr_lfilter_kernels.h     one biquad IIR section along time on a waveform (signal.LFilter): lanes run along time, float64
+//                             inside; carries across lanes, waves and steps through companion-matrix powers; a whole-signal
+//                             and a segmented (three-launch) form; the reverse scan is the adjoint
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
-// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h next to their kernel headers.
+// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h, kpr_host_lfilter.h next to their kernel headers.
 // This file: the C ABI -- the extern "C" entry points, grouped as in include/kapre_hip.h.
 //
 // gfx950 only: wave64, v_mfma_f32_16x16x4_f32, 160 KiB LDS.  No CUDA/compat paths.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -89,6 +93,7 @@
 #include "kpr_griffin_lim_kernels.h"
 #include "kpr_time_stretch_kernels.h"
 #include "kpr_hpss_kernels.h"
+#include "kpr_lfilter_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -97,6 +102,7 @@
 #include "kpr_host_mel.h"
 #include "kpr_host_ops.h"
 #include "kpr_host_griffin_lim.h"
+#include "kpr_host_lfilter.h"
 
 // ==========================================================================================
 // C ABI
@@ -139,7 +145,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -1023,6 +1029,35 @@ int kpr_hpss_f32(const float* x, int64_t batch, int ch, int64_t frames, int64_t 
 int kpr_hpss_c64(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
                  double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream) {
     return run_hpss<true>(x, batch, ch, frames, freq, layout, kh, kp, power, margin_h, margin_p, want_mask, out_h, out_p, out_ch, stream);
+}
+
+/* ---- LFilter (kpr_lfilter_kernels.h) ------------------------------------------------------------ */
+int kpr_lfilter_plan(int64_t batch, int channels, int64_t len, int layout, int* out) {
+    if (!out) return fail(KPR_E_BADARG, "out is NULL");
+    if (int e = lfilter_dims(batch, channels, len, layout)) return e;
+    out[0] = kLfLane;
+    out[1] = kLfWaveSamples;
+    out[2] = kLfStep;
+    out[3] = kLfSeg;
+    out[4] = lfilter_form(batch, channels, len);
+    return 0;
+}
+int kpr_lfilter_carry(const double coef[5], int64_t n, double M[4]) {
+    if (!M) return fail(KPR_E_BADARG, "M is NULL");
+    if (int e = lfilter_coef(coef)) return e;
+    if (n < 0 || n > kLfCarryMax) return fail(KPR_E_BADARG, "chunk length %lld outside [0, 2^20]", (long long)n);
+    std::vector<std::array<double, 4>> m;
+    lfilter_carries(coef[3], coef[4], 0, {n}, &m);
+    std::copy(m[0].begin(), m[0].end(), M);
+    return 0;
+}
+int64_t kpr_lfilter_workspace_bytes(int64_t batch, int channels, int64_t len, int layout) {
+    if (lfilter_dims(batch, channels, len, layout)) return -1;
+    return (int64_t)lfilter_workspace(batch, channels, len);
+}
+int kpr_lfilter_f32(const float* x, int64_t batch, int channels, int64_t len, int layout, const double coef[5], int reverse, float* out,
+                    void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
+    return run_lfilter(x, batch, channels, len, layout, coef, reverse, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

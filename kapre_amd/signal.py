@@ -4,7 +4,8 @@ constructor signatures, validation, get_config() keys and output shapes; the ari
 libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with a DCT-II matrix).
 MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.mu_law_encoding / mu_law_decoding
 (kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32).  Resample has no counterpart in the reference: it is
-the step in front of every front end (kpr_resample_f32)."""
+the step in front of every front end (kpr_resample_f32).  Neither have LFilter, Preemphasis and Deemphasis: biquad filtering of
+the waveform itself (kpr_lfilter_f32)."""
 import math
 
 import numpy as np
@@ -13,7 +14,8 @@ from . import _ffi, autograd, backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
-__all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample']
+__all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample', 'LFilter', 'Preemphasis',
+           'Deemphasis']
 
 
 def _resolve_format(fmt):
@@ -285,4 +287,86 @@ class Resample(Layer):
         config.update({'orig_freq': self.orig_freq, 'new_freq': self.new_freq,
                        'lowpass_filter_width': self.lowpass_filter_width, 'rolloff': self.rolloff,
                        'data_format': self.data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class LFilter(Layer):
+    """A cascade of biquad IIR sections along time over the waveform (``backend.lfilter``): pre-emphasis, DC blockers,
+    de-emphasis, shelving and peaking equalisers (``backend.biquad_sos``), loudness weighting.  ``sos``: array-like (n, 6) or
+    (6,) in ``scipy.signal``'s row convention (b0, b1, b2, a0, a1, a2), 1 <= n <= 8, every section stable (``ValueError``
+    otherwise).  ``zero_phase`` runs every section forward and then every section from the last sample to the
+    first, from zero states: ``scipy.signal.sosfiltfilt`` with ``padlen=0`` without its steady-state initial conditions.
+
+    (batch, time, ch) for ``channels_last``, (batch, ch, time) for ``channels_first``; the output has the input's shape.
+    numpy or torch, float32 (a float64 input raises ``TypeError``).  The arithmetic is float64 inside the kernel with the
+    float64 coefficients: each section's output is the float32 rounding of ``scipy.signal.lfilter`` on the float64 copy of
+    its input.  Differentiable with respect to the waveform (the sections in reverse order in the other direction).
+
+    Non-finite input: with t0 the first NaN / Inf sample of a series, every output before t0 (after it, for a pass in
+    reverse) equals bit for bit the output of the call in which that sample is 0; from t0 on that series is unspecified when
+    a1 or a2 is non-zero (a recurrence does not forget), a pure FIR section is affected at t0 ... t0 + 2 only, and other series
+    are never touched."""
+
+    def __init__(self, sos, zero_phase=False, data_format='default', **kwargs):
+        super(LFilter, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        self._sections = backend.lfilter_sections(sos)
+        rows = np.array(sos, dtype=np.float64)
+        self.sos = [[float(v) for v in row] for row in (rows[None, :] if rows.ndim == 1 else rows)]
+        self.zero_phase = bool(zero_phase)
+        # zero_phase: the whole cascade forward, then the whole cascade from the last sample to the first
+        self._plan = tuple((c, r) for r in ((False, True) if self.zero_phase else (False,)) for c in self._sections)
+        self.data_format_str = data_format
+        self.data_format = _resolve_format(data_format)
+        self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
+
+    def compute_output_shape(self, input_shape):
+        """the input's shape"""
+        return tuple(input_shape)
+
+    def call(self, x):
+        return backend._lfilter_run(x, self._plan, self.data_format)
+
+    def get_config(self):
+        config = super(LFilter, self).get_config()
+        config.update({'sos': [list(row) for row in self.sos], 'zero_phase': self.zero_phase,
+                       'data_format': self.data_format_str})
+        return config
+
+
+def _emphasis_coef(coef):
+    if isinstance(coef, bool) or np.ndim(coef) != 0 or not isinstance(coef, (int, float, np.integer, np.floating)):
+        raise ValueError('coef must be a number, got %r' % (coef,))
+    if not abs(float(coef)) < 1.0:
+        raise ValueError('|coef| < 1 is required, got %r' % (coef,))
+    return float(coef)
+
+
+@register_keras_serializable(package='Kapre')
+class Preemphasis(LFilter):
+    """y[t] = x[t] - coef x[t-1] along time (``LFilter`` with the section [1, -coef, 0, 1, 0, 0]: a pure FIR launch)."""
+
+    def __init__(self, coef=0.97, data_format='default', **kwargs):
+        self.coef = _emphasis_coef(coef)
+        super(Preemphasis, self).__init__([1.0, -self.coef, 0.0, 1.0, 0.0, 0.0], data_format=data_format, **kwargs)
+
+    def get_config(self):
+        config = Layer.get_config(self)
+        config.update({'coef': self.coef, 'data_format': self.data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class Deemphasis(LFilter):
+    """y[t] = x[t] + coef y[t-1] along time, the inverse of ``Preemphasis`` (``LFilter`` with the section
+    [1, 0, 0, 1, -coef, 0])."""
+
+    def __init__(self, coef=0.97, data_format='default', **kwargs):
+        self.coef = _emphasis_coef(coef)
+        super(Deemphasis, self).__init__([1.0, 0.0, 0.0, 1.0, -self.coef, 0.0], data_format=data_format, **kwargs)
+
+    def get_config(self):
+        config = Layer.get_config(self)
+        config.update({'coef': self.coef, 'data_format': self.data_format_str})
         return config
