@@ -440,6 +440,13 @@ int kpr_spec_augment_draw(int32_t* table, int64_t n_items, int n_time_masks, int
 int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table, int64_t n_items, int n_time_masks,
                                int n_freq_masks, int n_time, int n_freq, float mask_value, kpr_stream_t stream);
 
+/* kpr_index_draw: out[item] = an index uniform in [0, n_choices), n_items device int32 (augmentation.Reverb: the impulse response
+ * of every batch item).  The same 16-byte state, generator and rules as kpr_spec_augment_draw: Philox4x32-10, counter
+ * (item, 0, calls_lo, calls_hi), key (seed_lo, seed_hi) -> r0; out[item] = mulhi32(r0, n_choices); calls advances by one (also for
+ * n_items == 0).  n_choices < 1 or n_items < 0: KPR_E_BADARG; more than 2^20 items: KPR_E_UNSUPPORTED.  One launch, one workgroup,
+ * no host reads: capturable. */
+int kpr_index_draw(int32_t* out, int64_t n_items, int n_choices, void* state, kpr_stream_t stream);
+
 /* ChannelSwap (tf.gather along the channel axis): x, out viewed as (outer, n_ch, inner) elements of elem_bytes = 4
  * (float32) or 8 (complex64); out[o][c][:] = x[o][perm_host[c]][:].  channels_first: outer = batch, inner = the rest;
  * channels_last: outer = everything in front of the channel axis, inner = 1.
@@ -719,6 +726,31 @@ int kpr_lfilter_carry(const double coef[5], int64_t n, double M[4]);
 int64_t kpr_lfilter_workspace_bytes(int64_t batch, int channels, int64_t len, int layout);
 int kpr_lfilter_f32(const float* x, int64_t batch, int channels, int64_t len, int layout, const double coef[5] /* b0 b1 b2 a1 a2 */,
                     int reverse, float* out, void* workspace, size_t workspace_bytes, kpr_stream_t stream);
+
+/* ---- Convolve: a short complex FIR along the frame axis of a complex spectrogram, kapre_amd.signal.Convolve ----------------
+ * The middle launch of the partitioned overlap-save convolution (block length L, n_fft = 2 L, hop L): between kpr_stft_f32 with a
+ * rectangular window and kpr_istft_f32 with the synthesis window [0] * L + [1] * L.
+ * x: complex64 (outer, frames_in, inner), contiguous -> out: (outer, frames_out, inner); frames_out is the caller's choice.
+ * channels_first: outer = batch * ch, inner = n_freq, band_div = 1; channels_last: outer = batch, inner = n_freq * ch,
+ * band_div = ch; the bin of inner index i is i / band_div and n_freq = inner / band_div (inner % band_div != 0: KPR_E_BADARG).
+ * h: complex64 DEVICE table (n_ir, n_part, n_freq), 1 <= n_part <= 32, n_ir >= 1 (KPR_E_BADARG otherwise).
+ * idx: `items` DEVICE int32, one filter number per BATCH ITEM (outer % items == 0; the outer / items channels of an item share
+ * its filter), or NULL: filter 0 for every item.  An entry outside [0, n_ir) is clamped into it: the kernel never reads outside
+ * the table, whatever idx holds, and never reads idx on the host.
+ *   out[o, k, i] = sum_{p = 0}^{n_part - 1} x[o, k - p, i] h[idx[o / (outer / items)], p, i / band_div]
+ * with x[o, r, i] = 0 for r < 0 and r >= frames_in.  The sum runs in ascending p from +0, every term as the four FMAs
+ * re += xr hr; re -= xi hi; im += xr hi; im += xi hr in that order; a term whose input row is outside x is skipped.  So the same
+ * inputs give the same bits whatever the launch shape (no atomics), and a non-finite bin of x reaches the rows k ... k + n_part - 1
+ * of its own column only.
+ * x / h / out 8-byte, idx 4-byte aligned; 16-byte accesses when inner is even and x and out are 16-byte aligned.  x == out or any
+ * overlap of out with x, h or idx: KPR_E_BADARG, as are negative sizes and NULL x / h / out.  frames_in * inner or
+ * frames_out * inner >= 2^30: KPR_E_UNSUPPORTED.  outer, frames_out or inner == 0: returns 0, launches nothing.  One launch, no
+ * workspace, no host reads: capturable.
+ * kpr_spec_fir_plan (host only): out[0 ... 2] = output rows per wave, waves per workgroup (a workgroup covers their product of
+ * consecutive output frames per step) and the compile-time bucket (4, 8, 16 or 32) that n_part runs in; seams for tests. */
+int kpr_spec_fir_plan(int64_t frames_out, int64_t inner, int n_part, int* out /* 3 */);
+int kpr_spec_fir_c64(const void* x, int64_t outer, int64_t frames_in, int64_t inner, int band_div, const void* h, int n_ir, int n_part,
+                     const int32_t* idx /* may be NULL */, int64_t items, void* out, int64_t frames_out, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

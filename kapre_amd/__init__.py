@@ -29,10 +29,10 @@ from .time_frequency import (
 )
 
 from . import signal
-from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve
 
 from . import augmentation
-from .augmentation import SpecAugment, ChannelSwap
+from .augmentation import SpecAugment, ChannelSwap, Reverb
 
 from .composed import (
     get_stft_magnitude_layer,
@@ -107,8 +107,10 @@ __all__ = [
     'LFilter',
     'Preemphasis',
     'Deemphasis',
+    'Convolve',
     'SpecAugment',
     'ChannelSwap',
+    'Reverb',
     'get_stft_magnitude_layer',
     'get_melspectrogram_layer',
     'get_log_frequency_spectrogram_layer',

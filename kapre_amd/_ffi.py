@@ -220,6 +220,12 @@ EXPORTS = {
     "kpr_lfilter_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_size_t, ctypes.c_void_p]),
+    # Convolve (kapre_amd/signal.py) and Reverb (kapre_amd/augmentation.py)
+    "kpr_spec_fir_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "kpr_spec_fir_c64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "kpr_index_draw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -631,6 +637,15 @@ def spec_augment_apply(x, table, n_time_masks, n_freq_masks, n_time, n_freq, mas
     return out
 
 
+def index_draw(state, n_items: int, n_choices: int):
+    """``n_items`` int32 indices uniform in [0, n_choices), drawn on the device from ``state`` (int64[2] there: seed, calls;
+    calls advances by one)."""
+    import torch
+    out = torch.empty((int(n_items),), dtype=torch.int32, device=state.device)
+    _call("kpr_index_draw", state.device, ptr(out), int(n_items), int(n_choices), ptr(state))
+    return out
+
+
 def channel_gather(x, ch_axis: int, perm):
     """``x`` (float32 / complex64) with the channels of axis ``ch_axis`` in the order ``perm`` (tf.gather)."""
     import torch
@@ -1015,3 +1030,25 @@ def hpss(x, fmt, kh: int, kp: int, power: float, margin_h: float, margin_p: floa
     _call("kpr_hpss_c64" if cplx else "kpr_hpss_f32", x.device, ptr(x), b, c, t, m, layout(fmt) if isinstance(fmt, str) else int(fmt),
           int(kh), int(kp), float(power), float(margin_h), float(margin_p), int(mode), ph, pp, out_ch)
     return res
+
+
+# Convolve (kapre_amd/signal.py) and Reverb (kapre_amd/augmentation.py)
+def spec_fir_plan(frames_out: int, inner: int, n_part: int):
+    """(rows_per_wave, waves_per_group, bucket): the time tiling kpr_spec_fir_c64 uses and the compile-time bucket that
+    ``n_part`` partitions run in (host only)."""
+    out = (ctypes.c_int * 3)()
+    check(lib().kpr_spec_fir_plan(int(frames_out), int(inner), int(n_part), out), "kpr_spec_fir_plan")
+    return tuple(int(v) for v in out)
+
+
+def spec_fir(x, fmt, h, idx, frames_out: int):
+    """A complex FIR along the frame axis of the rank-4 complex64 ``x``: ``frames_out`` frames, output frame k the sum over p of
+    input frame k - p (zero outside ``x``) times h[idx[item], p, bin].  ``h``: complex64 device table (n_ir, n_part, n_freq);
+    ``idx``: int32 device tensor of one filter number per batch item, or None for filter 0."""
+    import torch
+    b, c, _, m = dims_of(x.shape, fmt)
+    outer, t, inner, band_div, _ = _time_geometry(x.shape, fmt)
+    out = torch.empty(shape_of(fmt, b, c, int(frames_out), m), dtype=torch.complex64, device=x.device)
+    _call("kpr_spec_fir_c64", x.device, ptr(x), outer, t, inner, band_div, ptr(h), int(h.shape[0]), int(h.shape[1]), ptr(idx), b,
+          ptr(out), int(frames_out))
+    return out

@@ -6,6 +6,9 @@ types are the reference's; with ``training`` in ``(None, False)`` both return th
 ``(seed, calls)``), so a training step copies nothing from the host and a captured graph draws new masks at every
 replay.  The stream is this package's own: TensorFlow's generator is not reproduced (and could not be).  ``set_seed``
 makes runs repeatable; the layer's config carries no seed, as upstream.
+
+``Reverb`` has no counterpart in the reference: room-impulse-response augmentation of the waveform, one impulse response per
+batch item drawn from the same device generator (``kpr_index_draw``), applied by ``backend.fftconvolve``'s three launches.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from . import _ffi, autograd, backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
-__all__ = ['SpecAugment', 'ChannelSwap', 'set_seed']
+__all__ = ['SpecAugment', 'ChannelSwap', 'Reverb', 'set_seed']
 
 _seed = None          # what set_seed gave; None: OS entropy at the first use of a device
 _states = {}          # device index -> int64[2] on that device: (seed, calls) as kpr_spec_augment_draw reads them
@@ -205,4 +208,54 @@ class SpecAugment(Layer):
                 'data_format': _config_format(self.data_format),
             }
         )
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class Reverb(Layer):
+    """Room-impulse-response augmentation of a waveform batch: in training every batch item is convolved with one of the
+    impulse responses ``irs`` (array-like (n_ir, len) or (len,)), drawn on the device by ``kpr_index_draw`` from the generator
+    that ``SpecAugment`` uses (``set_seed`` makes a run repeatable bit for bit; a captured graph draws anew at every replay).
+    The output has the input's shape: the first ``time`` samples of the full convolution, causally aligned (sample t depends on
+    the input up to t).  ``normalize`` scales every impulse response to unit energy, once, on the host.  The channels of an
+    item share its impulse response.  With ``training`` in ``(None, False)`` the layer returns its input OBJECT and launches
+    nothing.  float32; differentiable with respect to the waveform.  ``last_index`` is the device int32 vector drawn by the
+    last training call."""
+
+    def __init__(self, irs, normalize=True, input_data_format='default', **kwargs):
+        super(Reverb, self).__init__(**kwargs)
+        self.input_data_format = _resolve_format(input_data_format)
+        h = backend.convolve_irs(irs)
+        self.irs = h.tolist()
+        self.normalize = bool(normalize)
+        if self.normalize:
+            energy = np.sqrt(np.sum(h * h, axis=1, keepdims=True))
+            if np.any(energy == 0.0):
+                raise ValueError('Reverb: an impulse response of zero energy cannot be normalised')
+            h = h / energy
+        self._plan = backend.ConvolvePlan(h)
+        self.last_index = None
+
+    def compute_output_shape(self, input_shape):
+        """the input's shape"""
+        return tuple(input_shape)
+
+    def call(self, x, training=None):
+        if training in (None, False):
+            return x
+        if len(x.shape) != 3:
+            raise ValueError('Reverb expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+        if _ffi.is_f64(x):
+            raise TypeError('Reverb has float32 kernels only; got a float64 input (cast it to float32)')
+        import torch
+
+        x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+        t = _ffi.dims_of(x.shape, self.input_data_format)[2]
+        self.last_index = _ffi.index_draw(device_state(x.device), x.shape[0], self._plan.n_ir)
+        return backend._convolve_run(x, self._plan, self.input_data_format, 'full', index=self.last_index, out_len=t)
+
+    def get_config(self):
+        config = super(Reverb, self).get_config()
+        config.update({'irs': self.irs, 'normalize': self.normalize,
+                       'input_data_format': _config_format(self.input_data_format)})
         return config

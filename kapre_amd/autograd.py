@@ -14,7 +14,8 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   one backward kernel, the forward scan in reversed time (input gradient only: its parameters are constants);
   ``CMVN`` keeps its output and ``rstd`` per column and runs one backward kernel, two sums along time and a sweep;
   ``Resample^T`` is the forward's polyphase kernel with the adjoint table; ``LFilter^T`` is its sections in reverse order,
-  each the forward kernel scanning in the other direction;
+  each the forward kernel scanning in the other direction; ``Convolve^T`` is the forward's three launches with the filter
+  table of the time-reversed impulse responses (which are constants: no gradient reaches them);
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -404,7 +405,35 @@ def _functions():
                 g = _ffi.lfilter(g, ctx.data_format, coef, not reverse)
             return g, None, None
 
-    _FN = dict(stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
+    class ConvolveFn(torch.autograd.Function):
+        """y = the samples [first, first + n_out) of x * h, a linear map of the waveform: backward = the same three launches
+        with the table of the time-reversed impulse responses on the cotangent, zero-extended to the full length where the
+        forward trimmed it, read at [len - 1, len - 1 + T).  The impulse responses are constants and get no gradient."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, plan, idx, first, n_out):
+            from . import backend
+            ctx.data_format, ctx.plan, ctx.idx, ctx.first, ctx.n_out = data_format, plan, idx, first, n_out
+            ctx.t_axis = 1 if data_format == _CH_LAST_STR else 2
+            ctx.t_in = x.shape[ctx.t_axis]
+            full = backend._convolve_full(x.detach(), data_format, plan, idx)
+            return full.narrow(ctx.t_axis, first, n_out).contiguous()
+
+        @staticmethod
+        def backward(ctx, g):
+            from . import backend
+            g = g.contiguous().to(torch.float32)
+            n_full = ctx.t_in + ctx.plan.ir_len - 1
+            if ctx.first != 0 or ctx.n_out != n_full:
+                shape = list(g.shape)
+                shape[ctx.t_axis] = n_full
+                gfull = torch.zeros(shape, dtype=torch.float32, device=g.device)
+                gfull.narrow(ctx.t_axis, ctx.first, ctx.n_out).copy_(g)
+                g = gfull
+            back = backend._convolve_full(g, ctx.data_format, ctx.plan, ctx.idx, adjoint=True)
+            return back.narrow(ctx.t_axis, ctx.plan.ir_len - 1, ctx.t_in).contiguous(), None, None, None, None, None
+
+    _FN = dict(convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
                mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn)
     return _FN
@@ -483,3 +512,7 @@ def resample(x, data_format, forward_plan, adjoint_plan, out_len):
 
 def lfilter(x, data_format, plan):
     return _functions()['lfilter'].apply(x, data_format, tuple(plan))
+
+
+def convolve(x, data_format, plan, idx, first, n_out):
+    return _functions()['convolve'].apply(x, data_format, plan, idx, first, n_out)

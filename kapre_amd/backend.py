@@ -3,7 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
 ``get_window_fn`` (backend.py:58-100), ``validate_data_format_str`` (:103-123),
 ``magnitude_to_decibel`` (:126-194), ``filterbank_mel`` (:197-231), ``filterbank_log`` (:234-299),
-``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn``, ``resample``, ``lfilter`` and ``griffin_lim`` have no counterpart there.
+``mu_law_encoding`` (:302-319), ``mu_law_decoding`` (:322-341).  ``pcen``, ``cmvn``, ``resample``, ``lfilter``, ``fftconvolve`` and ``griffin_lim`` have no counterpart there.
 
 Constants that the reference builds once on the host through TensorFlow/librosa (windows, the mel
 and log filterbanks) are built here once on the host in numpy (float64 arithmetic, float32
@@ -660,6 +660,246 @@ def lfilter(x, sos, data_format='default', reverse=False):
     sections = lfilter_sections(sos)
     fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
     return _lfilter_run(x, tuple((c, bool(reverse)) for c in sections), fmt)
+
+
+# --------------------------------------------------------------------------------------
+# convolution with an impulse response (partitioned overlap-save)
+# --------------------------------------------------------------------------------------
+CONVOLVE_BLOCKS = (256, 512, 1024)
+CONVOLVE_PREFERRED_PARTITIONS = 16        # the block rule: the smallest block with at most this many partitions
+CONVOLVE_MAX_PARTITIONS = 32              # what kpr_spec_fir_c64 takes
+CONVOLVE_MAX_IR = CONVOLVE_MAX_PARTITIONS * CONVOLVE_BLOCKS[-1]
+CONVOLVE_TABLE_MAX_BYTES = 256 << 20
+CONVOLVE_MODES = ('full', 'same', 'valid')
+
+
+def convolve_block(ir_len, block_size=None):
+    """The block length L of the partitioned convolution with an impulse response of ``ir_len`` samples: the smallest of
+    256, 512, 1024 that cuts it into at most 16 partitions, else 1024.  ``block_size`` overrides the rule with one of the
+    three.  ``ValueError`` for an impulse response longer than 32 * 1024 = 32768 samples, for one that a given
+    ``block_size`` cuts into more than 32 partitions, and for any other ``block_size``."""
+    n = int(ir_len)
+    if n < 1:
+        raise ValueError('convolve: the impulse response must hold at least one sample, got %d' % n)
+    if n > CONVOLVE_MAX_IR:
+        raise ValueError('convolve: an impulse response of %d samples is beyond the limit of %d (%d partitions of %d samples)'
+                         % (n, CONVOLVE_MAX_IR, CONVOLVE_MAX_PARTITIONS, CONVOLVE_BLOCKS[-1]))
+    if block_size is not None:
+        if isinstance(block_size, bool) or not isinstance(block_size, (int, np.integer)) or int(block_size) not in CONVOLVE_BLOCKS:
+            raise ValueError('convolve: block_size must be one of %s, got %r' % (CONVOLVE_BLOCKS, block_size))
+        L = int(block_size)
+        if -(-n // L) > CONVOLVE_MAX_PARTITIONS:
+            raise ValueError('convolve: block_size %d cuts an impulse response of %d samples into %d partitions, beyond the '
+                             'limit of %d' % (L, n, -(-n // L), CONVOLVE_MAX_PARTITIONS))
+        return L
+    for L in CONVOLVE_BLOCKS:
+        if -(-n // L) <= CONVOLVE_PREFERRED_PARTITIONS:
+            return L
+    return CONVOLVE_BLOCKS[-1]
+
+
+def convolve_irs(ir):
+    """The impulse responses as a float64 (n_ir, len) host array: ``ir`` is array-like (len,) or (n_ir, len), finite, with
+    n_ir >= 1 and len >= 1 (``ValueError``).  They are constants: a torch tensor is read once, on the host, and gets no
+    gradient."""
+    if hasattr(ir, 'detach'):
+        ir = ir.detach().cpu().numpy()
+    try:
+        h = np.array(ir, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('convolve: ir must be array-like of shape (len,) or (n_ir, len), got %r' % (ir,))
+    if h.ndim == 1:
+        h = h[None, :]
+    if h.ndim != 2 or h.shape[0] < 1 or h.shape[1] < 1:
+        raise ValueError('convolve: ir must have shape (len,) or (n_ir, len) with n_ir, len >= 1, got shape %s'
+                         % (tuple(np.shape(ir)),))
+    if not np.all(np.isfinite(h)):
+        raise ValueError('convolve: every sample of ir must be finite')
+    return np.ascontiguousarray(h)
+
+
+def _convolve_table_bytes(n_ir, n_part, L):
+    nbytes = n_ir * n_part * (L + 1) * 8
+    if nbytes > CONVOLVE_TABLE_MAX_BYTES:
+        raise ValueError('convolve: the filter table of %d impulse responses x %d partitions x %d bins takes %d bytes '
+                         '(%.1f MiB), beyond the limit of %d MiB' % (n_ir, n_part, L + 1, nbytes, nbytes / 2.0 ** 20,
+                                                                     CONVOLVE_TABLE_MAX_BYTES >> 20))
+    return nbytes
+
+
+def convolve_table(ir, L, adjoint=False):
+    """The filter table of the partitioned convolution with block length ``L``: complex64 (n_ir, P, L + 1) with
+    P = ceil(len / L) and row p of filter i being rfft(ir[i, p L : (p + 1) L], n = 2 L), computed in float64 and rounded
+    once.  ``adjoint``: the table of the time-reversed impulse responses (the backward pass).  ``ValueError`` naming the
+    size for a table above 256 MiB."""
+    L = int(L)
+    shape = tuple(np.shape(ir))
+    if len(shape) in (1, 2) and all(shape):                            # (refused by its size before anything is copied)
+        _convolve_table_bytes(shape[0] if len(shape) == 2 else 1, -(-shape[-1] // L), L)
+    h = convolve_irs(ir)
+    n_ir, n = h.shape
+    P = -(-n // L)
+    if adjoint:
+        h = h[:, ::-1]
+    padded = np.zeros((n_ir, P * L), dtype=np.float64)
+    padded[:, :n] = h
+    return np.fft.rfft(padded.reshape(n_ir, P, L), n=2 * L, axis=-1).astype(np.complex64)
+
+
+_CONVOLVE_CONSTS = {}                    # (what, ..., device) -> device tensor
+_CONVOLVE_CONSTS_MAX = 32                # filter tables kept per process (a layer holds on to its own)
+
+
+def _convolve_const(key, device, make_numpy):
+    import torch
+
+    k = key + (str(device),)
+    t = _CONVOLVE_CONSTS.get(k)
+    if t is None:
+        while len(_CONVOLVE_CONSTS) >= _CONVOLVE_CONSTS_MAX:
+            _CONVOLVE_CONSTS.pop(next(iter(_CONVOLVE_CONSTS)))
+        t = _CONVOLVE_CONSTS[k] = torch.from_numpy(np.ascontiguousarray(make_numpy())).to(device)
+    return t
+
+
+class ConvolvePlan:
+    """What a convolution with fixed impulse responses needs beyond the signal: the float64 host copy of the impulse
+    responses, the block length, and the device tables (forward and adjoint), built on first use per device and kept."""
+
+    def __init__(self, ir, block_size=None):
+        import hashlib
+
+        self.h = convolve_irs(ir)
+        self.n_ir, self.ir_len = self.h.shape
+        self.L = convolve_block(self.ir_len, block_size)
+        self.n_part = -(-self.ir_len // self.L)
+        _convolve_table_bytes(self.n_ir, self.n_part, self.L)
+        self._digest = hashlib.sha1(self.h.tobytes()).hexdigest()
+        self._tables = {}
+
+    def table(self, device, adjoint=False):
+        k = (str(device), bool(adjoint))
+        t = self._tables.get(k)
+        if t is None:
+            t = self._tables[k] = _convolve_const(('table', self._digest, self.h.shape, self.L, bool(adjoint)), device,
+                                                   lambda: convolve_table(self.h, self.L, adjoint))
+        return t
+
+    def windows(self, device):
+        """(analysis, synthesis): ones(2 L) and [0] * L + [1] * L"""
+        L = self.L
+        return (_convolve_const(('ones', L), device, lambda: np.ones(2 * L, dtype=np.float32)),
+                _convolve_const(('tail', L), device, lambda: np.concatenate([np.zeros(L, np.float32), np.ones(L, np.float32)])))
+
+
+def convolve_length(t, ir_len, mode):
+    """Output length of a convolution of ``t`` samples with ``ir_len``: 'full' t + ir_len - 1, 'same' t, 'valid'
+    t - ir_len + 1 (``ValueError`` below 1); ``None`` stays ``None``."""
+    if mode not in CONVOLVE_MODES:
+        raise ValueError("convolve: mode must be one of 'full', 'same', 'valid', got %r" % (mode,))
+    if t is None:
+        return None
+    t = int(t)
+    if mode == 'full':
+        return t + ir_len - 1
+    if mode == 'same':
+        return t
+    if t - ir_len + 1 < 1:
+        raise ValueError("convolve: mode 'valid' needs a signal at least as long as the impulse response, got %d < %d"
+                         % (t, ir_len))
+    return t - ir_len + 1
+
+
+def _convolve_offset(ir_len, mode):
+    """First sample of the full convolution that ``mode`` keeps ('same': scipy's centring)."""
+    return {'full': 0, 'same': (ir_len - 1) // 2, 'valid': ir_len - 1}[mode]
+
+
+def _convolve_full(x, fmt, plan, idx, adjoint=False):
+    """The three launches: every sample of the full convolution of the float32 device waveform ``x`` (or, with ``adjoint``,
+    of its convolution with the time-reversed impulse responses) as a view of the inverse launch's output."""
+    b, c, t = _ffi.dims_of(x.shape, fmt)
+    L = plan.L
+    ones, tail = plan.windows(x.device)
+    lay = _ffi.layout(fmt)
+    geom = _ffi.StftGeom(b, c, t, 2 * L, 2 * L, L, 1, 1, lay, lay)
+    k_in = _ffi.num_frames(geom)                                   # ceil((t + L) / L)
+    n_full = t + plan.ir_len - 1
+    k_out = -(-n_full // L)
+    spec = _ffi.stft(x, geom, k_in, ones, _ffi.OUT_COMPLEX)
+    spec = _ffi.spec_fir(spec, fmt, plan.table(x.device, adjoint), idx, k_out)
+    wave = _ffi.istft(spec, tail, 2 * L, 2 * L, L, fmt, fmt)        # (k_out + 1) L samples; sample n of the convolution is n + L
+    return wave.narrow(1 if fmt == _CH_LAST_STR else 2, L, n_full)
+
+
+def _convolve_index(plan, index, batch, device):
+    """The int32 device vector of one filter number per batch item, or None for the one shared impulse response."""
+    import torch
+
+    if index is None:
+        if plan.n_ir == 1:
+            return None
+        if plan.n_ir != batch:
+            raise ValueError('convolve: %d impulse responses for a batch of %d: without index there must be one, or one per '
+                             'batch item' % (plan.n_ir, batch))
+        return _convolve_const(('arange', batch), device, lambda: np.arange(batch, dtype=np.int32))
+    if isinstance(index, torch.Tensor) and index.is_cuda:
+        if index.dtype != torch.int32 or tuple(index.shape) != (batch,):
+            raise ValueError('convolve: a device index must be an int32 tensor of shape (%d,), got %s %s'
+                             % (batch, index.dtype, tuple(index.shape)))
+        return index.contiguous()
+    idx = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+    if idx.shape != (batch,) or idx.dtype.kind not in 'iu':
+        raise ValueError('convolve: index must hold one integer per batch item (%d), got shape %s, dtype %s'
+                         % (batch, idx.shape, idx.dtype))
+    if idx.size and (idx.min() < 0 or idx.max() >= plan.n_ir):
+        raise ValueError('convolve: index values must lie in [0, %d), got %d ... %d' % (plan.n_ir, idx.min(), idx.max()))
+    return torch.from_numpy(idx.astype(np.int32)).to(device)
+
+
+def _convolve_run(x, plan, fmt, mode, index=None, out_len=None):
+    """``x`` (rank 3) convolved along time through ``plan``; ``fmt`` is resolved.  ``out_len``: keep that many samples from
+    the mode's first one (Reverb: the first T of 'full')."""
+    import torch
+
+    from . import autograd
+    if len(x.shape) != 3:
+        raise ValueError('convolve expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('convolve has float32 kernels only; got a float64 input (cast it to float32)')
+    b, _, t = _ffi.dims_of(x.shape, fmt)
+    n_out = convolve_length(t, plan.ir_len, mode) if out_len is None else int(out_len)
+    first = _convolve_offset(plan.ir_len, mode)
+    grad = autograd.needs_grad(x)
+    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
+    idx = _convolve_index(plan, index, b, x.device)
+    if grad:
+        return autograd.convolve(x, fmt, plan, idx, first, n_out)
+    return _convolve_full(x, fmt, plan, idx).narrow(1 if fmt == _CH_LAST_STR else 2, first, n_out).contiguous()
+
+
+def fftconvolve(x, ir, mode='full', index=None, data_format='default', block_size=None):
+    """Convolution of a waveform batch with impulse responses on the GPU (``scipy.signal.fftconvolve`` along time,
+    ``torchaudio.functional.fftconvolve``): room impulse responses, microphone and channel responses, long FIR filters.
+    (b, time, ch) for ``channels_last``, (b, ch, time) for ``channels_first``; float32 in and out.
+
+    ``ir``: (len,), one impulse response for everything; (n_ir, len) with ``index``, one filter number per batch item (host
+    integers are validated, an int32 device tensor is taken as it is and clamped by the kernel); or (batch, len) without
+    ``index``, item i with ir[i].  The channels of an item share its impulse response.  ``mode``: 'full' (time + len - 1
+    samples), 'same' (time samples, scipy's centring: from sample (len - 1) // 2 of 'full') or 'valid' (time - len + 1,
+    ``ValueError`` below 1).
+
+    Partitioned overlap-save with block length L = ``convolve_block(len, block_size)``: one STFT launch (n_fft 2 L, hop L,
+    rectangular window), the spectral FIR ``kpr_spec_fir_c64`` with the ``convolve_table`` of the impulse responses, one
+    inverse-STFT launch, and the trim; nothing is copied to the host.  The impulse responses are constants (no gradient); a
+    waveform that ``requires_grad`` gets a ``grad_fn`` whose backward is the same three launches with the table of the
+    time-reversed impulse responses.  ``ValueError`` for an impulse response longer than 32768 samples or a table above
+    256 MiB, ``TypeError`` for a float64 input."""
+    validate_data_format_str(data_format)
+    if mode not in CONVOLVE_MODES:
+        raise ValueError("convolve: mode must be one of 'full', 'same', 'valid', got %r" % (mode,))
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return _convolve_run(x, ConvolvePlan(ir, block_size), fmt, mode, index)
 
 
 # --------------------------------------------------------------------------------------

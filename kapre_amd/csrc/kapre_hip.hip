@@ -44,8 +44,11 @@
 //   kpr_lfilter_kernels.h     one biquad IIR section along time on a waveform (signal.LFilter): lanes run along time, float64
 //                             inside; carries across lanes, waves and steps through companion-matrix powers; a whole-signal
 //                             and a segmented (three-launch) form; the reverse scan is the adjoint
+//   kpr_spec_fir_kernels.h    a short complex FIR along the frame axis of every bin of a complex spectrogram with a per-item filter
+//                             table: the middle launch of the partitioned FFT convolution (signal.Convolve, augmentation.Reverb);
+//                             filter values in registers, no LDS, no barrier
 // The host code (table caches, launch plans, routes, argument validation) follows the kernels: kpr_host.h (shared by every family),
-// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h, kpr_host_lfilter.h next to their kernel headers.
+// then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h, kpr_host_lfilter.h, kpr_host_convolve.h next to their kernel headers.
 // This file: the C ABI -- the extern "C" entry points, grouped as in include/kapre_hip.h.
 //
 // gfx950 only: wave64, v_mfma_f32_16x16x4_f32, 160 KiB LDS.  No CUDA/compat paths.
@@ -94,6 +97,7 @@
 #include "kpr_time_stretch_kernels.h"
 #include "kpr_hpss_kernels.h"
 #include "kpr_lfilter_kernels.h"
+#include "kpr_spec_fir_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -103,6 +107,7 @@
 #include "kpr_host_ops.h"
 #include "kpr_host_griffin_lim.h"
 #include "kpr_host_lfilter.h"
+#include "kpr_host_convolve.h"
 
 // ==========================================================================================
 // C ABI
@@ -794,6 +799,20 @@ int kpr_spec_augment_draw(int32_t* table, int64_t n_items, int n_time_masks, int
     return launch_check("k_specaug_draw");
 }
 
+int kpr_index_draw(int32_t* out, int64_t n_items, int n_choices, void* state, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    if (n_items < 0 || n_choices < 1) return fail(KPR_E_BADARG, "bad n_items / n_choices (%lld, %d)", (long long)n_items, n_choices);
+    if (n_items > (1LL << 20))
+        return fail(KPR_E_UNSUPPORTED, "%lld items: the one-workgroup draw takes at most 2^20", (long long)n_items);
+    if (!state) return fail(KPR_E_BADARG, "state must not be NULL");
+    if (n_items > 0 && !out) return fail(KPR_E_BADARG, "out must not be NULL");
+    if (ranges_overlap(out, (uintptr_t)n_items * 4, state, 16)) return fail(KPR_E_BADARG, "out overlaps state");
+    // (a call without items still advances the counter: one launch, one step of the stream)
+    hipLaunchKernelGGL(k_index_draw, dim3(1), dim3(1024), 0, (hipStream_t)stream, out, (int)n_items, (unsigned)n_choices,
+                       (unsigned long long*)state);
+    return launch_check("k_index_draw");
+}
+
 int kpr_spec_augment_apply_f32(const float* x, float* out, const int32_t* table, int64_t n_items, int n_time_masks,
                                int n_freq_masks, int n_time, int n_freq, float mask_value, kpr_stream_t stream) {
     if (int e = api_enter()) return e;
@@ -1058,6 +1077,13 @@ int64_t kpr_lfilter_workspace_bytes(int64_t batch, int channels, int64_t len, in
 int kpr_lfilter_f32(const float* x, int64_t batch, int channels, int64_t len, int layout, const double coef[5], int reverse, float* out,
                     void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
     return run_lfilter(x, batch, channels, len, layout, coef, reverse, out, workspace, workspace_bytes, stream);
+}
+
+/* ---- Convolve (kpr_spec_fir_kernels.h) ---------------------------------------------------------- */
+int kpr_spec_fir_plan(int64_t frames_out, int64_t inner, int n_part, int* out) { return spec_fir_plan(frames_out, inner, n_part, out); }
+int kpr_spec_fir_c64(const void* x, int64_t outer, int64_t frames_in, int64_t inner, int band_div, const void* h, int n_ir, int n_part,
+                     const int32_t* idx, int64_t items, void* out, int64_t frames_out, kpr_stream_t stream) {
+    return run_spec_fir(x, outer, frames_in, inner, band_div, h, n_ir, n_part, idx, items, out, frames_out, stream);
 }
 
 }  // extern "C"

@@ -57,6 +57,20 @@ __global__ __launch_bounds__(1024) void k_specaug_draw(int* __restrict__ table, 
     if (threadIdx.x == 0) state[1] = calls + 1;
 }
 
+// One workgroup, the same state and the same generator as k_specaug_draw.  Entry item: counter (item, 0, calls_lo, calls_hi),
+// key (seed_lo, seed_hi); out[item] = mulhi(r0, n_choices), uniform in 0 .. n_choices - 1 (augmentation.Reverb: which impulse
+// response an item gets).  One lane stores calls + 1 behind the barrier.
+__global__ __launch_bounds__(1024) void k_index_draw(int* __restrict__ out, int n_items, unsigned n_choices, unsigned long long* state) {
+    const unsigned long long seed = state[0], calls = state[1];
+    for (int e = threadIdx.x; e < n_items; e += blockDim.x) {
+        unsigned c[4] = {(unsigned)e, 0u, (unsigned)calls, (unsigned)(calls >> 32)};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        out[e] = (int)__umulhi(c[0], n_choices);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) state[1] = calls + 1;
+}
+
 // out = masked ? mask_value : x (tf.where, augmentation.py:264): a copy, bit for bit on the elements that pass.  x / out are n_items
 // blocks of n_time x n_freq floats (one channel: channels_first and channels_last are the same bytes).  A workgroup owns at most
 // kAugChunk consecutive floats of one item; it turns the item's intervals into two LDS bitmaps -- the rows its floats touch, the

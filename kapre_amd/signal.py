@@ -5,7 +5,8 @@ libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with 
 MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.mu_law_encoding / mu_law_decoding
 (kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32).  Resample has no counterpart in the reference: it is
 the step in front of every front end (kpr_resample_f32).  Neither have LFilter, Preemphasis and Deemphasis: biquad filtering of
-the waveform itself (kpr_lfilter_f32)."""
+the waveform itself (kpr_lfilter_f32), and Convolve: convolution with a fixed impulse response (kpr_stft_f32, kpr_spec_fir_c64,
+kpr_istft_f32)."""
 import math
 
 import numpy as np
@@ -15,7 +16,7 @@ from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample', 'LFilter', 'Preemphasis',
-           'Deemphasis']
+           'Deemphasis', 'Convolve']
 
 
 def _resolve_format(fmt):
@@ -369,4 +370,45 @@ class Deemphasis(LFilter):
     def get_config(self):
         config = Layer.get_config(self)
         config.update({'coef': self.coef, 'data_format': self.data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class Convolve(Layer):
+    """Convolution of the waveform with a fixed impulse response along time (``backend.fftconvolve``;
+    ``torchaudio.transforms.Convolve``): room, microphone and channel responses, FIR filters of up to 32768 taps.  ``ir``:
+    array-like (len,), shared by every item and channel, or (n, len) for batches of exactly n items, item i with ir[i].
+    ``mode``: 'full', 'same' (scipy's centring) or 'valid'.  ``block_size``: None for ``backend.convolve_block``'s rule, or one of
+    256, 512, 1024.
+
+    (batch, time, ch) -> (batch, time', ch) for ``channels_last``, (batch, ch, time) -> (batch, ch, time') for
+    ``channels_first``, time' = time + len - 1, time or time - len + 1.  numpy or torch, float32 (a float64 input raises
+    ``TypeError``).  Three launches and a trim; differentiable with respect to the waveform (the same three launches with the
+    time-reversed impulse response).  The impulse response is a constant of the layer: it travels in the config and gets no
+    gradient."""
+
+    def __init__(self, ir, mode='full', block_size=None, input_data_format='default', **kwargs):
+        super(Convolve, self).__init__(**kwargs)
+        backend.validate_data_format_str(input_data_format)
+        backend.convolve_length(None, 1, mode)                      # ValueError for an unknown mode
+        self._plan = backend.ConvolvePlan(ir, block_size)
+        self.ir = self._plan.h[0].tolist() if np.ndim(ir) == 1 else self._plan.h.tolist()
+        self.mode = mode
+        self.block_size = None if block_size is None else int(block_size)
+        self.input_data_format_str = input_data_format
+        self.input_data_format = _resolve_format(input_data_format)
+        self.time_axis = 2 if self.input_data_format == _CH_FIRST_STR else 1
+
+    def compute_output_shape(self, input_shape):
+        """(b, t, ch) -> (b, t', ch); (b, ch, t) -> (b, ch, t') with t' the length ``mode`` keeps"""
+        b, c, t = _ffi.dims_of(input_shape, self.input_data_format)
+        return _ffi.shape_of(self.input_data_format, b, c, backend.convolve_length(t, self._plan.ir_len, self.mode))
+
+    def call(self, x):
+        return backend._convolve_run(x, self._plan, self.input_data_format, self.mode)
+
+    def get_config(self):
+        config = super(Convolve, self).get_config()
+        config.update({'ir': self.ir, 'mode': self.mode, 'block_size': self.block_size,
+                       'input_data_format': self.input_data_format_str})
         return config
