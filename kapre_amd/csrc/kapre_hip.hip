@@ -443,13 +443,20 @@ int kpr_apply_filterbank_f32(const float* x, int64_t batch, int channels, int64_
         const size_t lds = sizeof(float) * 4 * 64 * (size_t)ntiles * ((n_freq + 15) / 16);
         const unsigned grid = (unsigned)std::min<long long>((rows + 63) / 64, 256 * 8);
         hipStream_t st = (hipStream_t)stream;
+        // thin_gemm_shape admits up to 4 tiles x 32 k-groups = 128 KiB of B fragments: above 64 KiB the instance opts in
+        auto launch = [&](auto nt) -> int {
+            static LdsOptIn lds_opt_in;
+            if (lds > 64 * 1024)
+                if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_thin_gemm<nt>))) return e;
+            hipLaunchKernelGGL(k_thin_gemm<nt>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out);
+            return launch_check("k_thin_gemm");
+        };
         switch (ntiles) {
-            case 1: hipLaunchKernelGGL(k_thin_gemm<1>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out); break;
-            case 2: hipLaunchKernelGGL(k_thin_gemm<2>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out); break;
-            case 3: hipLaunchKernelGGL(k_thin_gemm<3>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out); break;
-            default: hipLaunchKernelGGL(k_thin_gemm<4>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out); break;
+            case 1: return launch(std::integral_constant<int, 1>{});
+            case 2: return launch(std::integral_constant<int, 2>{});
+            case 3: return launch(std::integral_constant<int, 3>{});
+            default: return launch(std::integral_constant<int, 4>{});
         }
-        return launch_check("k_thin_gemm");
     }
     GemmArgs ga{};
     ga.in.rows = rows; ga.out.rows = rows;
