@@ -7,12 +7,16 @@ namespace kpr {
 // ------------------------------------------------------------------------------------------
 // elementwise complex -> real
 // ------------------------------------------------------------------------------------------
+// |v| = sqrt(fma(re, re, fl(im * im))): ONE fused multiply-add under the root, written out so that the optimiser's contraction
+// does not decide the last bit (and cannot decide it differently in an unrolled body and its remainder).  hp_abs (HPSS) and
+// pv_abs (TimeStretch) form the same expression: their magnitudes equal Magnitude()'s bit for bit.  The squares overflow from
+// components of about 1.8e19 (+Inf) and underflow under about 1e-19 (INTEGRATION.md "Non-finite values").
 __global__ void k_cplx_to_real(const float2* __restrict__ x, long long n, int phase,
                                float* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
         float2 v = x[i];
-        out[i] = phase ? atan2f(v.y, v.x) : sqrtf(v.x * v.x + v.y * v.y);
+        out[i] = phase ? atan2f(v.y, v.x) : sqrtf(fmaf(v.x, v.x, v.y * v.y));
     }
 }
 

@@ -165,6 +165,11 @@ def test_complex_input(fmt):
     mag = kapre.Magnitude()(dd)
     for kh, kp, power, margin in ((31, 31, 2.0, 1.0), (17, 7, 1.0, (2.0, 3.0)), (5, 3, 3.0, 1.0)):
         lay = lambda **kw: kapre.HPSS(kernel_size=(kh, kp), power=power, margin=margin, data_format=fmt, **kw)
+        # hp_abs forms |D| as k_cplx_to_real does (one fused multiply-add under the root): the medians of D are the medians of
+        # Magnitude()(D) bit for bit, and so are the masks
+        med_c, med_r = (_run(t, fmt, kh, kp, mode=_ffi.HPSS_MEDIANS) for t in (dd, mag))
+        for a, b in zip(med_c, med_r):
+            np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
         m_c, m_r = lay(mask=True)(dd), lay(mask=True)(mag)
         assert m_c.dtype == torch.float32 and torch.equal(m_c, m_r)
         out = lay()(dd)
