@@ -102,18 +102,6 @@ static const char* status_text(unsigned bits) {
              (bits & kStSelfTest) ? " self-test(bounded wait ran out)" : "");
     return buf;
 }
-// entry of every API call that launches hot kernels: the launch log restarts, and a status word raised by an EARLIER call's
-// kernels fails this one (sticky until kpr_device_status reads it -- like a HIP sticky error, but recoverable)
-static int api_enter() {
-    launch_log_begin();
-    if (unsigned* hostp = g_status.host.load(std::memory_order_acquire)) {
-        const unsigned bits = *static_cast<volatile unsigned*>(hostp);
-        if (bits)
-            return fail(KPR_E_DEVICE, "a kernel of an earlier call raised the device status word (%s): its results are wrong; "
-                        "kpr_device_status() reads and clears the condition", status_text(bits));
-    }
-    return 0;
-}
 // `detail`: the template arguments beyond the transform size that pick the INSTANCE ("s4", "w16", "rj4,v2" ...): the fuzz gate of
 // tests/test_fuzz_gate.py asserts that every instance of the large-launch kernels was reached, not just every family
 static int launch_check(const char* what, int tag = 0, const char* detail = nullptr) {

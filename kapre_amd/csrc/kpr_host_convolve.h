@@ -29,7 +29,6 @@ static void launch_spec_fir(int bucket, const ColLaunch& l, const FirArgs& a, hi
 // device; idx: `items` device int32 or NULL, never read here
 static int run_spec_fir(const void* x, int64_t outer, int64_t frames_in, int64_t inner, int band_div, const void* h, int n_ir, int n_part,
                         const int32_t* idx, int64_t items, void* out, int64_t frames_out, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (outer < 0 || frames_in < 0 || frames_out < 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/frames_in/frames_out/inner");
     if (n_part < 1 || n_part > kFirMaxPart) return fail(KPR_E_BADARG, "n_part = %d outside [1, %d]", n_part, kFirMaxPart);
     if (n_ir < 1 || band_div < 1 || items < 0) return fail(KPR_E_BADARG, "bad n_ir/band_div/items (%d, %d, %lld)", n_ir, band_div, (long long)items);

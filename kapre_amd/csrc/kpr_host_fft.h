@@ -1,6 +1,6 @@
 // kpr_host_fft.h -- host side of the FFT building blocks (kpr_fft.h, kpr_fft_mr.h, kpr_generic_kernels.h): which transform sizes
 // each family takes, the device tables (five builders over cached_table), with_pow2 / with_mr and the mixed-radix plan typedefs,
-// the plan of the generic engine, fft_family.
+// the plan of the generic engine, fft_family, fft_plan (the body of kpr_fft_plan).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host.h; not stand-alone).
 #pragma once
 
@@ -113,6 +113,12 @@ static int get_bluestein(int n_fft, const float2** out) { return cached_table(g_
 static int get_dft_fwd(int n_fft, const float** out) { return cached_table(g_dft_fwd, n_fft, build_dft_fwd, out); }
 static int get_dft_inv(int n_fft, const float** out) { return cached_table(g_dft_inv, n_fft, build_dft_inv, out); }
 static int get_twiddles64(int n_fft, const double2** out) { return cached_table(g_tw64, n_fft, build_twiddles64, out); }
+// the twiddles of the generic engine's element type T (launch_stft_gen, launch_irfft_gen)
+template <typename T>
+static int twiddles_of(int n_fft, const typename Cplx<T>::type** out) {
+    if constexpr (sizeof(T) == 4) return get_twiddles(n_fft, out);
+    else return get_twiddles64(n_fft, out);
+}
 
 // n -> f(std::integral_constant<int, n>) for the power-of-two template sizes n = 128, 256, 512, 1024 (anything else: 1024) -- the
 // half transform size NC = n_fft / 2 of the power-of-two kernels, the Bluestein length M, the bin count of k_fb_pw
@@ -259,6 +265,25 @@ static int fft_family(const kpr_stft_geom* s) {
     // every other size with small prime factors (odd sizes, 1200, 1536, 2000 ...): run-time mixed-radix FFT
     if (gen_ok_f32(s)) return FAM_GEN;
     return FAM_GEMM;
+}
+
+// kpr_fft_plan: the dispatch's own answer (fft_family) for the cropped geometry of a forward transform
+static int fft_plan(int n_fft, int win_length) {
+    if (n_fft < 2 || win_length < 1) return -1;
+    kpr_stft_geom s{};
+    s.batch = 1; s.channels = 1; s.time = n_fft; s.n_fft = n_fft; s.win_length = std::min(win_length, n_fft); s.hop_length = 1;
+    // The one input on which this function has never agreed with the dispatch: n_fft 4096 / 8192 with win_length > n_fft.  The
+    // forward transform crops such frames and runs k_stft_big; this function has answered as if the sub-FFT family refused them,
+    // and callers may have recorded that answer, so it stays.
+    if (big_nfft(n_fft) && win_length > n_fft) return gen_ok_f32(&s) ? KPR_FFT_GENERIC : KPR_FFT_DFT_GEMM;
+    switch (fft_family(&s)) {
+        case FAM_POW2: return KPR_FFT_POW2;
+        case FAM_MR:   return mixed_radix_plan(n_fft) == 1 ? KPR_FFT_MIXED_RADIX : KPR_FFT_TWO_PASS;
+        case FAM_BS:   return KPR_FFT_BLUESTEIN;
+        case FAM_BIG:  return KPR_FFT_SUB_FFT;
+        case FAM_GEN:  return KPR_FFT_GENERIC;
+        default:       return KPR_FFT_DFT_GEMM;
+    }
 }
 
 }  // namespace kpr

@@ -106,7 +106,7 @@ static int gl_layout(const kpr_stft_geom* g, int64_t n_frames, bool with_momentu
     l->spec = gl_align(n * 8);
     l->mag = with_power ? gl_align(n * 4) : 0;
     l->part = gl_part_bytes(g->batch, (int64_t)(n / (size_t)std::max<int64_t>(g->batch, 1)));
-    const int64_t wi = kpr_istft_workspace_bytes(g, n_frames), wf = kpr_stft_workspace_bytes(fwd, KPR_OUT_COMPLEX);
+    const int64_t wi = istft_workspace_bytes<float>(g, n_frames), wf = stft_workspace_bytes(fwd, KPR_OUT_COMPLEX);
     if (wi < 0 || wf < 0) return KPR_E_BADARG;
     l->istft = gl_align((size_t)wi);
     l->stft = gl_align((size_t)wf);

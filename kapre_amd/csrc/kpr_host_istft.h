@@ -1,6 +1,6 @@
 // kpr_host_istft.h -- host side of kpr_istft_kernels.h / kpr_istft_pw_kernels.h (and of the inverse kernel of kpr_generic_kernels.h):
 // the plans and launchers of the one-launch inverse kernels, the inverse-FFT launchers of the two-kernel path, IstftRoute /
-// istft_route, the overlap-add tail, and run_istft_f32, the body of kpr_istft_f32.
+// istft_route, the overlap-add tail, istft_workspace_bytes, and run_istft_f32 / run_istft_f64, the bodies of kpr_istft_f32 / _f64.
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_stft.h; not stand-alone).
 #pragma once
 
@@ -349,15 +349,24 @@ static int launch_irfft_fast(const float2* spec, const Geom& g, const float* syn
     return launch_framewise(&k_irfft<NC>, nullptr, nblocks, 1, 2, 256, lds, st, "k_irfft", 0, spec, g, synth, tw, frames, nblocks);
 }
 
-static int launch_irfft_gen_f32(const float2* spec, const Geom& g, const float* synth_window, float* frames,
-                                hipStream_t st) {
+// the run-time mixed-radix inverse FFT, T = float (FAM_GEN) or double (run_istft_f64); LDS opt-in state per T and instance
+template <typename T>
+static int launch_irfft_gen(const typename Cplx<T>::type* spec, const Geom& g, const T* synth_window, T* frames, hipStream_t st) {
+    typedef typename Cplx<T>::type T2;
     GenLaunch l;
-    if (int e = gen_launch_plan(sizeof(float2), g.n_fft, &l)) return e;
-    const float2* tw = nullptr;
-    if (int e = get_twiddles(g.n_fft, &tw)) return e;
+    if (int e = gen_launch_plan(sizeof(T2), g.n_fft, &l)) return e;
+    const T2* tw = nullptr;
+    if (int e = twiddles_of<T>(g.n_fft, &tw)) return e;
     static LdsOptIn opt_in[2];
-    return launch_gen(l.tw_lds ? &k_irfft_gen<float, true> : &k_irfft_gen<float, false>, opt_in[l.tw_lds ? 1 : 0], l, g, st,
-                      "k_irfft_gen<float>", spec, g, synth_window, tw, l.p, frames);
+    return launch_gen(l.tw_lds ? &k_irfft_gen<T, true> : &k_irfft_gen<T, false>, opt_in[l.tw_lds ? 1 : 0], l, g, st,
+                      sizeof(T) == 4 ? "k_irfft_gen<float>" : "k_irfft_gen<double>", spec, g, synth_window, tw, l.p, frames);
+}
+
+// the workspace of the two-kernel path (kpr_istft_workspace_bytes, kpr_istft_f64_workspace_bytes): every windowed frame
+template <typename T>
+static int64_t istft_workspace_bytes(const kpr_stft_geom* s, int64_t n_frames) {
+    if (check_geom(s) || n_frames < 0) return -1;
+    return 256 + (int64_t)sizeof(T) * s->batch * s->channels * n_frames * s->win_length;
 }
 
 // the second kernel of the two-kernel path: overlap-add of the windowed frames in the workspace into the waveform
@@ -396,7 +405,7 @@ static IstftRoute istft_route(const kpr_stft_geom* s, long long F, const Geom& g
     return r;
 }
 
-// ---- kpr_istft_f32 behind api_enter: checks, route, launch (kpr_griffin_lim_f32 runs it once per iteration) ----
+// ---- kpr_istft_f32: checks, route, launch (run_griffin_lim runs it once per iteration) ----
 static int run_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_frames, const float* synth_window, float* out,
                          void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
     if (int e = check_geom(s)) return e;
@@ -405,7 +414,7 @@ static int run_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_fra
     g.pad_left = 0;
     if (g.total_frames == 0) return 0;
     if (!spec || !synth_window || !out) return fail(KPR_E_BADARG, "spec / window / out must not be NULL");
-    const int64_t need = kpr_istft_workspace_bytes(s, n_frames);
+    const int64_t need = istft_workspace_bytes<float>(s, n_frames);
     if (!workspace || workspace_bytes < need)
         return fail(KPR_E_WORKSPACE, "istft workspace: need %lld bytes", (long long)need);
     hipStream_t st = (hipStream_t)stream;
@@ -439,7 +448,7 @@ static int run_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_fra
     } else if (r.fam == FAM_BIG) {    // 4096 / 8192: sub-FFT kernel, then the gather
         if (int e = launch_irfft_big(sp, g, synth_window, frames, st)) return e;
     } else if (r.fam == FAM_GEN) {    // small prime factors: run-time mixed-radix inverse FFT, then the gather
-        if (int e = launch_irfft_gen_f32(sp, g, synth_window, frames, st)) return e;
+        if (int e = launch_irfft_gen<float>(sp, g, synth_window, frames, st)) return e;
     } else {
         const float* idft = nullptr;
         if (int e = get_dft_inv(s->n_fft, &idft)) return e;
@@ -457,6 +466,24 @@ static int run_istft_f32(const void* spec, const kpr_stft_geom* s, int64_t n_fra
         }
     }
     return run_ola<float>(frames, s, n_frames, s->in_layout == KPR_CHANNELS_LAST, out, st);
+}
+
+// ---- kpr_istft_f64: the generic engine into the workspace, then the overlap-add ----
+static int run_istft_f64(const void* spec, const kpr_stft_geom* s, int64_t n_frames, const double* synth_window, double* out,
+                         void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = check_geom(s)) return e;
+    if (n_frames < 0) return fail(KPR_E_BADARG, "negative frame count");
+    Geom g = make_geom(s, n_frames);
+    g.pad_left = 0;
+    if (g.total_frames == 0) return 0;
+    if (!spec || !synth_window || !out) return fail(KPR_E_BADARG, "spec / window / out must not be NULL");
+    const int64_t need = istft_workspace_bytes<double>(s, n_frames);
+    if (!workspace || workspace_bytes < need)
+        return fail(KPR_E_WORKSPACE, "istft (float64) workspace: need %lld bytes", (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    double* frames = reinterpret_cast<double*>(workspace);
+    if (int e = launch_irfft_gen<double>((const double2*)spec, g, synth_window, frames, st)) return e;
+    return run_ola<double>(frames, s, n_frames, s->in_layout == KPR_CHANNELS_LAST && s->channels > 1, out, st);
 }
 
 }  // namespace kpr

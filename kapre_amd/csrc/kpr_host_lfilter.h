@@ -45,6 +45,16 @@ static void lfilter_carries(double a1d, double a2d, int sigma, const std::vector
         else out->push_back({(double)(A + sg * B), (double)(A + sg * B - sg * C - D), (double)(-sg * B), (double)(-sg * B + D)});
     }
 }
+// kpr_lfilter_carry: M_n in the plain basis for one chunk length n
+static int lfilter_carry(const double* coef, int64_t n, double* M) {
+    if (!M) return fail(KPR_E_BADARG, "M is NULL");
+    if (int e = lfilter_coef(coef)) return e;
+    if (n < 0 || n > kLfCarryMax) return fail(KPR_E_BADARG, "chunk length %lld outside [0, 2^20]", (long long)n);
+    std::vector<std::array<double, 4>> m;
+    lfilter_carries(coef[3], coef[4], 0, {n}, &m);
+    std::copy(m[0].begin(), m[0].end(), M);
+    return 0;
+}
 // the sign of the basis: poles in the right half plane (a1 <= 0) carry z1 + z2, in the left z1 - z2
 static int lfilter_sigma(double a1) { return a1 <= 0.0 ? 1 : -1; }
 
@@ -114,7 +124,6 @@ static int lfilter_launch(const LfArgs& a, bool vec, bool rev, long long grid, h
 
 static int run_lfilter(const float* x, int64_t batch, int channels, int64_t len, int layout, const double* coef, int reverse, float* out,
                        void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (int e = lfilter_dims(batch, channels, len, layout)) return e;
     if (int e = lfilter_coef(coef)) return e;
     if (reverse != 0 && reverse != 1) return fail(KPR_E_BADARG, "reverse must be 0 or 1, got %d", reverse);

@@ -1,6 +1,7 @@
 // kpr_host_mel.h -- host side of the mel / filterbank / decibel kernels (kpr_mel_kernels.h, kpr_mel_ts_kernels.h, kpr_mel_pw_kernels.h,
 // kpr_fb_pw_kernels.h, kpr_mel_mr_kernels.h, k_db_* and k_band_mel of kpr_misc_kernels.h): tile ranges, the schedules and their
-// caches, the packed filterbank (header, band plan, verification), the launchers, the decibel helpers, MelRoute / mel_route, fb_route.
+// caches, the packed filterbank (header, band plan, verification, the host-only pack / k-range builders), the launchers, the decibel
+// helpers, the workspace sizes, MelRoute / mel_route and run_mel_f32, fb_route and the two float32 ApplyFilterbank bodies.
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_istft.h; not stand-alone).
 #pragma once
 
@@ -279,6 +280,73 @@ static int verify_packed(const float* fb_packed, int K, int M, const int32_t* kr
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_pack_ok.size() > 1024) g_pack_ok.clear();
     g_pack_ok[{fb_packed, key}] = pi;
+    return 0;
+}
+
+// kpr_filterbank_forget: drop what is cached about one packed blob (NULL: about all of them)
+static int filterbank_forget(const float* fb_packed) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!fb_packed) { g_pack_ok.clear(); return 0; }
+    for (auto it = g_pack_ok.begin(); it != g_pack_ok.end();)
+        it = (it->first.first == (const void*)fb_packed) ? g_pack_ok.erase(it) : std::next(it);
+    return 0;
+}
+
+// ---- the host-only filterbank builders: kpr_filterbank_pack_floats, kpr_filterbank_pack, kpr_filterbank_kranges ----
+static int64_t filterbank_pack_floats(int n_freq, int n_filt, const int32_t* fb_kranges_host) {
+    if (n_freq <= 0 || n_filt <= 0) return -1;
+    MelSched sch;
+    if (build_sched(n_freq, n_filt, fb_kranges_host, &sch)) return -1;
+    return (int64_t)packed_chunks(sch) * 512 + kPackHeaderFloats + pw_section_cap(n_freq);   // header | fp32 MFMA fragments | band plan
+}
+
+static int filterbank_pack(const float* fb_host, int n_freq, int n_filt, const int32_t* fb_kranges_host, float* out_host) {
+    if (!fb_host || !out_host || n_freq <= 0 || n_filt <= 0)
+        return fail(KPR_E_BADARG, "bad arguments to kpr_filterbank_pack");
+    MelSched sch;
+    if (int e = build_sched(n_freq, n_filt, fb_kranges_host, &sch)) return e;
+    {
+        uint32_t hdr[kPackHeaderFloats] = {0};
+        const int chunks = packed_chunks(sch);
+        hdr[0] = kPackMagic; hdr[1] = (uint32_t)n_freq; hdr[2] = (uint32_t)n_filt; hdr[3] = (uint32_t)sch.ntiles;
+        hdr[4] = (uint32_t)chunks; hdr[5] = kranges_hash(n_freq, n_filt, fb_kranges_host);
+        if (const int cap = pw_section_cap(n_freq)) {                 // band plan for k_mel_pw (after the fragments)
+            uint32_t* sec = reinterpret_cast<uint32_t*>(out_host) + kPackHeaderFloats + (size_t)chunks * 512;
+            std::memset(sec, 0, sizeof(uint32_t) * cap);
+            if (build_band_plan(fb_host, n_freq, n_filt, sec, &hdr[7])) hdr[6] = (uint32_t)(kPackHeaderFloats + chunks * 512);
+        }
+        std::memcpy(out_host, hdr, sizeof(hdr));
+        out_host += kPackHeaderFloats;
+    }
+    for (int t = 0; t < sch.ntiles; ++t) {
+        size_t pos = (size_t)sch.chunk0[t] * 512;
+        for (int c = 0; c < (sch.khi[t] - sch.klo[t]) / kChunkRows; ++c)
+            for (int g = 0; g < 2; ++g)
+                for (int l = 0; l < 64; ++l)
+                    for (int s4 = 0; s4 < 4; ++s4) {
+                        const int k = sch.klo[t] + kChunkRows * c + 16 * g + 4 * s4 + (l >> 4);
+                        const int m = 16 * t + (l & 15);
+                        out_host[pos++] = (k < n_freq && m < n_filt) ? fb_host[(size_t)k * n_filt + m] : 0.0f;
+                    }
+    }
+    return 0;
+}
+
+static int filterbank_kranges(const float* fb_host, int n_freq, int n_filt, int32_t* out_host) {
+    if (!fb_host || !out_host || n_freq <= 0 || n_filt <= 0)
+        return fail(KPR_E_BADARG, "bad arguments to kpr_filterbank_kranges");
+    const int ntiles = (n_filt + 15) / 16;
+    for (int t = 0; t < ntiles; ++t) {
+        int lo = n_freq, hi = 0;
+        for (int k = 0; k < n_freq; ++k)
+            for (int m = t * 16; m < std::min(n_filt, t * 16 + 16); ++m) {
+                float v = fb_host[(size_t)k * n_filt + m];
+                if (v != 0.0f || v != v) { lo = std::min(lo, k); hi = std::max(hi, k + 1); }
+            }
+        if (lo >= hi) { lo = 0; hi = 0; }
+        out_host[2 * t] = lo & ~3;
+        out_host[2 * t + 1] = (hi + 3) & ~3;
+    }
     return 0;
 }
 
@@ -681,6 +749,12 @@ static int db_chunks(long long n_items, long long item_size) {
     return (int)std::max<long long>(1, std::min<long long>(std::min<long long>(256, want), item_size / 4096));
 }
 
+// the statistics words of n_items items (x slots) to their initial values: ahead of every decibel pass
+static int stats_init(unsigned* stats, long long n_items, hipStream_t st) {
+    hipLaunchKernelGGL(k_stats_init, dim3(grid_1d(n_items, 256)), dim3(256), 0, st, stats, n_items);
+    return launch_check("k_stats_init");
+}
+
 static int db_clamp(float* out, long long n_items, long long item_size, float dyn,
                     const unsigned* stats, hipStream_t st, int slots = 1) {
     if (n_items <= 0 || item_size <= 0) return 0;
@@ -712,6 +786,24 @@ static bool fused_nfft(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_ff
 static int64_t stats_region_bytes(int64_t batch) {
     int64_t b = 256 + (int64_t)sizeof(unsigned) * 2 * std::max<int64_t>(1, batch) * db_slots_cap(batch);
     return (b + 255) & ~(int64_t)255;
+}
+// ... plus the frame-contiguous complex spectrum the two-kernel path stages behind it
+static int64_t mel_staged_bytes(int64_t batch, long long total_frames, int K) {
+    return stats_region_bytes(batch) + (int64_t)sizeof(float) * 2 * total_frames * K;
+}
+
+// kpr_mel_workspace_bytes / kpr_mel_workspace_bytes_unpacked (unpacked: always the staged size)
+static int64_t mel_workspace_bytes(const kpr_stft_geom* s, int n_filt, bool unpacked) {
+    if (check_geom(s) || n_filt <= 0) return -1;
+    // two-kernel path (stages the complex spectrum): every n_fft without a fused kernel, and filterbanks with more
+    // 16-filter tiles than the tile-synchronous kernel's schedule holds (banks without a band plan of more than 256 filters are
+    // beyond k_mel_ts, and beyond k_mel_ws whenever a consumer's slice exceeds 64 chunks -- always at n_fft 512; ADVICE r05: such a
+    // call used to fail with KPR_E_WORKSPACE once k_mel_fused, the catch-all of round 1, was gone).  A bank of at most 256
+    // filters that neither kernel's schedule holds (dense matrices) still needs kpr_mel_workspace_bytes_unpacked(): the call then
+    // fails with KPR_E_WORKSPACE and names that size; the Python layer retries with it.
+    if (unpacked || !fused_nfft(s->n_fft) || (n_filt + 15) / 16 > kTsMaxTiles)
+        return mel_staged_bytes(s->batch, s->batch * s->channels * frames_of(s), s->n_fft / 2 + 1);
+    return stats_region_bytes(s->batch);
 }
 
 enum { MEL_PW, MEL_PW_PAIR, MEL_TS, MEL_WS, MEL_MR, MEL_STAGED };     // MEL_STAGED: an STFT into the workspace, then a product
@@ -826,7 +918,7 @@ static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool pac
     }
     // two-kernel path: STFT (frame-contiguous) -> (|.| x filterbank) product [+ dB]
     r.fam = MEL_STAGED;
-    r.workspace = stats_region_bytes(s->batch) + (int64_t)sizeof(float) * 2 * g.total_frames * g.K;
+    r.workspace = mel_staged_bytes(s->batch, g.total_frames, g.K);
     r.stage = StftRoute{fft_family(s), STFT_K, 0, 0};
     r.stage_mode = KPR_OUT_COMPLEX;
     r.product = PROD_GEMM;
@@ -853,6 +945,100 @@ static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool pac
     return r;
 }
 
+// ---- kpr_mel_f32: checks, the packed filterbank, route, launch [+ the decibel clamp] ----
+static int run_mel_f32(const float* x, const kpr_stft_geom* s, const float* window, const float* fb, const float* fb_packed, int n_filt,
+                       const int32_t* fb_kranges_host, const kpr_db_params* db, float* out, void* workspace, int64_t workspace_bytes,
+                       kpr_stream_t stream) {
+    if (int e = check_geom(s)) return e;
+    if (int e = check_db(db)) return e;
+    if (n_filt <= 0) return fail(KPR_E_BADARG, "n_filt must be positive");
+    const long long F = frames_of(s);
+    const int64_t need = mel_workspace_bytes(s, n_filt, false);
+    const kpr_stft_geom se = forward_geom(s);                    // win_length > n_fft: cropped frames (see forward_geom)
+    s = &se;
+    Geom g = make_geom(s, F);
+    if (g.total_frames == 0) return 0;
+    if (!x || !window || !fb || !out)
+        return fail(KPR_E_BADARG, "x / window / fb / out must not be NULL");
+    if (!workspace || workspace_bytes < need)
+        return fail(KPR_E_WORKSPACE, "mel workspace: need %lld bytes", (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    MelSched sch{};
+    const int sched_rc = get_sched(g.K, n_filt, fb_kranges_host, &sch);
+    if (sched_rc != 0 && sched_rc != KPR_E_UNSUPPORTED) return sched_rc;          // malformed k-ranges etc.: report
+    const bool have_sched = sched_rc == 0;                                         // UNSUPPORTED: more tiles than the
+    if (!have_sched) { fb_packed = nullptr; fb_kranges_host = nullptr; }           // schedule holds -> dense GEMM
+    PackInfo pinfo{0, 0, 0, 0, 0};
+    const float* blob = fb_packed;
+    if (fb_packed) {
+        if (int e = verify_packed(fb_packed, g.K, n_filt, fb_kranges_host, sch, st, &pinfo)) return e;
+        fb_packed += kPackHeaderFloats;
+    }
+    int cus = 256;
+    if (int e = device_cus(&cus)) return e;
+    const MelRoute r = mel_route(s, g, n_filt, blob != nullptr, pinfo, sch, fb_kranges_host, out, cus, db && db->enabled);
+    if (workspace_bytes < r.workspace)
+        return fail(KPR_E_WORKSPACE, "mel workspace (unpacked filterbank path): need %lld bytes", (long long)r.workspace);
+    DbDev dbd = make_db(db);
+    unsigned* stats = reinterpret_cast<unsigned*>(workspace);
+    const int slots = dbd.enabled ? db_slots(s->batch) : 1;       // statistics slots per item (small batches, see DbDev)
+    if (dbd.enabled) {
+        dbd.slot_mask = slots - 1;
+        dbd.slot_stride = (int)(2 * s->batch);
+        if (int e = stats_init(stats, (long long)s->batch * slots, st)) return e;
+    }
+    g.cfast = r.cfast;
+    const float2* tw = nullptr;
+    if (r.fam != MEL_STAGED)
+        if (int e = get_twiddles(s->n_fft, &tw)) return e;
+    auto run = [&]() -> int {
+        switch (r.fam) {
+            case MEL_PW:
+                if (r.plain) return launch_mel_pw_plain_w(r.w, x, g, window, tw, blob, pinfo, n_filt, out, st);
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    return launch_mel_pw_w<nc>(r.w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st);
+                });
+            case MEL_PW_PAIR:
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    if constexpr (nc >= 512) return launch_mel_pw_pair<nc>(x, g, window, tw, blob, pinfo, n_filt, r.cl_slots, dbd, stats, out, st);
+                    else return no_instance("k_mel_pw_pair");
+                });
+            case MEL_TS:
+                if (r.rf64) return launch_mel_ts<256, 64>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    return launch_mel_ts<nc>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                });
+            case MEL_WS:
+                return with_pow2(s->n_fft / 2, [&](auto nc) {
+                    if constexpr (nc >= 512) return launch_mel_ws<nc>(r.ws_form, x, g, window, tw, fb_packed, sch, dbd, stats, out, st);
+                    else return no_instance("k_mel_ws");
+                });
+            case MEL_MR:
+                return with_mr(s->n_fft, [&](auto ff) {
+                    return launch_mel_mr_inst<typename decltype(ff)::type>(x, g, window, tw, fb_packed, r.ts, dbd, stats, out, st);
+                });
+        }
+        float* spec = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + stats_region_bytes(s->batch));
+        Geom gc = g;
+        gc.out_cl = 0;
+        if (int e = launch_stft(r.stage, x, gc, window, r.stage_mode, spec, cus, st)) return e;
+        if (r.product == PROD_WS) return launch_mel_ws<1024, true>(r.ws_form, spec, g, nullptr, nullptr, fb_packed, sch, dbd, stats, out, st);
+        if (r.product == PROD_BAND) return run_band_mel(spec, g, fb, sch, dbd, stats, out, st);
+        GemmArgs ga{};
+        ga.in = frames_contig_map(g, g.K);
+        ga.out = frames_out_map(g, n_filt);
+        ga.Kdim = g.K; ga.N = n_filt; ga.ldb = n_filt;
+        ga.db = dbd; ga.stats = stats;
+        if (fb_kranges_host) {
+            ga.has_kr = 1;
+            for (int t = 0; t < sch.ntiles; ++t) { ga.klo[t] = sch.klo[t]; ga.khi[t] = sch.khi[t]; }
+        }
+        return dbd.enabled ? run_gemm<A_CABS, E_DB>(spec, fb, ga, out, st) : run_gemm<A_CABS, E_PLAIN>(spec, fb, ga, out, st);
+    };
+    if (int e = run()) return e;
+    return dbd.enabled ? db_clamp(out, s->batch, (long long)s->channels * F * n_filt, dbd.dyn, stats, st, slots) : 0;
+}
+
 // narrow matrices (LogmelToMFCC's DCT, small filterbanks) on contiguous rows of a multiple of four floats: the thin GEMM
 static bool thin_gemm_shape(int n_freq, int n_filt) { return (n_filt + 15) / 16 <= 4 && n_freq <= 512 && (n_freq & 3) == 0; }
 
@@ -866,7 +1052,7 @@ static Geom rows_geom(long long rows, long long frames, int channels, int n_freq
     return g;
 }
 
-enum { FB_PW, FB_WS, FB_BAND, FB_UNPACKED };      // FB_UNPACKED: kpr_apply_filterbank_f32 (thin GEMM or generic GEMM)
+enum { FB_PW, FB_WS, FB_BAND, FB_UNPACKED };      // FB_UNPACKED: run_apply_filterbank_f32 (thin GEMM or generic GEMM)
 
 // calls whose packed filterbank is verified (get_sched + verify_packed) ahead of fb_route
 static bool fb_packed_candidate(const float* x, const float* fb_packed, const float* out, long long rows, int n_freq, int n_filt) {
@@ -891,6 +1077,90 @@ static int fb_route(bool verified, const PackInfo& pi, const MelSched& sch, cons
         sizeof(float) * (size_t)kBandRows * n_freq <= 160 * 1024 && get_sched(n_freq, n_filt, kr, band_sch) == 0)
         return FB_BAND;
     return FB_UNPACKED;
+}
+
+// ---- kpr_apply_filterbank_f32: the thin GEMM on its shapes, else the generic GEMM (with the k-ranges, if given) ----
+static int run_apply_filterbank_f32(const float* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout, const float* fb,
+                                    int n_filt, const int32_t* fb_kranges_host, float* out, kpr_stream_t stream) {
+    if (int e = check_rows_args(batch, channels, frames, n_freq, n_filt, layout, "bad sizes", "bad layout enum")) return e;
+    const long long rows = batch * channels * frames;
+    if (rows == 0) return 0;
+    if (!x || !fb || !out) return fail(KPR_E_BADARG, "x / fb / out must not be NULL");
+    const int ntiles = (n_filt + 15) / 16;
+    if (ntiles > kMaxTiles || n_freq > 32000) fb_kranges_host = nullptr;   // GemmArgs holds 16-bit k-ranges for 64 tiles: dense product
+    const bool contiguous = layout == KPR_CHANNELS_FIRST || channels == 1;
+    if (contiguous && thin_gemm_shape(n_freq, n_filt) && (((uintptr_t)x) & 15) == 0) {
+        const size_t lds = sizeof(float) * 4 * 64 * (size_t)ntiles * ((n_freq + 15) / 16);
+        const unsigned grid = (unsigned)std::min<long long>((rows + 63) / 64, 256 * 8);
+        hipStream_t st = (hipStream_t)stream;
+        // thin_gemm_shape admits up to 4 tiles x 32 k-groups = 128 KiB of B fragments: above 64 KiB the instance opts in
+        auto launch = [&](auto nt) -> int {
+            static LdsOptIn lds_opt_in;
+            if (lds > 64 * 1024)
+                if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_thin_gemm<nt>))) return e;
+            hipLaunchKernelGGL(k_thin_gemm<nt>, dim3(grid), dim3(256), lds, st, x, rows, n_freq, fb, n_filt, out);
+            return launch_check("k_thin_gemm");
+        };
+        switch (ntiles) {
+            case 1: return launch(std::integral_constant<int, 1>{});
+            case 2: return launch(std::integral_constant<int, 2>{});
+            case 3: return launch(std::integral_constant<int, 3>{});
+            default: return launch(std::integral_constant<int, 4>{});
+        }
+    }
+    GemmArgs ga{};
+    ga.in.rows = rows; ga.out.rows = rows;
+    if (layout == KPR_CHANNELS_LAST) {
+        // rows r = (b*F + f)*C + c
+        ga.in.D0 = channels; ga.in.D1 = 1;
+        ga.in.s2 = (long long)n_freq * channels; ga.in.s1 = 0; ga.in.s0 = 1; ga.in.es = channels;
+        ga.out.D0 = channels; ga.out.D1 = 1;
+        ga.out.s2 = (long long)n_filt * channels; ga.out.s1 = 0; ga.out.s0 = 1; ga.out.es = channels;
+    } else {
+        ga.in.D0 = 1; ga.in.D1 = 1; ga.in.s2 = n_freq; ga.in.s1 = 0; ga.in.s0 = 0; ga.in.es = 1;
+        ga.out.D0 = 1; ga.out.D1 = 1; ga.out.s2 = n_filt; ga.out.s1 = 0; ga.out.s0 = 0; ga.out.es = 1;
+    }
+    ga.Kdim = n_freq; ga.N = n_filt; ga.ldb = n_filt;
+    if (fb_kranges_host) {
+        const int kp = (n_freq + 3) & ~3;
+        ga.has_kr = 1;
+        for (int t = 0; t < ntiles; ++t) {
+            int lo = fb_kranges_host[2 * t], hi = fb_kranges_host[2 * t + 1];
+            if (lo < 0 || hi > kp || lo > hi) return fail(KPR_E_BADARG, "bad k-range");
+            ga.klo[t] = (short)lo; ga.khi[t] = (short)hi;
+        }
+    }
+    return run_gemm<A_PLAIN, E_PLAIN>(x, fb, ga, out, (hipStream_t)stream);
+}
+
+// ---- kpr_apply_filterbank_packed_f32: the kernels of a verified packed filterbank (fb_route), else the body above ----
+static int run_apply_filterbank_packed_f32(const float* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout,
+                                           const float* fb, const float* fb_packed, int n_filt, const int32_t* fb_kranges_host,
+                                           float* out, kpr_stream_t stream) {
+    if (int e = check_rows_args(batch, channels, frames, n_freq, n_filt, layout, "bad sizes", "bad layout enum")) return e;
+    const long long rows = batch * channels * frames;
+    const bool contiguous = layout == KPR_CHANNELS_FIRST || channels == 1;
+    hipStream_t st = (hipStream_t)stream;
+    MelSched sch{};
+    PackInfo pinfo{0, 0, 0, 0, 0};
+    const bool verified = fb_packed_candidate(x, fb_packed, out, rows, n_freq, n_filt) &&
+                          get_sched(n_freq, n_filt, fb_kranges_host, &sch) == 0;
+    if (verified)
+        if (int e = verify_packed(fb_packed, n_freq, n_filt, fb_kranges_host, sch, st, &pinfo)) return e;
+    switch (fb_route(verified, pinfo, sch, x, fb, out, rows, channels, n_freq, n_filt, contiguous, fb_kranges_host, &sch)) {
+        case FB_PW:
+            return with_pow2((int)pinfo.L * kPts, [&](auto nc) {
+                return contiguous ? launch_fb_pw<nc, false>(x, rows, n_freq, fb_packed, pinfo, n_filt, fb, out, st)
+                                  : launch_fb_pw<nc, true>(x, rows / 2, n_freq, fb_packed, pinfo, n_filt, fb, out, st);
+            });
+        case FB_WS:
+            return launch_mel_ws<1024, true>(mel_ws_form(sch, true, n_freq), x, rows_geom(rows, frames, channels, n_freq, !contiguous),
+                                             nullptr, nullptr, fb_packed + kPackHeaderFloats, sch, make_db(nullptr), nullptr, out, st);
+        case FB_BAND:
+            return run_band_mel(x, rows_geom(rows, frames, channels, n_freq, false), fb, sch, make_db(nullptr), nullptr, out, st);
+        default:
+            return run_apply_filterbank_f32(x, batch, channels, frames, n_freq, layout, fb, n_filt, fb_kranges_host, out, stream);
+    }
 }
 
 }  // namespace kpr

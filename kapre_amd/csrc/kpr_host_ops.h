@@ -1,8 +1,9 @@
-// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, signal, augmentation, companding, PCEN, CMVN,
-// Resample, TimeStretch and HPSS entry points (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
+// kpr_host_ops.h -- the run_* bodies (argument checks + launch) of the elementwise, decibel, float64 filterbank, signal (Frame, Energy,
+// Delta), augmentation, companding, PCEN, CMVN, Resample, TimeStretch and HPSS entry points, forward and backward, and the host-only
+// frame count and resample table (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
 // kpr_augment_kernels.h, kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h,
-// kpr_time_stretch_kernels.h, kpr_hpss_kernels.h).  The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch
-// (kpr_host.h; the device side is kpr_cols.h).
+// kpr_time_stretch_kernels.h, kpr_hpss_kernels.h).  No body restarts the launch log or reads the status word: the entry points do.
+// The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch (kpr_host.h; device side: kpr_cols.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
 
@@ -12,7 +13,6 @@ namespace kpr {
 // (the two precisions have always worded a negative n differently)
 template <typename T>
 static int run_cplx_to_real(const void* x, int64_t n, int phase, T* out, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (n < 0) return fail(KPR_E_BADARG, sizeof(T) == 4 ? "negative size" : "negative element count");
     if (n == 0) return 0;
     if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
@@ -94,7 +94,6 @@ static int stream_ptrs(const void* in, const void* in2, const void* out, int64_t
 template <int OP>
 static int run_mu_law(const void* in, const void* g, void* out, int64_t n, int quantization_channels, const char* names,
                       kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     MuLawDev p;
     if (int e = mu_law_args(n, quantization_channels, &p)) return e;
     if (n == 0) return 0;
@@ -108,7 +107,6 @@ static int run_mu_law(const void* in, const void* g, void* out, int64_t n, int q
 template <bool DROP>
 static int run_freq_map(const float* in, int64_t batch, int channels, int64_t frames, int n_freq, int layout, float* out,
                         kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (batch < 0 || channels <= 0 || frames < 0 || n_freq <= 0 || (unsigned)layout > 1u)
         return fail(KPR_E_BADARG, "bad batch/channels/frames/n_freq/layout");
     const long long plane = (long long)frames * n_freq;
@@ -149,7 +147,6 @@ static int run_pcen(bool bwd, const float* x, const float* smooth, const float* 
                     int band_div, int n_bands, const float* s, const float* alpha, const float* delta, const float* r, float eps,
                     float* out, float* smooth_out, kpr_stream_t stream, bool with_params = false, float* gparams = nullptr,
                     void* workspace = nullptr, size_t workspace_bytes = 0) {
-    if (int e = api_enter()) return e;
     if (outer < 0 || frames < 0 || inner < 0 || band_div <= 0 || n_bands <= 0)
         return fail(KPR_E_BADARG, "bad outer/frames/inner/band_div/n_bands");
     if (with_params && (!gparams || ((uintptr_t)gparams & 3))) return fail(KPR_E_BADARG, "gparams must be a 4-byte aligned pointer");
@@ -234,7 +231,6 @@ static void launch_cmvn(int mode, dim3 grid, dim3 block, hipStream_t st, const C
 
 static int run_cmvn(bool bwd, const float* x, const float* rstd, const float* gy, int64_t outer, int64_t frames, int64_t inner,
                     int norm_vars, float eps, float* out, float* rstd_out, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (outer < 0 || frames < 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/frames/inner");
     if (norm_vars != 0 && norm_vars != 1) return fail(KPR_E_BADARG, "norm_vars must be 0 or 1, got %d", norm_vars);
     if (!bwd && !(eps >= 0.0f && std::isfinite(eps))) return fail(KPR_E_BADARG, "eps must be finite and not negative");
@@ -346,6 +342,32 @@ static int resample_size(int orig_freq, int new_freq, int lowpass_filter_width, 
     return 0;
 }
 
+// kpr_resample_table: table_host[P][n_taps] and first_host[P] of the construction above (host only)
+static int resample_table(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, float* table_host,
+                          int32_t* first_host) {
+    ResampleShape r;
+    if (!table_host || !first_host) return fail(KPR_E_BADARG, "table_host / first_host must not be NULL");
+    if (int e = resample_size(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint, &r)) return e;
+    const double scale = r.rolloff * (double)std::min(r.orig, r.fnew) / (double)r.orig;
+    const double per_u = r.rolloff / (double)std::max(r.orig, r.fnew);
+    for (int p = 0; p < r.P; ++p) {
+        long long lo, hi;
+        resample_support(r, p, &lo, &hi);
+        first_host[p] = (int32_t)lo;
+        for (int k = 0; k < r.n_taps; ++k) {
+            const long long j = lo + k;
+            double v = 0.0;
+            if (j <= hi) {
+                const double t = (double)(j * r.P - (long long)p * r.Q) * per_u;     // base tau
+                const double c = std::cos(M_PI * t / (2.0 * r.L));
+                v = scale * (t == 0.0 ? 1.0 : std::sin(M_PI * t) / (M_PI * t)) * c * c;
+            }
+            table_host[(size_t)p * r.n_taps + k] = (float)v;
+        }
+    }
+    return 0;
+}
+
 // the tile of the dispatch: `pt` phases x `nb` blocks per workgroup, work items of 8 blocks `ng` apart (kpr_resample_kernels.h).
 // The staged span of a tile is at most (nb - 1) Q + (first[p0 + pt - 1] - first[p0]) + n_taps words per channel; the plan holds
 // for both channel counts of the kernel, so kpr_resample_plan needs no layout.
@@ -404,7 +426,6 @@ static int resample_dims(int n_phases, int n_taps, int step) {
 
 static int run_resample(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table, const int32_t* first,
                         int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (batch < 0 || channels <= 0 || in_len < 0 || out_len < 0 || (unsigned)layout > 1u)
         return fail(KPR_E_BADARG, "bad batch/channels/in_len/out_len/layout");
     if (int e = resample_dims(n_phases, n_taps, step)) return e;
@@ -453,7 +474,6 @@ static int run_resample(const float* x, int64_t batch, int channels, int64_t in_
 // x: (outer, frames_in, inner) complex64 -> out: (outer, frames_out, inner); idx / alpha: frames_out device entries, never read here
 static int run_time_stretch(const void* x, int64_t outer, int64_t frames_in, int64_t frames_out, int64_t inner, const int32_t* idx,
                             const float* alpha, void* out, uint32_t* phase_out, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (outer < 0 || frames_in < 0 || frames_out < 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/frames_in/frames_out/inner");
     const long long lim = 1LL << 30;
     if (inner > 0 && (frames_in > (lim - 1) / inner || frames_out > (lim - 1) / inner))
@@ -507,7 +527,6 @@ static int hpss_half_windows(int kh, int kp, int* hh, int* hp) {
 template <bool CPLX>
 static int run_hpss(const void* x, int64_t batch, int ch, int64_t frames, int64_t freq, int layout, int kh, int kp, double power,
                     double margin_h, double margin_p, int want_mask, void* out_h, void* out_p, int out_ch, kpr_stream_t stream) {
-    if (int e = api_enter()) return e;
     if (batch < 0 || ch < 0 || frames < 0 || freq < 0 || (unsigned)layout > 1u) return fail(KPR_E_BADARG, "bad batch/ch/frames/freq/layout");
     int hh, hp;
     if (int e = hpss_half_windows(kh, kp, &hh, &hp)) return e;
@@ -573,16 +592,95 @@ static int run_hpss(const void* x, int64_t batch, int ch, int64_t frames, int64_
     return launch_check("k_hpss", small ? 15 : 31, CPLX ? "c64" : "f32");
 }
 
+// ---- Frame / Energy / Delta (kpr_signal_kernels.h) and their backward passes (kpr_grad_kernels.h) ----
+// frames per signal (kpr_frame_count); -1 with the message set: bad sizes
+static int64_t frame_count(int64_t time, int frame_length, int hop_length, int pad_end) {
+    if (time < 0 || frame_length <= 0 || hop_length <= 0) {
+        fail(KPR_E_BADARG, "bad time/frame_length/hop_length (%lld, %d, %d)", (long long)time, frame_length,
+             hop_length);
+        return -1;
+    }
+    if (pad_end) return (time + hop_length - 1) / hop_length;
+    return time < frame_length ? 0 : 1 + (time - frame_length) / hop_length;
+}
+
 static int frame_args(int64_t batch, int channels, int64_t time, int layout, int frame_length,
                       int hop_length, int pad_end, float pad_value, FrameArgs* a) {
     if (batch < 0 || channels <= 0 || (unsigned)layout > 1u)
         return fail(KPR_E_BADARG, "bad batch/channels/layout (%lld, %d, %d)", (long long)batch, channels, layout);
-    const int64_t f = kpr_frame_count(time, frame_length, hop_length, pad_end);
+    const int64_t f = frame_count(time, frame_length, hop_length, pad_end);
     if (f < 0) return KPR_E_BADARG;
     if (f > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many frames per signal");
     a->n_sig = batch * channels; a->T = time; a->C = channels; a->F = (int)f; a->L = frame_length;
     a->hop = hop_length; a->cl = layout == KPR_CHANNELS_LAST && channels > 1; a->pad_value = pad_value;
     return 0;
+}
+
+static int run_frame_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, int frame_length, int hop_length,
+                         int pad_end, float pad_value, float* out, kpr_stream_t stream) {
+    FrameArgs a;
+    if (int e = frame_args(batch, channels, time, layout, frame_length, hop_length, pad_end, pad_value, &a))
+        return e;
+    const long long nrows = (a.cl ? (long long)batch : a.n_sig) * a.F;
+    if (nrows == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    const int rowlen = a.cl ? a.L * a.C : a.L;
+    const bool vec = (rowlen & 3) == 0 && (((uintptr_t)out) & 15) == 0;
+    const long long work = nrows * (vec ? rowlen / 4 : rowlen);
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_frame<v>, dim3(grid_1d(work, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, a, out, nrows);
+    });
+    return launch_check("k_frame");
+}
+
+static int run_energy_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, int frame_length, int hop_length,
+                          int pad_end, float pad_value, float scale, float* out, kpr_stream_t stream) {
+    FrameArgs a;
+    if (int e = frame_args(batch, channels, time, layout, frame_length, hop_length, pad_end, pad_value, &a))
+        return e;
+    a.cl = layout == KPR_CHANNELS_LAST;            // output order depends on it even for one channel
+    const long long nout = a.n_sig * a.F;
+    if (nout == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if (time == 0) return fail(KPR_E_UNSUPPORTED, "energy of an empty signal with pad_end");
+    const int chunks = (a.F + kEnFrames - 1) / kEnFrames;
+    const int q = frame_length / hop_length;
+    size_t lds = sizeof(float) * 2 * (size_t)(kEnFrames + q + 1);
+    if (lds > 64 * 1024) return fail(KPR_E_UNSUPPORTED, "frame_length / hop_length = %d is too large", q);
+    // room for one partial sum per float4 of a workgroup's range (streaming path), when it fits 64 KiB
+    int part_words = 0;
+    if (hop_length % 4 == 0) {
+        const size_t pw = (size_t)(kEnFrames + q + 1) * (hop_length / 4);
+        if (lds + sizeof(float) * pw <= 64 * 1024) { part_words = (int)pw; lds += sizeof(float) * pw; }
+    }
+    hipLaunchKernelGGL(k_energy, dim3((unsigned)std::min<long long>(a.n_sig * chunks, 1 << 16)), dim3(256), lds,
+                       (hipStream_t)stream, x, a, scale, out, chunks, part_words);
+    return launch_check("k_energy");
+}
+
+static int run_frame_bwd_f32(const float* g, int64_t batch, int channels, int64_t time, int layout, int frame_length,
+                             int hop_length, int pad_end, float* gx, kpr_stream_t stream) {
+    FrameArgs a;
+    if (int e = frame_args(batch, channels, time, layout, frame_length, hop_length, pad_end, 0.0f, &a)) return e;
+    a.cl = layout == KPR_CHANNELS_LAST;
+    const long long total = a.n_sig * a.T;
+    if (total == 0) return 0;
+    if (!gx || (!g && a.F > 0)) return fail(KPR_E_BADARG, "g / gx must not be NULL");
+    hipLaunchKernelGGL(k_frame_bwd, dim3(grid_1d(total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, g, a, gx);
+    return launch_check("k_frame_bwd");
+}
+
+static int run_energy_bwd_f32(const float* x, const float* g, int64_t batch, int channels, int64_t time, int layout,
+                              int frame_length, int hop_length, int pad_end, float scale, float* gx, kpr_stream_t stream) {
+    FrameArgs a;
+    if (int e = frame_args(batch, channels, time, layout, frame_length, hop_length, pad_end, 0.0f, &a)) return e;
+    a.cl = layout == KPR_CHANNELS_LAST;
+    const long long total = a.n_sig * a.T;
+    if (total == 0) return 0;
+    if (!x || !gx || (!g && a.F > 0)) return fail(KPR_E_BADARG, "x / g / gx must not be NULL");
+    hipLaunchKernelGGL(k_energy_bwd, dim3(grid_1d(total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, g, a,
+                       scale, gx);
+    return launch_check("k_energy_bwd");
 }
 
 // Delta and its backward pass: the checks, the rows x columns view of the tensor and the filter's half width and scale
@@ -603,6 +701,32 @@ static int delta_args(int64_t batch, int channels, int64_t frames, int n_freq, i
     return 0;
 }
 
+static int run_delta_f32(const float* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout, int win_length,
+                         int pad_mode, float* out, kpr_stream_t stream) {
+    DeltaArgs a;
+    if (int e = delta_args(batch, channels, frames, n_freq, layout, win_length, pad_mode, &a)) return e;
+    if (a.total == 0) return 0;
+    if (!x || !out || x == out) return fail(KPR_E_BADARG, "x / out must not be NULL or aliased");
+    const bool vec = (a.inner & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_delta<v>, dim3(grid_1d(a.total / v, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, a.outer,
+                           (long long)frames, a.inner, a.n, pad_mode, a.scale, out);
+    });
+    return launch_check("k_delta");
+}
+
+static int run_delta_bwd_f32(const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int layout, int win_length,
+                             int pad_mode, float* gx, kpr_stream_t stream) {
+    DeltaArgs a;
+    if (int e = delta_args(batch, channels, frames, n_freq, layout, win_length, pad_mode, &a)) return e;
+    if (a.total == 0) return 0;
+    if (!g || !gx || g == gx) return fail(KPR_E_BADARG, "g / gx must not be NULL or aliased");
+    hipLaunchKernelGGL(k_delta_bwd, dim3(grid_1d(a.total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, g, a.outer,
+                       (long long)frames, a.inner, a.n, pad_mode, a.scale, gx);
+    return launch_check("k_delta_bwd");
+}
+
+// ---- SpecAugment / ChannelSwap (kpr_augment_kernels.h) ----
 static int aug_geom(int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq, AugGeom* a) {
     if (n_items < 0 || n_time <= 0 || n_freq <= 0) return fail(KPR_E_BADARG, "bad n_items/n_time/n_freq");
     if (n_time_masks < 0 || n_freq_masks < 0 || n_time_masks > kAugMaxMasks || n_freq_masks > kAugMaxMasks)
@@ -612,6 +736,155 @@ static int aug_geom(int64_t n_items, int n_time_masks, int n_freq_masks, int n_t
                     (long long)n_time * n_freq);
     *a = AugGeom{(int)n_items, n_time_masks, n_freq_masks, n_time, n_freq, 0, 0};
     return 0;
+}
+
+static int run_spec_augment_draw(int32_t* table, int64_t n_items, int n_time_masks, int n_freq_masks, int n_time, int n_freq,
+                                 int time_mask_param, int freq_mask_param, void* state, kpr_stream_t stream) {
+    AugGeom a;
+    if (int e = aug_geom(n_items, n_time_masks, n_freq_masks, n_time, n_freq, &a)) return e;
+    // augmentation.py:245: an axis shorter than its mask parameter is an error (only asked of an axis that has masks)
+    if (n_time_masks > 0 && (time_mask_param < 1 || time_mask_param > n_time))
+        return fail(KPR_E_BADARG, "time_mask_param %d outside [1, n_time = %d]", time_mask_param, n_time);
+    if (n_freq_masks > 0 && (freq_mask_param < 1 || freq_mask_param > n_freq))
+        return fail(KPR_E_BADARG, "freq_mask_param %d outside [1, n_freq = %d]", freq_mask_param, n_freq);
+    // the draw is one workgroup (the counter has one writer): 2^20 entries are 1024 per lane, some tens of microseconds
+    if (n_items * (long long)(n_time_masks + n_freq_masks) > (1LL << 20))
+        return fail(KPR_E_UNSUPPORTED, "mask table of %lld entries: the one-workgroup draw takes at most 2^20",
+                    (long long)(n_items * (long long)(n_time_masks + n_freq_masks)));
+    if (!state) return fail(KPR_E_BADARG, "state must not be NULL");
+    if (a.n_items * (a.n_tm + a.n_fm) > 0 && !table) return fail(KPR_E_BADARG, "table must not be NULL");
+    a.tparam = time_mask_param;
+    a.fparam = freq_mask_param;
+    // (a call without entries still advances the counter: one launch, one step of the stream)
+    hipLaunchKernelGGL(k_specaug_draw, dim3(1), dim3(1024), 0, (hipStream_t)stream, table, a, (unsigned long long*)state);
+    return launch_check("k_specaug_draw");
+}
+
+static int run_index_draw(int32_t* out, int64_t n_items, int n_choices, void* state, kpr_stream_t stream) {
+    if (n_items < 0 || n_choices < 1) return fail(KPR_E_BADARG, "bad n_items / n_choices (%lld, %d)", (long long)n_items, n_choices);
+    if (n_items > (1LL << 20))
+        return fail(KPR_E_UNSUPPORTED, "%lld items: the one-workgroup draw takes at most 2^20", (long long)n_items);
+    if (!state) return fail(KPR_E_BADARG, "state must not be NULL");
+    if (n_items > 0 && !out) return fail(KPR_E_BADARG, "out must not be NULL");
+    if (ranges_overlap(out, (uintptr_t)n_items * 4, state, 16)) return fail(KPR_E_BADARG, "out overlaps state");
+    // (a call without items still advances the counter: one launch, one step of the stream)
+    hipLaunchKernelGGL(k_index_draw, dim3(1), dim3(1024), 0, (hipStream_t)stream, out, (int)n_items, (unsigned)n_choices,
+                       (unsigned long long*)state);
+    return launch_check("k_index_draw");
+}
+
+static int run_spec_augment_apply(const float* x, float* out, const int32_t* table, int64_t n_items, int n_time_masks,
+                                  int n_freq_masks, int n_time, int n_freq, float mask_value, kpr_stream_t stream) {
+    AugGeom a;
+    if (int e = aug_geom(n_items, n_time_masks, n_freq_masks, n_time, n_freq, &a)) return e;
+    if (n_items == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if (n_time_masks + n_freq_masks > 0 && !table) return fail(KPR_E_BADARG, "table must not be NULL");
+    const long long isz = (long long)n_time * n_freq;
+    const bool vec = ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    if (n_freq > kAugMaxFreq)
+        return fail(KPR_E_UNSUPPORTED, "n_freq = %d: the copy form holds at most %d bins per row", n_freq, kAugMaxFreq);
+    // partial overlap would let a workgroup read what another has already masked (out == x: in place)
+    const uintptr_t nb = (uintptr_t)(n_items * isz * 4);
+    if (x != out && ranges_overlap(x, nb, out, nb)) return fail(KPR_E_BADARG, "x and out overlap (only out == x, in place, is allowed)");
+    const long long chunks = (isz + kAugChunk - 1) / kAugChunk;
+    if (n_items * chunks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many items");
+    with_vec<4>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_specaug_apply<v>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, (hipStream_t)stream, x, table, a,
+                           (int)chunks, mask_value, out);
+    });
+    return launch_check("k_specaug_apply");
+}
+
+static int run_channel_gather(const void* x, void* out, int64_t outer, int n_ch, int64_t inner, int elem_bytes, const int32_t* perm,
+                              kpr_stream_t stream) {
+    if (outer < 0 || n_ch <= 0 || inner < 0) return fail(KPR_E_BADARG, "bad outer/n_ch/inner");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(KPR_E_BADARG, "elem_bytes must be 4 (float32) or 8 (complex64), got %d", elem_bytes);
+    if (n_ch > kGatherMaxCh)
+        return fail(KPR_E_UNSUPPORTED, "%d channels: the permutation travels in the kernel arguments, at most %d", n_ch, kGatherMaxCh);
+    if (!perm) return fail(KPR_E_BADARG, "perm must not be NULL");
+    GatherPerm gp{};
+    for (int c = 0; c < n_ch; ++c) {
+        if (perm[c] < 0 || perm[c] >= n_ch) return fail(KPR_E_BADARG, "perm[%d] = %d outside [0, %d)", c, perm[c], n_ch);
+        gp.p[c] = perm[c];
+    }
+    const long long words = inner * (elem_bytes / 4);                 // 4-byte words per (o, c) row
+    if (outer == 0 || words == 0) return 0;
+    if (!x || !out || x == out) return fail(KPR_E_BADARG, "x / out must not be NULL or aliased");
+    const long long rows = outer * n_ch;
+    if (words < 64) {
+        if (words * n_ch > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "row too long");
+        hipLaunchKernelGGL(k_channel_gather_rows, dim3(grid_1d(outer, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned*)x, (unsigned*)out, (long long)outer, n_ch, (int)words, gp);
+        return launch_check("k_channel_gather_rows");
+    }
+    const bool vec = (words & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    const long long units = vec ? words / 4 : words;
+    const dim3 grid((unsigned)std::min<long long>((units + 1023) / 1024, 64), (unsigned)std::min<long long>(rows, 65535));
+    if (vec)
+        hipLaunchKernelGGL(k_channel_gather<uint4>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)out, rows,
+                           n_ch, units, gp);
+    else
+        hipLaunchKernelGGL(k_channel_gather<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned*)x,
+                           (unsigned*)out, rows, n_ch, units, gp);
+    return launch_check("k_channel_gather");
+}
+
+// ---- float64 ApplyFilterbank and MagnitudeToDecibel (kpr_generic_kernels.h) ----
+static int run_apply_filterbank_f64(const double* x, int64_t batch, int channels, int64_t frames, int n_freq, int layout,
+                                    const double* fb, int n_filt, double* out, kpr_stream_t stream) {
+    if (int e = check_rows_args(batch, channels, frames, n_freq, n_filt, layout, "bad filterbank shape", "bad layout %d")) return e;
+    const long long total = (long long)batch * channels * frames * n_filt;
+    if (total == 0) return 0;
+    if (!x || !fb || !out) return fail(KPR_E_BADARG, "x / fb / out must not be NULL");
+    hipLaunchKernelGGL(k_filterbank_f64, dim3(grid_1d(total, 256)), dim3(256), 0, (hipStream_t)stream, x,
+                       (long long)batch, channels, (long long)frames, n_freq,
+                       (layout == KPR_CHANNELS_LAST && channels > 1) ? 1 : 0, fb, n_filt, out);
+    return launch_check("k_filterbank_f64");
+}
+
+static int run_mag_to_db_f64(const double* x, int64_t n_items, int64_t item_size, double ref_value, double amin,
+                             double dynamic_range, double* out, kpr_stream_t stream) {
+    if (n_items < 0 || item_size < 0) return fail(KPR_E_BADARG, "negative size");
+    if (int e = check_db_values(ref_value, amin, dynamic_range)) return e;
+    if (n_items == 0 || item_size == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if (n_items > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "float64 decibel: more than 2^31 - 1 items");
+    const double ref_term = 10.0 * std::log10(std::max(amin, ref_value));
+    hipLaunchKernelGGL(k_db_f64, dim3((unsigned)n_items), dim3(1024), 0, (hipStream_t)stream, x,
+                       (long long)item_size, amin, ref_term, dynamic_range, out);
+    return launch_check("k_db_f64");
+}
+
+// ---- float32 MagnitudeToDecibel: statistics, the log pass, the clamp (the helpers it shares with the fused mel: kpr_host_mel.h) ----
+static int64_t db_workspace_bytes(int64_t n_items) {
+    if (n_items < 0) return -1;
+    return 256 + (int64_t)sizeof(unsigned) * 2 * std::max<int64_t>(1, n_items);
+}
+
+static int run_mag_to_db_f32(const float* x, int64_t n_items, int64_t item_size, const kpr_db_params* db, float* out,
+                             void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
+    if (!db) return fail(KPR_E_BADARG, "db params are NULL");
+    kpr_db_params p = *db;
+    p.enabled = 1;
+    if (int e = check_db(&p)) return e;
+    if (n_items < 0 || item_size < 0) return fail(KPR_E_BADARG, "negative size");
+    if (n_items == 0 || item_size == 0) return 0;
+    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if (!workspace || workspace_bytes < db_workspace_bytes(n_items))
+        return fail(KPR_E_WORKSPACE, "db workspace: need %lld bytes", (long long)db_workspace_bytes(n_items));
+    hipStream_t st = (hipStream_t)stream;
+    DbDev dbd = make_db(&p);
+    unsigned* stats = reinterpret_cast<unsigned*>(workspace);
+    if (int e = stats_init(stats, n_items, st)) return e;
+    int chunks = db_chunks(n_items, item_size);
+    if (opt(OPT_DB_CHUNKS) > 0) chunks = opt(OPT_DB_CHUNKS);
+    // (aligned bases: 16-byte accesses on the aligned middle of every chunk)
+    with_vec<4>(((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0, [&](auto v) {
+        hipLaunchKernelGGL(k_db_log<v>, dim3((unsigned)(n_items * chunks)), dim3(256), 0, st, x, (long long)item_size, chunks, dbd, stats, out);
+    });
+    if (int e = launch_check("k_db_log")) return e;
+    return db_clamp(out, n_items, item_size, dbd.dyn, stats, st);
 }
 
 }  // namespace kpr

@@ -1,6 +1,6 @@
 // kpr_host_stft.h -- host side of kpr_stft_kernels.h (and of the forward kernel of kpr_generic_kernels.h): the DFT-as-GEMM forward
-// transform, the launchers of every forward FFT family, stft_pow2_kernel, StftRoute / stft_route, launch_stft, and run_stft_f32,
-// the body of kpr_stft_f32.
+// transform, the launchers of every forward FFT family, stft_pow2_kernel, StftRoute / stft_route, launch_stft, stft_workspace_bytes,
+// and run_stft_f32 / run_stft_f64, the bodies of kpr_stft_f32 / kpr_stft_f64.
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_fft.h; not stand-alone).
 #pragma once
 
@@ -166,14 +166,17 @@ static int launch_stft_bs(const float* x, const Geom& g, const float* window, in
     return with_pow2(m, [&](auto m_c) { return launch_stft_bs_m<m_c>(x, g, window, tw, bs, mode, out, st); });
 }
 
-static int launch_stft_gen_f32(const float* x, const Geom& g, const float* window, int mode, void* out, hipStream_t st) {
+// the run-time mixed-radix forward FFT, T = float (FAM_GEN) or double (run_stft_f64); LDS opt-in state per T and instance
+template <typename T>
+static int launch_stft_gen(const T* x, const Geom& g, const T* window, int mode, void* out, hipStream_t st) {
+    typedef typename Cplx<T>::type T2;
     GenLaunch l;
-    if (int e = gen_launch_plan(sizeof(float2), g.n_fft, &l)) return e;
-    const float2* tw = nullptr;
-    if (int e = get_twiddles(g.n_fft, &tw)) return e;
+    if (int e = gen_launch_plan(sizeof(T2), g.n_fft, &l)) return e;
+    const T2* tw = nullptr;
+    if (int e = twiddles_of<T>(g.n_fft, &tw)) return e;
     static LdsOptIn opt_in[2];
-    return launch_gen(l.tw_lds ? &k_stft_gen<float, true> : &k_stft_gen<float, false>, opt_in[l.tw_lds ? 1 : 0], l, g, st,
-                      "k_stft_gen<float>", x, g, window, tw, l.p, mode, out);
+    return launch_gen(l.tw_lds ? &k_stft_gen<T, true> : &k_stft_gen<T, false>, opt_in[l.tw_lds ? 1 : 0], l, g, st,
+                      sizeof(T) == 4 ? "k_stft_gen<float>" : "k_stft_gen<double>", x, g, window, tw, l.p, mode, out);
 }
 
 struct StftRoute {
@@ -213,12 +216,20 @@ static int launch_stft(const StftRoute& r, const float* x, const Geom& g, const 
         case FAM_MR:  return launch_stft_mr(x, g, window, mode, out, st);
         case FAM_BS:  return launch_stft_bs(x, g, window, mode, out, st);
         case FAM_BIG: return launch_stft_big(x, g, window, mode, out, st);
-        case FAM_GEN: return launch_stft_gen_f32(x, g, window, mode, out, st);
+        case FAM_GEN: return launch_stft_gen<float>(x, g, window, mode, out, st);
         default:      return stft_gemm(x, g, window, (float*)out, st);
     }
 }
 
-// ---- kpr_stft_f32 behind api_enter: checks, route, launch (kpr_griffin_lim_f32 runs it once per iteration) ----
+// kpr_stft_workspace_bytes (and the forward transforms of Griffin-Lim)
+static int64_t stft_workspace_bytes(const kpr_stft_geom* s, int mode) {
+    if (check_geom(s)) return -1;
+    const kpr_stft_geom se = forward_geom(s);
+    // (no device query: the CU count only picks among kernels that need no workspace)
+    return stft_route(&se, make_geom(&se, frames_of(s)), mode, 256).workspace;
+}
+
+// ---- kpr_stft_f32: checks, route, launch (run_griffin_lim runs it once per iteration) ----
 static int run_stft_f32(const float* x, const kpr_stft_geom* s, const float* window, void* out, int mode,
                         void* workspace, int64_t workspace_bytes, kpr_stream_t stream) {
     if (int e = check_geom(s)) return e;
@@ -242,6 +253,18 @@ static int run_stft_f32(const float* x, const kpr_stft_geom* s, const float* win
     hipLaunchKernelGGL(k_cplx_to_real, dim3(grid_1d(n, 256)), dim3(256), 0, st,
                        (const float2*)workspace, n, mode == KPR_OUT_PHASE ? 1 : 0, (float*)out);
     return launch_check("k_cplx_to_real");
+}
+
+// ---- kpr_stft_f64: the generic engine at every transform size ----
+static int run_stft_f64(const double* x, const kpr_stft_geom* s, const double* window, void* out, int mode, kpr_stream_t stream) {
+    if (int e = check_geom(s)) return e;
+    if (mode < KPR_OUT_COMPLEX || mode > KPR_OUT_PHASE) return fail(KPR_E_BADARG, "bad mode %d", mode);
+    const long long F = frames_of(s);
+    Geom g = make_geom(s, F);
+    if (g.total_frames == 0) return 0;
+    if (!x || !window || !out) return fail(KPR_E_BADARG, "x / window / out must not be NULL");
+    g.win = std::min(g.win, g.n_fft);                            // win_length > n_fft: cropped frames (see forward_geom)
+    return launch_stft_gen<double>(x, g, window, mode, out, (hipStream_t)stream);
 }
 
 }  // namespace kpr

@@ -429,3 +429,222 @@ def test_gradient_request_without_a_gpu_fails_loudly():
     for layer in (kapre.STFT(n_fft=256, hop_length=64), kapre.MagnitudeToDecibel(), kapre.Delta(win_length=5)):
         with pytest.raises(RuntimeError, match='HIP device'):
             layer(x if not isinstance(layer, (kapre.MagnitudeToDecibel, kapre.Delta)) else torch.ones(1, 5, 7, 1, requires_grad=True))
+
+
+# ---------------------------------------------------------------------------------------------
+# refusals of the entry points whose bodies live in the kpr_host_*.h headers: return code and message
+# ---------------------------------------------------------------------------------------------
+P, Q, R, S = 0x10000, 0x20000, 0x30000, 0x40000       # device pointers that no refusal dereferences
+BIG = 1 << 40
+
+
+def _geom(batch=2, channels=1, time=4000, n_fft=512, win=512, hop=128, pad_begin=0, pad_end=0, il=0, ol=0):
+    return ctypes.byref(_ffi.StftGeom(batch, channels, time, n_fft, win, hop, pad_begin, pad_end, il, ol))
+
+
+def _db(enabled=1, ref=1.0, amin=1e-5, dyn=80.0):
+    return ctypes.byref(_ffi.DbParams(enabled, ref, amin, dyn))
+
+
+def _i32(*v):
+    a = np.asarray(v, np.int32)
+    return a, a.ctypes.data
+
+
+def _f64(*v):
+    return (ctypes.c_double * len(v))(*v)
+
+
+BAD_KR, BAD_KR_PTR = _i32(-4, 8)
+PERM_OK, PERM_OK_PTR = _i32(1, 0)
+PERM_BAD, PERM_BAD_PTR = _i32(0, 5)
+COEF_OK, COEF_UNSTABLE = _f64(1.0, 0.0, 0.0, -0.5, 0.25), _f64(1.0, 0.0, 0.0, 0.0, 2.0)
+BAD_GEOM = dict(channels=0)
+LONG64 = dict(time=40000, n_fft=20000, win=20000, hop=5000)       # no float64 plan: two frame buffers exceed the LDS
+
+# (entry point, arguments, return code, fragment of kpr_last_error() or None); "2:" rows have two faults and pin which one is reported
+REFUSALS = [
+    # ---- fused mel
+    ("kpr_mel_f32", lambda: (P, _geom(**BAD_GEOM), P, P, None, 40, None, None, P, P, BIG, None), -1, b"bad batch/channels/time"),
+    ("kpr_mel_f32", lambda: (P, _geom(il=2), P, P, None, 40, None, None, P, P, BIG, None), -1, b"bad layout enum"),
+    ("kpr_mel_f32", lambda: (P, _geom(), P, P, None, 40, None, _db(ref=0.0), P, P, BIG, None), -1, b"ref_value must be positive"),
+    ("kpr_mel_f32", lambda: (P, _geom(), P, P, None, 0, None, None, P, P, BIG, None), -1, b"n_filt must be positive"),
+    ("kpr_mel_f32", lambda: (P, _geom(**BAD_GEOM), P, P, None, 0, None, _db(amin=0.0), P, P, BIG, None), -1, b"2:bad batch/channels/time"),
+    ("kpr_mel_f32", lambda: (P, _geom(), P, P, None, 0, None, _db(dyn=0.0), P, P, BIG, None), -1, b"2:dynamic_range must be positive"),
+    ("kpr_mel_f32", lambda: (None, _geom(), P, P, None, 40, None, None, P, P, BIG, None), -1, b"x / window / fb / out must not be NULL"),
+    ("kpr_mel_f32", lambda: (P, _geom(), P, P, None, 40, None, None, P, P, 767, None), -4, b"mel workspace: need 768 bytes"),
+    ("kpr_mel_f32", lambda: (P, _geom(), P, P, None, 40, None, None, None, None, 0, None), -1, b"2:x / window / fb / out must not be NULL"),
+    ("kpr_mel_f32", lambda: (P, _geom(n_fft=400, win=400, hop=100), P, P, None, 40, None, None, P, None, BIG, None), -4,
+     b"mel workspace: need 119760 bytes"),
+    ("kpr_mel_workspace_bytes", lambda: (_geom(**BAD_GEOM), 40, None), -1, b"bad batch/channels/time"),
+    ("kpr_mel_workspace_bytes", lambda: (_geom(), 0, None), -1, None),
+    ("kpr_mel_workspace_bytes_unpacked", lambda: (_geom(hop=0), 40), -1, b"bad n_fft/win_length/hop_length"),
+    ("kpr_mel_workspace_bytes_unpacked", lambda: (_geom(), 0), -1, None),
+    # ---- the packed filterbank (host only)
+    ("kpr_filterbank_pack_floats", lambda: (0, 40, None), -1, None),
+    ("kpr_filterbank_pack_floats", lambda: (257, 1025, None), -1, b"exceeds the 1024-filter limit"),
+    ("kpr_filterbank_pack_floats", lambda: (257, 16, BAD_KR_PTR), -1, b"bad filterbank k-range for tile 0"),
+    ("kpr_filterbank_pack", lambda: (None, 257, 16, None, P), -1, b"bad arguments to kpr_filterbank_pack"),
+    ("kpr_filterbank_pack", lambda: (P, 257, 16, None, None), -1, b"bad arguments to kpr_filterbank_pack"),
+    ("kpr_filterbank_pack", lambda: (P, 257, 16, BAD_KR_PTR, P), -1, b"bad filterbank k-range for tile 0"),
+    ("kpr_filterbank_pack", lambda: (P, 257, 1025, None, P), -2, b"exceeds the 1024-filter limit"),
+    ("kpr_filterbank_pack", lambda: (P, 257, 0, BAD_KR_PTR, P), -1, b"2:bad arguments to kpr_filterbank_pack"),
+    ("kpr_filterbank_kranges", lambda: (P, 0, 16, P), -1, b"bad arguments to kpr_filterbank_kranges"),
+    ("kpr_filterbank_kranges", lambda: (None, 257, 0, None), -1, b"2:bad arguments to kpr_filterbank_kranges"),
+    # ---- ApplyFilterbank (n_freq 10 is no thin-GEMM shape: the generic GEMM's checks)
+    ("kpr_apply_filterbank_f32", lambda: (P, 2, 1, 5, 0, 0, Q, 13, None, R, None), -1, b"bad sizes"),
+    ("kpr_apply_filterbank_f32", lambda: (P, 2, 1, 5, 10, 2, Q, 13, None, R, None), -1, b"bad layout enum"),
+    ("kpr_apply_filterbank_f32", lambda: (P, -1, 1, 5, 10, 7, Q, 13, None, R, None), -1, b"2:bad sizes"),
+    ("kpr_apply_filterbank_f32", lambda: (None, 2, 1, 5, 10, 0, Q, 13, None, R, None), -1, b"x / fb / out must not be NULL"),
+    ("kpr_apply_filterbank_f32", lambda: (P, 2, 1, 5, 10, 0, Q, 13, BAD_KR_PTR, R, None), -1, b"bad k-range"),
+    ("kpr_apply_filterbank_f32", lambda: (P, 2, 1, 5, 10, 0, Q, 13, BAD_KR_PTR, None, None), -1, b"2:x / fb / out must not be NULL"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (P, 2, 0, 5, 10, 0, Q, None, 13, None, R, None), -1, b"bad sizes"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (P, 2, 1, 5, 10, -1, Q, None, 13, None, R, None), -1, b"bad layout enum"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (P, 2, 1, 5, 10, 0, None, None, 13, None, R, None), -1, b"x / fb / out must not be NULL"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (P, 2, 1, 5, 10, 0, Q, None, 13, BAD_KR_PTR, R, None), -1, b"bad k-range"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (None, 2, 1, 5, 10, 3, Q, S, 13, BAD_KR_PTR, R, None), -1, b"2:bad layout enum"),
+    ("kpr_apply_filterbank_packed_f32", lambda: (None, 2, 1, 5, 10, 0, Q, S, 13, BAD_KR_PTR, R, None), -1, b"2:x / fb / out must not be NULL"),
+    ("kpr_apply_filterbank_f64", lambda: (P, 2, 1, 5, 10, 0, Q, 0, R, None), -1, b"bad filterbank shape"),
+    ("kpr_apply_filterbank_f64", lambda: (P, 2, 1, 5, 10, 2, Q, 13, R, None), -1, b"bad layout 2"),
+    ("kpr_apply_filterbank_f64", lambda: (P, 2, 1, -5, 10, 2, Q, 13, R, None), -1, b"2:bad filterbank shape"),
+    ("kpr_apply_filterbank_f64", lambda: (P, 2, 1, 5, 10, 0, None, 13, R, None), -1, b"x / fb / out must not be NULL"),
+    ("kpr_apply_filterbank_f64", lambda: (None, 2, 1, 5, 10, 3, Q, 13, R, None), -1, b"2:bad layout 3"),
+    # ---- MagnitudeToDecibel
+    ("kpr_db_workspace_bytes", lambda: (-1,), -1, None),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, 100, None, Q, R, BIG, None), -1, b"db params are NULL"),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, 100, _db(enabled=0, ref=0.0), Q, R, BIG, None), -1, b"ref_value must be positive"),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, 100, _db(amin=-1.0), Q, R, BIG, None), -1, b"amin must be positive"),
+    ("kpr_mag_to_db_f32", lambda: (P, -3, 100, _db(), Q, R, BIG, None), -1, b"negative size"),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, -100, _db(amin=0.0), Q, R, BIG, None), -1, b"2:amin must be positive"),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, 100, _db(), None, R, BIG, None), -1, b"x / out must not be NULL"),
+    ("kpr_mag_to_db_f32", lambda: (P, 3, 100, _db(), Q, R, 279, None), -4, b"db workspace: need 280 bytes"),
+    ("kpr_mag_to_db_f32", lambda: (None, 3, 100, _db(), Q, None, 0, None), -1, b"2:x / out must not be NULL"),
+    ("kpr_mag_to_db_f64", lambda: (P, 3, -1, 1.0, 1e-5, 80.0, Q, None), -1, b"negative size"),
+    ("kpr_mag_to_db_f64", lambda: (P, 3, 100, 1.0, 1e-5, 0.0, Q, None), -1, b"dynamic_range must be positive"),
+    ("kpr_mag_to_db_f64", lambda: (P, -3, 100, 0.0, 1e-5, 80.0, Q, None), -1, b"2:negative size"),
+    ("kpr_mag_to_db_f64", lambda: (None, 3, 100, 1.0, 1e-5, 80.0, Q, None), -1, b"x / out must not be NULL"),
+    ("kpr_mag_to_db_f64", lambda: (P, 1 << 31, 1, 1.0, 1e-5, 80.0, Q, None), -2, b"float64 decibel: more than 2^31 - 1 items"),
+    ("kpr_mag_to_db_f64", lambda: (P, 1 << 31, 1, 1.0, 1e-5, 80.0, None, None), -1, b"2:x / out must not be NULL"),
+    # ---- float64 STFT / inverse STFT
+    ("kpr_stft_workspace_bytes", lambda: (_geom(**BAD_GEOM), 0), -1, b"bad batch/channels/time"),
+    ("kpr_stft_f64", lambda: (P, _geom(**BAD_GEOM), Q, R, 0, None), -1, b"bad batch/channels/time"),
+    ("kpr_stft_f64", lambda: (P, _geom(), Q, R, 3, None), -1, b"bad mode 3"),
+    ("kpr_stft_f64", lambda: (P, _geom(pad_begin=1, hop=1024), Q, R, -1, None), -1, b"2:pad_begin needs n_fft >= hop_length"),
+    ("kpr_stft_f64", lambda: (None, _geom(), Q, R, 0, None), -1, b"x / window / out must not be NULL"),
+    ("kpr_stft_f64", lambda: (None, _geom(), Q, R, 3, None), -1, b"2:bad mode 3"),
+    ("kpr_stft_f64", lambda: (P, _geom(**LONG64), Q, R, 0, None), -2, b"float64 path: n_fft = 20000 does not fit in LDS"),
+    ("kpr_stft_f64", lambda: (P, _geom(**LONG64), None, R, 0, None), -1, b"2:x / window / out must not be NULL"),
+    ("kpr_istft_workspace_bytes", lambda: (_geom(), -1), -1, None),
+    ("kpr_istft_f64_workspace_bytes", lambda: (_geom(), -1), -1, None),
+    ("kpr_istft_f64_workspace_bytes", lambda: (_geom(**BAD_GEOM), 7), -1, b"bad batch/channels/time"),
+    ("kpr_istft_f64", lambda: (P, _geom(**BAD_GEOM), 7, Q, R, S, BIG, None), -1, b"bad batch/channels/time"),
+    ("kpr_istft_f64", lambda: (P, _geom(), -7, Q, R, S, BIG, None), -1, b"negative frame count"),
+    ("kpr_istft_f64", lambda: (None, _geom(), -7, Q, R, S, BIG, None), -1, b"2:negative frame count"),
+    ("kpr_istft_f64", lambda: (P, _geom(), 7, None, R, S, BIG, None), -1, b"spec / window / out must not be NULL"),
+    ("kpr_istft_f64", lambda: (P, _geom(), 7, Q, R, S, 57599, None), -4, b"istft (float64) workspace: need 57600 bytes"),
+    ("kpr_istft_f64", lambda: (P, _geom(), 7, Q, None, None, 0, None), -1, b"2:spec / window / out must not be NULL"),
+    ("kpr_istft_f64", lambda: (P, _geom(**LONG64), 7, Q, R, S, BIG, None), -2, b"float64 path: n_fft = 20000 does not fit in LDS"),
+    ("kpr_istft_f64", lambda: (P, _geom(**LONG64), 7, Q, R, S, 8, None), -4, b"2:istft (float64) workspace: need"),
+    # ---- Frame / Energy / Delta and their backward passes
+    ("kpr_frame_f32", lambda: (P, -1, 1, 1000, 0, 50, 25, 0, 0.0, Q, None), -1, b"bad batch/channels/layout"),
+    ("kpr_frame_f32", lambda: (P, 2, 1, 1000, 0, 50, 0, 0, 0.0, Q, None), -1, b"bad time/frame_length/hop_length"),
+    ("kpr_frame_f32", lambda: (P, 2, 1, 1000, 2, 0, 25, 0, 0.0, Q, None), -1, b"2:bad batch/channels/layout"),
+    ("kpr_frame_f32", lambda: (P, 2, 1, 1 << 32, 0, 1, 1, 0, 0.0, Q, None), -2, b"too many frames per signal"),
+    ("kpr_frame_f32", lambda: (None, 2, 1, 1000, 0, 50, 25, 0, 0.0, Q, None), -1, b"x / out must not be NULL"),
+    ("kpr_frame_f32", lambda: (None, 2, 1, -1000, 0, 50, 25, 0, 0.0, Q, None), -1, b"2:bad time/frame_length/hop_length"),
+    ("kpr_energy_f32", lambda: (P, 2, 0, 1000, 0, 50, 25, 0, 0.0, 1.0, Q, None), -1, b"bad batch/channels/layout"),
+    ("kpr_energy_f32", lambda: (P, 2, 1, 1000, 0, 0, 25, 0, 0.0, 1.0, Q, None), -1, b"bad time/frame_length/hop_length"),
+    ("kpr_energy_f32", lambda: (P, 2, 1, 1000, 0, 50, 25, 0, 0.0, 1.0, None, None), -1, b"x / out must not be NULL"),
+    ("kpr_energy_f32", lambda: (P, 2, 1, 200000, 0, 100000, 1, 0, 0.0, 1.0, Q, None), -2, b"frame_length / hop_length = 100000 is too large"),
+    ("kpr_energy_f32", lambda: (None, 2, 1, 200000, 0, 100000, 1, 0, 0.0, 1.0, Q, None), -1, b"2:x / out must not be NULL"),
+    ("kpr_delta_f32", lambda: (P, 2, 1, 50, 0, 0, 5, 1, Q, None), -1, b"bad batch/channels/frames/n_freq/layout"),
+    ("kpr_delta_f32", lambda: (P, 2, 1, 50, 13, 0, 4, 1, Q, None), -1, b"win_length must be odd and >= 3, got 4"),
+    ("kpr_delta_f32", lambda: (P, 2, 1, 50, 13, 0, 5, 3, Q, None), -1, b"bad pad mode 3"),
+    ("kpr_delta_f32", lambda: (P, 2, 1, 50, 13, 0, 1, -1, Q, None), -1, b"2:win_length must be odd and >= 3, got 1"),
+    ("kpr_delta_f32", lambda: (P, 2, 1, 50, 13, 0, 5, 1, P, None), -1, b"x / out must not be NULL or aliased"),
+    ("kpr_delta_f32", lambda: (None, 2, 1, 50, 13, 0, 5, 7, Q, None), -1, b"2:bad pad mode 7"),
+    ("kpr_frame_bwd_f32", lambda: (P, 2, 1, 1000, 3, 50, 25, 0, Q, None), -1, b"bad batch/channels/layout"),
+    ("kpr_frame_bwd_f32", lambda: (P, 2, 1, 1000, 0, 50, 25, 0, None, None), -1, b"g / gx must not be NULL"),
+    ("kpr_frame_bwd_f32", lambda: (None, 2, 1, 1000, 0, 50, -25, 0, Q, None), -1, b"2:bad time/frame_length/hop_length"),
+    ("kpr_energy_bwd_f32", lambda: (P, Q, 2, 1, 1000, 0, -50, 25, 0, 1.0, R, None), -1, b"bad time/frame_length/hop_length"),
+    ("kpr_energy_bwd_f32", lambda: (None, Q, 2, 1, 1000, 0, 50, 25, 0, 1.0, R, None), -1, b"x / g / gx must not be NULL"),
+    ("kpr_energy_bwd_f32", lambda: (None, Q, -2, 1, 1000, 0, 50, 25, 0, 1.0, R, None), -1, b"2:bad batch/channels/layout"),
+    ("kpr_delta_bwd_f32", lambda: (P, 2, 1, 50, 13, 0, 6, 1, Q, None), -1, b"win_length must be odd and >= 3, got 6"),
+    ("kpr_delta_bwd_f32", lambda: (P, 2, 1, 50, 13, 0, 5, 1, P, None), -1, b"g / gx must not be NULL or aliased"),
+    ("kpr_delta_bwd_f32", lambda: (P, 2, 1, 50, 13, 2, 5, 1, P, None), -1, b"2:bad batch/channels/frames/n_freq/layout"),
+    # ---- SpecAugment / index draw / ChannelSwap
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 0, 64, 10, 10, Q, None), -1, b"bad n_items/n_time/n_freq"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 33, 2, 100, 64, 10, 10, Q, None), -1, b"mask counts (33, 2) outside [0, 32] per axis"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 65536, 65536, 10, 10, Q, None), -2, b"n_time * n_freq = 4294967296 elements per item"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 100, 64, 101, 10, Q, None), -1, b"time_mask_param 101 outside [1, n_time = 100]"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 100, 64, 10, 0, Q, None), -1, b"freq_mask_param 0 outside [1, n_freq = 64]"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 100, 64, 0, 0, Q, None), -1, b"2:time_mask_param 0 outside"),
+    ("kpr_spec_augment_draw", lambda: (P, 1 << 20, 1, 1, 100, 64, 10, 10, Q, None), -2, b"mask table of 2097152 entries"),
+    ("kpr_spec_augment_draw", lambda: (P, 4, 2, 2, 100, 64, 10, 10, None, None), -1, b"state must not be NULL"),
+    ("kpr_spec_augment_draw", lambda: (None, 4, 2, 2, 100, 64, 10, 10, Q, None), -1, b"table must not be NULL"),
+    ("kpr_spec_augment_draw", lambda: (None, 4, 2, 2, 100, 64, 10, 10, None, None), -1, b"2:state must not be NULL"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, Q, R, -1, 2, 2, 100, 64, 0.0, None), -1, b"bad n_items/n_time/n_freq"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, None, R, 4, 2, 2, 100, 64, 0.0, None), -1, b"x / out must not be NULL"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, Q, None, 4, 2, 2, 100, 64, 0.0, None), -1, b"table must not be NULL"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, Q, R, 4, 2, 2, 1, 65537, 0.0, None), -2, b"n_freq = 65537: the copy form holds at most 65536 bins per row"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, P + 4, R, 1, 2, 2, 4, 4, 0.0, None), -1, b"x and out overlap"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, Q, None, 4, 2, 2, 1, 65537, 0.0, None), -1, b"2:table must not be NULL"),
+    ("kpr_spec_augment_apply_f32", lambda: (P, P + 4, R, 1, 2, 2, 1, 65537, 0.0, None), -2, b"2:n_freq = 65537"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 0, 100, 4, PERM_OK_PTR, None), -1, b"bad outer/n_ch/inner"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 2, 100, 2, PERM_OK_PTR, None), -1, b"elem_bytes must be 4 (float32) or 8 (complex64), got 2"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 65, 100, 4, PERM_OK_PTR, None), -2, b"65 channels: the permutation travels in the kernel arguments, at most 64"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 2, 100, 4, None, None), -1, b"perm must not be NULL"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 2, 100, 4, PERM_BAD_PTR, None), -1, b"perm[1] = 5 outside [0, 2)"),
+    ("kpr_channel_gather", lambda: (P, P, 3, 2, 100, 4, PERM_OK_PTR, None), -1, b"x / out must not be NULL or aliased"),
+    ("kpr_channel_gather", lambda: (P, Q, 3, 2, 100, 16, None, None), -1, b"2:elem_bytes must be"),
+    ("kpr_channel_gather", lambda: (None, Q, 3, 2, 100, 4, PERM_BAD_PTR, None), -1, b"2:perm[1] = 5 outside"),
+    ("kpr_index_draw", lambda: (P, 4, 0, None, None), -1, b"2:bad n_items / n_choices (4, 0)"),
+    ("kpr_index_draw", lambda: (None, 4, 3, None, None), -1, b"2:state must not be NULL"),
+    # ---- host-only table builders
+    ("kpr_resample_table", lambda: (2, 1, 6, 0.99, 0, None, P), -1, b"table_host / first_host must not be NULL"),
+    ("kpr_resample_table", lambda: (0, 1, 6, 0.99, 0, P, Q), -1, b"orig_freq and new_freq must be positive, got 0 and 1"),
+    ("kpr_resample_table", lambda: (2, 1, 6, 1.5, 0, P, Q), -1, b"rolloff must lie in (0, 1], got 1.5"),
+    ("kpr_resample_table", lambda: (0, 1, 6, 0.99, 0, P, None), -1, b"2:table_host / first_host must not be NULL"),
+    ("kpr_lfilter_carry", lambda: (COEF_OK, 16, None), -1, b"M is NULL"),
+    ("kpr_lfilter_carry", lambda: (None, 16, _f64(0, 0, 0, 0)), -1, b"coef is NULL"),
+    ("kpr_lfilter_carry", lambda: (COEF_OK, -1, _f64(0, 0, 0, 0)), -1, b"chunk length -1 outside [0, 2^20]"),
+    ("kpr_lfilter_carry", lambda: (None, 16, None), -1, b"2:M is NULL"),
+    ("kpr_lfilter_carry", lambda: (COEF_UNSTABLE, -1, _f64(0, 0, 0, 0)), -1, b"2:lie outside the stability triangle"),
+]
+
+
+def test_refusals_return_code_and_message():
+    """Every row returns before any HIP call (no GPU needed, nothing is launched): bad geometry, bad enums, non-positive sizes, bad
+    decibel parameters, NULL pointers of a non-empty problem, aliased buffers, small workspaces, the augmentation caps."""
+    L = _ffi.lib()
+    for i, (name, args, rc, text) in enumerate(REFUSALS):
+        got = getattr(L, name)(*args())
+        assert got == rc, (i, name, got, L.kpr_last_error())
+        if text is not None:
+            frag = text[2:] if text.startswith(b"2:") else text
+            assert frag in L.kpr_last_error(), (i, name, L.kpr_last_error())
+    for name in {name for name, _, _, _ in REFUSALS if name.endswith(("_f32", "_f64")) or name in ("kpr_channel_gather", "kpr_spec_augment_draw")}:
+        assert any(n == name and t and t.startswith(b"2:") for n, _, _, t in REFUSALS), name
+
+
+def test_workspace_sizes_of_the_host_only_entry_points():
+    L = _ffi.lib()
+    assert L.kpr_db_workspace_bytes(0) == 264 and L.kpr_db_workspace_bytes(3) == 280
+    g = _ffi.StftGeom(2, 3, 0, 512, 400, 128, 0, 0, 0, 0)
+    assert L.kpr_istft_workspace_bytes(ctypes.byref(g), 7) == 256 + 4 * 2 * 3 * 7 * 400
+    assert L.kpr_istft_f64_workspace_bytes(ctypes.byref(g), 7) == 256 + 8 * 2 * 3 * 7 * 400
+    assert L.kpr_istft_workspace_bytes(ctypes.byref(g), 0) == L.kpr_istft_f64_workspace_bytes(ctypes.byref(g), 0) == 256
+    # the statistics region: 256 + 8 bytes x 32 slots per item up to 8192 items (one slot beyond), rounded to 256
+    fused, staged = _ffi.StftGeom(2, 1, 4000, 512, 512, 128, 0, 0, 0, 0), _ffi.StftGeom(2, 1, 4000, 400, 400, 100, 0, 0, 0, 0)
+    assert L.kpr_mel_workspace_bytes(ctypes.byref(fused), 40, None) == 768
+    assert L.kpr_mel_workspace_bytes(ctypes.byref(fused), 257, None) == L.kpr_mel_workspace_bytes_unpacked(ctypes.byref(fused), 40) == 768 + 8 * 2 * 28 * 257
+    assert L.kpr_mel_workspace_bytes(ctypes.byref(staged), 40, None) == L.kpr_mel_workspace_bytes_unpacked(ctypes.byref(staged), 40) == 768 + 8 * 2 * 37 * 201
+    many = _ffi.StftGeom(8193, 1, 100, 512, 512, 128, 0, 0, 0, 0)
+    assert L.kpr_mel_workspace_bytes(ctypes.byref(many), 40, None) == 66048
+    # the forward transform needs a workspace on the DFT-as-GEMM path with a real-valued output only (n_fft 2049 = 3 x 683)
+    gemm = _ffi.StftGeom(1, 1, 5000, 2049, 2049, 512, 0, 0, 0, 0)
+    assert L.kpr_stft_workspace_bytes(ctypes.byref(gemm), _ffi.OUT_COMPLEX) == 0
+    assert L.kpr_stft_workspace_bytes(ctypes.byref(gemm), _ffi.OUT_MAGNITUDE) == 8 * 6 * 1025
+    assert L.kpr_stft_workspace_bytes(ctypes.byref(fused), _ffi.OUT_PHASE) == 0
+    # win_length > n_fft: the frame count keeps the caller's win_length (frames are cropped after they are cut)
+    assert L.kpr_stft_workspace_bytes(ctypes.byref(_ffi.StftGeom(1, 1, 5000, 2049, 3000, 512, 0, 0, 0, 0)), _ffi.OUT_MAGNITUDE) == 8 * 4 * 1025

@@ -32,8 +32,9 @@ def one(pattern, text):
 
 # ---- 1. constants ------------------------------------------------------------------------------------------------
 def test_constants_are_the_ones_in_the_source():
-    mel, host, misc, hip, ops, gen, common = (source(n) for n in ('kpr_host_mel.h', 'kpr_host.h', 'kpr_misc_kernels.h', 'kapre_hip.hip',
-                                                                  'kpr_host_ops.h', 'kpr_generic_kernels.h', 'kpr_common.h'))
+    mel, host, misc, ops, gen, common = (source(n) for n in ('kpr_host_mel.h', 'kpr_host.h', 'kpr_misc_kernels.h',
+                                                             'kpr_host_ops.h', 'kpr_generic_kernels.h', 'kpr_common.h'))
+    hip = ops + mel                                      # the decibel bodies (kpr_host_ops.h), the statistics-init helper
     want, cap, per = one(r'const long long want = \((\d+) \+ n_items - 1\) / std::max<long long>\(1, n_items\);\s*'
                          r'return \(int\)std::max<long long>\(1, std::min<long long>\(std::min<long long>\((\d+), want\), item_size / (\d+)\)\);', mel)
     assert (int(want), int(cap), int(per)) == (m.DB_TARGET_BLOCKS, m.DB_MAX_CHUNKS, m.DB_MIN_CHUNK)

@@ -35,7 +35,8 @@ def product(expr):
 
 # ---- 1. constants ------------------------------------------------------------------------------------------------
 def test_constants_are_the_ones_in_the_source():
-    kern, hip, mel = source('kpr_signal_kernels.h'), source('kapre_hip.hip'), source('kpr_host_mel.h')
+    kern, mel = source('kpr_signal_kernels.h'), source('kpr_host_mel.h')
+    hip = source('kpr_host_ops.h') + mel                 # the Frame / Energy / Delta bodies, the thin-GEMM launch
     assert int(one(r'constexpr int kEnFrames = (\d+);', kern)) == m.EN_FRAMES
     assert product(one(r'i0 < n4; i0 \+= (\d+ \* \d+)\)', kern)) == m.EN_UNROLL
     unroll = int(one(r'f32x4 v\[(\d+)\];', kern))
@@ -70,7 +71,7 @@ def test_thin_gemm_cases_above_64_kib_agree_with_the_dispatch():
     assert {(c['K'], c['N']) for c in big} >= {(272, 64), (512, 33), (512, 64)}
     assert m.thin_plan(m.tcase(256, 64, 64))['lds'] == m.LDS_PLAIN
     assert m.thin_plan(m.tcase(512, 64, 64))['lds'] == 128 * 1024 <= 160 * 1024
-    opts_in = thin_launch_opts_in(source('kapre_hip.hip'))
+    opts_in = thin_launch_opts_in(source('kpr_host_mel.h'))
     assert opts_in == m.THIN_BIG_LDS_OPT_IN
     for c in big:
         assert opts_in, '%s: %d bytes of dynamic LDS and no opt-in at the launch' % (c['id'], m.thin_plan(c)['lds'])
