@@ -155,6 +155,11 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *   "lfilter_variant" 0 = automatic (default: kpr_lfilter_f32 walks every series with one workgroup, or cuts the time axis into
  *                  segments when batch * channels is too small to fill the device) | 1 = whole-signal for every shape | 2 = segmented
  *                  for every shape (A/B runs, tests; results within the error bound of each other, not bit-identical)
+ *   "addnoise_variant" 0 = automatic (default: in a batch of at least 256 items kpr_add_noise_f32 / kpr_add_noise_bwd_f32 keep an
+ *                  item of at most kpr_add_noise_plan's resident limit in the registers of one workgroup, one launch, and stream
+ *                  longer items and smaller batches in two) | 1 = streamed for
+ *                  every shape | 2 = resident wherever it applies (A/B runs, tests; results within the error bound of each other,
+ *                  not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -751,6 +756,51 @@ int kpr_lfilter_f32(const float* x, int64_t batch, int channels, int64_t len, in
 int kpr_spec_fir_plan(int64_t frames_out, int64_t inner, int n_part, int* out /* 3 */);
 int kpr_spec_fir_c64(const void* x, int64_t outer, int64_t frames_in, int64_t inner, int band_div, const void* h, int n_ir, int n_part,
                      const int32_t* idx /* may be NULL */, int64_t items, void* out, int64_t frames_out, kpr_stream_t stream);
+
+/* ---- AddNoise: noise mixed into a waveform at a per-item signal-to-noise ratio, kapre_amd.augmentation.AddNoise ------------
+ * x: float32 waveform, (batch, time, ch) [layout = LAST] or (batch, ch, time) [FIRST], contiguous; out: the same shape.
+ * noise: float32 DEVICE bank (n_noise, stride), row k holding lengths[k] samples (DEVICE int32, 1 <= lengths[k] <= stride).
+ * table: DEVICE int32 (batch, 4), the row of item b = (index, offset, snr in dB as float32 bits, 0).  The kernels clamp index into
+ * [0, n_noise), the length into [1, stride] and offset into [0, length): they never read outside the bank, whatever the table
+ * holds, and nothing is read on the host.  With k = index, o = offset, L = lengths[k], C = channels, T = time:
+ *   seg[t]  = noise[k][(o + t) mod L]                                   the noise tiles circularly
+ *   Sx      = sum_{c,t} x[b,c,t]^2,   Sn = sum_t seg[t]^2               float64 sums of the exact float32 products
+ *   g       = sqrt((Sx / (C T)) / (Sn / T)) 10^(-snr / 20)              float64, rounded once to float32; +0 if Sx == 0 or Sn == 0
+ *   out[b,c,t] = fmaf(g, seg[t], x[b,c,t])                              the channels of an item share its noise and its gain
+ * so snr is the ratio of the item's mean signal power to the mean power of the noise that is added.  stats: DEVICE float64
+ * (batch, 4), written: (Sx, Sn, g, 0) per item.  A NaN / Inf sample makes its own item non-finite and touches no other.
+ * kpr_add_noise_bwd_f32, the exact input gradient (noise and snr are constants, the gain is not):
+ *   D = sum_{c,t} gy[b,c,t] seg[t] (float64),  coef = (D g) / Sx rounded once to float32 (0 if Sx == 0),
+ *   gx[b,c,t] = fmaf(coef, x[b,c,t], gy[b,c,t])
+ * with (Sx, g) read from `stats`, the rows the forward call wrote; stats_out (may be NULL, may be `stats`): (Sx, Sn, g, D).
+ * Two forms (option "addnoise_variant"): resident -- an item of at most kpr_add_noise_plan's limit of floats stays in the
+ * registers of one workgroup, one launch, one read -- and streamed -- two launches, partial sums of chunks of the item in
+ * `workspace`, added in ascending chunk order.  No atomics: each form gives the same bits from the same inputs; the two sum in
+ * different orders and agree within the error bound, not bit for bit.  workspace: kpr_add_noise_workspace_bytes(...) bytes, 8-byte
+ * aligned, clear of everything else (KPR_E_WORKSPACE when the streamed form finds it NULL or short; the resident form does not
+ * read it).  16-byte accesses behind 16-byte aligned x / out (gy / x / gx); any 4-byte aligned base is taken.
+ * Errors: NULL pointers, n_noise < 1, stride < 1, time < 1, channels < 1, out overlapping x (there is no in-place form) or any
+ * other argument: KPR_E_BADARG; time * channels >= 2^30: KPR_E_UNSUPPORTED.  batch == 0: returns 0, launches nothing.  No host
+ * reads, nothing copied per call: capturable.
+ * kpr_add_noise_plan (host only): out[0 ... 3] = floats per chunk of the streamed form, chunks per item, the resident limit in
+ * floats per item, and the form (1 streamed, 2 resident) the dispatch uses for this shape under the current option; seams for tests.
+ * kpr_noise_draw: the table of a training step, drawn on the device.  The same 16-byte state, generator and rules as
+ * kpr_index_draw: Philox4x32-10, counter (item, 0, calls_lo, calls_hi), key (seed_lo, seed_hi) -> r0, r1, r2;
+ *   index = mulhi32(r0, n_noise), offset = mulhi32(r1, lengths[index]),
+ *   snr = (float)fma(snr_hi - snr_lo, r2 * 2^-32, snr_lo): the difference rounded to float64, ONE float64 fma, one rounding to
+ *   float32 -- uniform in [snr_lo, snr_hi], and snr_lo itself when the two are equal;
+ * calls advances by one (also for n_items == 0).  table 16-byte aligned.  n_noise < 1, n_items < 0, snr_lo > snr_hi or either not
+ * finite, NULL state / lengths / table: KPR_E_BADARG; more than 2^20 items: KPR_E_UNSUPPORTED.  One launch, one workgroup. */
+int kpr_noise_draw(int32_t* table, int64_t n_items, int n_noise, const int32_t* lengths, double snr_lo, double snr_hi, void* state,
+                   kpr_stream_t stream);
+int kpr_add_noise_plan(int64_t batch, int channels, int64_t time, int layout, int* out /* 4 */);
+int64_t kpr_add_noise_workspace_bytes(int64_t batch, int channels, int64_t time, int layout);
+int kpr_add_noise_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, const float* noise, int n_noise,
+                      int64_t stride, const int32_t* lengths, const int32_t* table, float* out, double* stats, void* workspace,
+                      size_t workspace_bytes, kpr_stream_t stream);
+int kpr_add_noise_bwd_f32(const float* gy, const float* x, int64_t batch, int channels, int64_t time, int layout, const float* noise,
+                          int n_noise, int64_t stride, const int32_t* lengths, const int32_t* table, const double* stats, float* gx,
+                          double* stats_out, void* workspace, size_t workspace_bytes, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

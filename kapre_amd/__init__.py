@@ -32,7 +32,7 @@ from . import signal
 from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve
 
 from . import augmentation
-from .augmentation import SpecAugment, ChannelSwap, Reverb
+from .augmentation import SpecAugment, ChannelSwap, Reverb, AddNoise
 
 from .composed import (
     get_stft_magnitude_layer,
@@ -111,6 +111,7 @@ __all__ = [
     'SpecAugment',
     'ChannelSwap',
     'Reverb',
+    'AddNoise',
     'get_stft_magnitude_layer',
     'get_melspectrogram_layer',
     'get_log_frequency_spectrogram_layer',

@@ -226,6 +226,18 @@ EXPORTS = {
                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "kpr_index_draw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # AddNoise (kapre_amd/augmentation.py)
+    "kpr_noise_draw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_add_noise_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "kpr_add_noise_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "kpr_add_noise_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kpr_add_noise_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1052,3 +1064,65 @@ def spec_fir(x, fmt, h, idx, frames_out: int):
     _call("kpr_spec_fir_c64", x.device, ptr(x), outer, t, inner, band_div, ptr(h), int(h.shape[0]), int(h.shape[1]), ptr(idx), b,
           ptr(out), int(frames_out))
     return out
+
+
+# AddNoise (kapre_amd/augmentation.py, backend.add_noise)
+ADDNOISE_STREAMED, ADDNOISE_RESIDENT = 1, 2
+
+
+def noise_draw(state, n_items: int, lengths, snr_lo: float, snr_hi: float):
+    """The int32 (n_items, 4) device table of an AddNoise step -- (index, offset, snr as float32 bits, 0) per item -- drawn on
+    the device from ``state`` (int64[2] there: seed, calls; calls advances by one): index uniform over the ``lengths`` (int32
+    device vector, one entry per noise), offset uniform below the length of that noise, snr uniform in [snr_lo, snr_hi]."""
+    import torch
+    table = torch.empty((int(n_items), 4), dtype=torch.int32, device=state.device)
+    _call("kpr_noise_draw", state.device, ptr(table), int(n_items), int(lengths.shape[0]), ptr(lengths), float(snr_lo),
+          float(snr_hi), ptr(state))
+    return table
+
+
+def add_noise_plan(batch: int, channels: int, time: int, fmt):
+    """(chunk_floats, chunks_per_item, resident_limit_floats, form) of kpr_add_noise_f32's dispatch for this shape under the
+    current ``addnoise_variant``; form is ADDNOISE_STREAMED or ADDNOISE_RESIDENT (host only)."""
+    out = (ctypes.c_int * 4)()
+    check(lib().kpr_add_noise_plan(int(batch), int(channels), int(time), fmt if isinstance(fmt, int) else layout(fmt), out),
+          "kpr_add_noise_plan")
+    return tuple(int(v) for v in out)
+
+
+def add_noise_workspace_bytes(batch: int, channels: int, time: int, fmt) -> int:
+    """Bytes of workspace the streamed form of kpr_add_noise_f32 / kpr_add_noise_bwd_f32 needs for this shape (host only)."""
+    n = int(lib().kpr_add_noise_workspace_bytes(int(batch), int(channels), int(time), fmt if isinstance(fmt, int) else layout(fmt)))
+    if n < 0:
+        check(-1, "kpr_add_noise_workspace_bytes")
+    return n
+
+
+def add_noise(x, fmt, bank, lengths, table):
+    """(y, stats): the float32 waveform ``x`` plus, per batch item, the noise ``bank[index]`` read circularly from ``offset`` and
+    scaled to the item's ``snr`` -- ``table`` is the int32 (batch, 4) device table of (index, offset, snr bits, 0), ``bank`` the
+    float32 (n_noise, stride) device bank, ``lengths`` its int32 lengths.  stats: float64 (batch, 4) rows (Sx, Sn, g, 0)."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    out = torch.empty_like(x)
+    stats = torch.empty((b, 4), dtype=torch.float64, device=x.device)
+    ws_bytes = add_noise_workspace_bytes(b, c, t, fmt)
+    ws = workspace(ws_bytes, x.device)
+    _call("kpr_add_noise_f32", x.device, ptr(x), b, c, t, layout(fmt), ptr(bank), int(bank.shape[0]), int(bank.shape[1]),
+          ptr(lengths), ptr(table), ptr(out), ptr(stats), ptr(ws), ws_bytes)
+    return out, stats
+
+
+def add_noise_bwd(gy, x, fmt, bank, lengths, table, stats):
+    """(gx, stats_out): the cotangent of ``x`` from the cotangent ``gy`` of ``add_noise(x, ...)[0]`` and the ``stats`` that call
+    returned; stats_out: float64 (batch, 4) rows (Sx, Sn, g, D)."""
+    import torch
+    gy = gy.contiguous().to(torch.float32)
+    b, c, t = dims_of(x.shape, fmt)
+    gx = torch.empty_like(x)
+    stats_out = torch.empty((b, 4), dtype=torch.float64, device=x.device)
+    ws_bytes = add_noise_workspace_bytes(b, c, t, fmt)
+    ws = workspace(ws_bytes, x.device)
+    _call("kpr_add_noise_bwd_f32", x.device, ptr(gy), ptr(x), b, c, t, layout(fmt), ptr(bank), int(bank.shape[0]),
+          int(bank.shape[1]), ptr(lengths), ptr(table), ptr(stats), ptr(gx), ptr(stats_out), ptr(ws), ws_bytes)
+    return gx, stats_out

@@ -9,6 +9,9 @@ makes runs repeatable; the layer's config carries no seed, as upstream.
 
 ``Reverb`` has no counterpart in the reference: room-impulse-response augmentation of the waveform, one impulse response per
 batch item drawn from the same device generator (``kpr_index_draw``), applied by ``backend.fftconvolve``'s three launches.
+
+``AddNoise`` has none either: additive noise at a random signal-to-noise ratio (MUSAN-style), the noise, its starting point and
+the ratio of every batch item drawn from that generator (``kpr_noise_draw``), mixed by ``kpr_add_noise_f32``.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ from . import _ffi, autograd, backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 from .keras_shim import Layer, register_keras_serializable
 
-__all__ = ['SpecAugment', 'ChannelSwap', 'Reverb', 'set_seed']
+__all__ = ['SpecAugment', 'ChannelSwap', 'Reverb', 'AddNoise', 'set_seed']
 
 _seed = None          # what set_seed gave; None: OS entropy at the first use of a device
 _states = {}          # device index -> int64[2] on that device: (seed, calls) as kpr_spec_augment_draw reads them
@@ -257,5 +260,64 @@ class Reverb(Layer):
     def get_config(self):
         config = super(Reverb, self).get_config()
         config.update({'irs': self.irs, 'normalize': self.normalize,
+                       'input_data_format': _config_format(self.input_data_format)})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class AddNoise(Layer):
+    """Additive-noise augmentation of a waveform batch: in training every batch item gets one of the mono ``noises`` (what
+    ``backend.noise_bank`` takes: (L,), (n, L) or a list of 1-D arrays of different lengths), read circularly from a random
+    offset and scaled so that the ratio of the item's mean power to the mean power of the added noise is a signal-to-noise ratio
+    drawn uniformly from ``snr_db = (low, high)`` in dB; a scalar ``snr_db`` fixes it.  The channels of an item share its noise
+    and its gain; a silent item, or a silent stretch of noise, leaves the item as it is.  Everything is drawn on the device by
+    ``kpr_noise_draw`` from the generator that ``SpecAugment`` and ``Reverb`` use (``set_seed`` makes a run repeatable bit for
+    bit; a captured graph draws anew at every replay, nothing is copied from the host per call).  With ``training`` in
+    ``(None, False)`` the layer returns its input OBJECT and launches nothing.  float32; differentiable with respect to the
+    waveform (exactly: the gain depends on it).  After a training call ``last_draw`` is the device int32 (batch, 4) table of
+    (index, offset, snr as float32 bits, 0) and ``last_stats`` the device float64 (batch, 4) rows (signal energy, noise
+    energy, gain, 0)."""
+
+    def __init__(self, noises, snr_db=(5.0, 20.0), input_data_format='default', **kwargs):
+        super(AddNoise, self).__init__(**kwargs)
+        self.input_data_format = _resolve_format(input_data_format)
+        self._plan = backend.NoisePlan(noises)
+        self.noises = [self._plan.bank[k, :n].astype(np.float64).tolist() for k, n in enumerate(self._plan.lengths)]
+        if np.ndim(snr_db) == 0:
+            lo = hi = float(snr_db)
+            self.snr_db = lo
+        else:
+            if len(snr_db) != 2:
+                raise ValueError('AddNoise: snr_db must be a number or (low, high), got %r' % (snr_db,))
+            lo, hi = float(snr_db[0]), float(snr_db[1])
+            self.snr_db = [lo, hi]
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError('AddNoise: snr_db must be finite with low <= high, got %r' % (snr_db,))
+        self._snr = (lo, hi)
+        self.last_draw = None
+        self.last_stats = None
+
+    def compute_output_shape(self, input_shape):
+        """the input's shape"""
+        return tuple(input_shape)
+
+    def call(self, x, training=None):
+        if training in (None, False):
+            return x
+        if len(x.shape) != 3:
+            raise ValueError('AddNoise expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+        if _ffi.is_f64(x):
+            raise TypeError('AddNoise has float32 kernels only; got a float64 input (cast it to float32)')
+        import torch
+
+        x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+        _, lengths = self._plan.device(x.device)
+        self.last_draw = _ffi.noise_draw(device_state(x.device), x.shape[0], lengths, *self._snr)
+        y, self.last_stats = backend._add_noise_run(x, self._plan, self.last_draw, self.input_data_format)
+        return y
+
+    def get_config(self):
+        config = super(AddNoise, self).get_config()
+        config.update({'noises': self.noises, 'snr_db': self.snr_db,
                        'input_data_format': _config_format(self.input_data_format)})
         return config

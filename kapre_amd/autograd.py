@@ -15,7 +15,9 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   ``CMVN`` keeps its output and ``rstd`` per column and runs one backward kernel, two sums along time and a sweep;
   ``Resample^T`` is the forward's polyphase kernel with the adjoint table; ``LFilter^T`` is its sections in reverse order,
   each the forward kernel scanning in the other direction; ``Convolve^T`` is the forward's three launches with the filter
-  table of the time-reversed impulse responses (which are constants: no gradient reaches them);
+  table of the time-reversed impulse responses (which are constants: no gradient reaches them); ``AddNoise`` is not linear
+  (its gain follows the item's energy): backward is its two kernels in their other modes, a dot product with the wrapped
+  noise and ``gy + coef x``, from the saved input, draw table and stats rows;
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -433,7 +435,27 @@ def _functions():
             back = backend._convolve_full(g, ctx.data_format, ctx.plan, ctx.idx, adjoint=True)
             return back.narrow(ctx.t_axis, ctx.plan.ir_len - 1, ctx.t_in).contiguous(), None, None, None, None, None
 
-    _FN = dict(convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
+    class AddNoiseFn(torch.autograd.Function):
+        """y = x + g(x) seg with the gain g proportional to ||x||: backward is exact, gx = gy + (<gy, seg> g / Sx) x -- the
+        forward's two kernels in their other modes (the dot product with the wrapped noise; the stream with x as its plain
+        second operand).  Saves x, the draw table and the stats rows, nothing else; noise and snr are constants."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, bank, lengths, table):
+            ctx.data_format, ctx.bank, ctx.lengths = data_format, bank, lengths
+            x = x.detach()
+            y, stats = _ffi.add_noise(x, data_format, bank, lengths, table)
+            ctx.save_for_backward(x, table, stats)
+            ctx.mark_non_differentiable(stats)
+            return y, stats
+
+        @staticmethod
+        def backward(ctx, g, _gstats):
+            x, table, stats = ctx.saved_tensors
+            gx, _ = _ffi.add_noise_bwd(g, x, ctx.data_format, ctx.bank, ctx.lengths, table, stats)
+            return gx, None, None, None, None
+
+    _FN = dict(add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
                mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn)
     return _FN
@@ -516,3 +538,8 @@ def lfilter(x, data_format, plan):
 
 def convolve(x, data_format, plan, idx, first, n_out):
     return _functions()['convolve'].apply(x, data_format, plan, idx, first, n_out)
+
+
+def add_noise(x, data_format, bank, lengths, table):
+    """(y, stats) of _ffi.add_noise with y on the tape"""
+    return _functions()['add_noise'].apply(x, data_format, bank, lengths, table)

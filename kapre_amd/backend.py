@@ -903,6 +903,145 @@ def fftconvolve(x, ir, mode='full', index=None, data_format='default', block_siz
 
 
 # --------------------------------------------------------------------------------------
+# additive noise at a signal-to-noise ratio
+# --------------------------------------------------------------------------------------
+def noise_bank(noises):
+    """``(bank, lengths)`` of a set of mono noise signals: float32 (n_noise, Lmax), every row zero-padded behind its own
+    samples, and int32 (n_noise,).  ``noises``: array-like (L,), (n, L), or a list of 1-D arrays of different lengths.
+    ``ValueError`` for an empty set, an empty noise, anything that is not 1-D per noise, and non-finite samples."""
+    if hasattr(noises, 'detach'):
+        noises = noises.detach().cpu().numpy()
+    rows = None
+    if not isinstance(noises, np.ndarray):
+        try:
+            seq = list(noises)
+        except TypeError:
+            raise ValueError('noise_bank: noises must be array-like, got %r' % (noises,))
+        if seq and all(np.ndim(r) == 1 for r in seq):            # a list of signals, each of its own length
+            rows = [r.detach().cpu().numpy() if hasattr(r, 'detach') else r for r in seq]
+    if rows is None:
+        try:
+            arr = np.asarray(noises, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('noise_bank: noises must be (L,), (n, L) or a list of 1-D arrays')
+        if arr.ndim == 1:
+            arr = arr[None, :]
+        if arr.ndim != 2:
+            raise ValueError('noise_bank: noises must be (L,), (n, L) or a list of 1-D arrays, got shape %s' % (arr.shape,))
+        rows = list(arr)
+    try:
+        rows = [np.asarray(r, dtype=np.float64) for r in rows]
+    except (TypeError, ValueError):
+        raise ValueError('noise_bank: every noise must be a 1-D array of numbers')
+    if not rows or any(r.ndim != 1 or r.size < 1 for r in rows):
+        raise ValueError('noise_bank: at least one noise, and at least one sample in every noise, are required')
+    if not all(np.all(np.isfinite(r)) for r in rows):
+        raise ValueError('noise_bank: every noise sample must be finite')
+    lengths = np.array([r.size for r in rows], dtype=np.int32)
+    bank = np.zeros((len(rows), int(lengths.max())), dtype=np.float32)
+    for k, r in enumerate(rows):
+        bank[k, :r.size] = r.astype(np.float32)
+    return bank, lengths
+
+
+class NoisePlan:
+    """The host copy of a noise bank and its device copies, made on first use per device and kept."""
+
+    def __init__(self, noises):
+        self.bank, self.lengths = noise_bank(noises)
+        self.n_noise = int(self.bank.shape[0])
+        self._dev = {}
+
+    def device(self, device):
+        import torch
+
+        t = self._dev.get(str(device))
+        if t is None:
+            t = self._dev[str(device)] = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.lengths).to(device))
+        return t
+
+
+def _noise_column(v, batch, device, what, dtype, np_dtype):
+    """One table column: a scalar, a host sequence of ``batch`` values, or a device tensor (batch,) of ``dtype``."""
+    import torch
+
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        if v.dtype != dtype or tuple(v.shape) != (batch,):
+            raise ValueError('add_noise: a device %s must be a %s tensor of shape (%d,), got %s %s'
+                             % (what, dtype, batch, v.dtype, tuple(v.shape)))
+        return v
+    a = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+    if a.ndim == 0:
+        a = np.full((batch,), a)
+    if a.shape != (batch,) or a.dtype.kind not in ('iu' if np_dtype == np.int32 else 'iuf'):
+        raise ValueError('add_noise: %s must be a scalar or hold one value per batch item (%d), got shape %s, dtype %s'
+                         % (what, batch, a.shape, a.dtype))
+    return a.astype(np_dtype)
+
+
+def noise_table(batch, device, lengths_host, snr_db, index=None, offset=None):
+    """The int32 (batch, 4) device table ``kpr_add_noise_f32`` reads -- (index, offset, snr as float32 bits, 0) per item -- from
+    scalars, host sequences or device tensors (int32 index / offset, float32 snr).  Host values are validated (``ValueError``:
+    an index outside the bank, an offset outside its noise, a non-finite snr); device values are clamped by the kernel."""
+    import torch
+
+    idx = _noise_column(0 if index is None else index, batch, device, 'index', torch.int32, np.int32)
+    off = _noise_column(0 if offset is None else offset, batch, device, 'offset', torch.int32, np.int32)
+    snr = _noise_column(snr_db, batch, device, 'snr_db', torch.float32, np.float32)
+    n_noise = len(lengths_host)
+    if isinstance(idx, np.ndarray) and idx.size and (idx.min() < 0 or idx.max() >= n_noise):
+        raise ValueError('add_noise: index values must lie in [0, %d), got %d ... %d' % (n_noise, idx.min(), idx.max()))
+    if isinstance(off, np.ndarray) and off.size:
+        limit = np.asarray(lengths_host)[idx] if isinstance(idx, np.ndarray) else np.full((batch,), int(np.max(lengths_host)))
+        if off.min() < 0 or np.any(off >= limit):
+            raise ValueError('add_noise: every offset must lie in [0, length of its noise)')
+    if isinstance(snr, np.ndarray) and not np.all(np.isfinite(snr)):
+        raise ValueError('add_noise: snr_db must be finite')
+    if all(isinstance(c, np.ndarray) for c in (idx, off, snr)):
+        host = np.zeros((batch, 4), dtype=np.int32)
+        host[:, 0], host[:, 1], host[:, 2] = idx, off, snr.view(np.int32)
+        return torch.from_numpy(host).to(device)
+    cols = [torch.from_numpy(c).to(device) if isinstance(c, np.ndarray) else c for c in (idx, off, snr)]
+    return torch.stack([cols[0], cols[1], cols[2].view(torch.int32), torch.zeros_like(cols[0])], dim=1).contiguous()
+
+
+def _add_noise_run(x, plan, table, fmt):
+    """(y, stats): ``x`` (float32 device tensor, rank 3) plus the noise that ``table`` names, and the float64 (batch, 4) rows
+    (Sx, Sn, g, 0); y is differentiable when ``x`` asks for it."""
+    from . import autograd
+
+    bank, lengths = plan.device(x.device)
+    if autograd.needs_grad(x):
+        return autograd.add_noise(x, fmt, bank, lengths, table)
+    return _ffi.add_noise(x, fmt, bank, lengths, table)
+
+
+def add_noise(x, noise, snr_db, index=None, offset=None, data_format='default'):
+    """Noise added to a waveform batch at a signal-to-noise ratio on the GPU (``torchaudio.functional.add_noise`` with a noise
+    that tiles circularly).  ``x``: (b, time, ch) for ``channels_last``, (b, ch, time) for ``channels_first``, float32 in and
+    out.  ``noise``: what ``noise_bank`` takes, (L,), (n, L) or a list of 1-D arrays.  Item b gets
+    ``seg[t] = noise[index[b]][(offset[b] + t) mod L]`` scaled by one gain, so that the ratio of the item's mean power (over
+    all its channels) to the mean power of the added noise is ``snr_db[b]`` dB; its channels share the noise and the gain.  A
+    silent item or a silent segment is returned as it is.  ``snr_db``: a scalar, a host sequence or a float32 device tensor
+    (batch,); ``index`` / ``offset``: host integers, host sequences or int32 device tensors, 0 by default.  Noise and snr are
+    constants; a waveform that ``requires_grad`` gets a ``grad_fn`` whose backward is exact (the gain depends on ``x``).
+    ``TypeError`` for a float64 input, ``ValueError`` for a rank other than 3."""
+    import torch
+
+    from . import autograd
+    validate_data_format_str(data_format)
+    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    if len(x.shape) != 3:
+        raise ValueError('add_noise expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise TypeError('add_noise has float32 kernels only; got a float64 input (cast it to float32)')
+    plan = noise if isinstance(noise, NoisePlan) else NoisePlan(noise)
+    x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+    table = noise_table(int(x.shape[0]), x.device, plan.lengths, snr_db, index, offset)
+    return _add_noise_run(x, plan, table, fmt)[0]
+
+
+# --------------------------------------------------------------------------------------
 # Griffin-Lim
 # --------------------------------------------------------------------------------------
 def griffin_lim_parameters(n_iter, momentum, power):

@@ -47,9 +47,13 @@
 //   kpr_spec_fir_kernels.h    a short complex FIR along the frame axis of every bin of a complex spectrogram with a per-item filter
 //                             table: the middle launch of the partitioned FFT convolution (signal.Convolve, augmentation.Reverb);
 //                             filter values in registers, no LDS, no barrier
+//   kpr_mix_kernels.h         a circularly tiled noise signal mixed into a waveform at a per-item signal-to-noise ratio
+//                             (augmentation.AddNoise) and its input gradient: float64 energy / dot-product sums along time without
+//                             atomics, then out = a + s b; streamed (two launches, a workspace of chunk sums) or resident in the
+//                             registers of one workgroup per item (one launch)
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -100,6 +104,7 @@
 #include "kpr_hpss_kernels.h"
 #include "kpr_lfilter_kernels.h"
 #include "kpr_spec_fir_kernels.h"
+#include "kpr_mix_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -110,6 +115,7 @@
 #include "kpr_host_griffin_lim.h"
 #include "kpr_host_lfilter.h"
 #include "kpr_host_convolve.h"
+#include "kpr_host_mix.h"
 
 // ==========================================================================================
 // C ABI
@@ -168,7 +174,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -598,6 +604,33 @@ int kpr_spec_fir_c64(const void* x, int64_t outer, int64_t frames_in, int64_t in
                      const int32_t* idx, int64_t items, void* out, int64_t frames_out, kpr_stream_t stream) {
     if (int e = api_enter()) return e;
     return run_spec_fir(x, outer, frames_in, inner, band_div, h, n_ir, n_part, idx, items, out, frames_out, stream);
+}
+
+/* ---- AddNoise (kpr_mix_kernels.h, k_noise_draw of kpr_augment_kernels.h) ---------------------- */
+int kpr_noise_draw(int32_t* table, int64_t n_items, int n_noise, const int32_t* lengths, double snr_lo, double snr_hi, void* state,
+                   kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_noise_draw(table, n_items, n_noise, lengths, snr_lo, snr_hi, state, stream);
+}
+int kpr_add_noise_plan(int64_t batch, int channels, int64_t time, int layout, int* out) {
+    return mix_plan(batch, channels, time, layout, out);
+}
+int64_t kpr_add_noise_workspace_bytes(int64_t batch, int channels, int64_t time, int layout) {
+    return mix_workspace_bytes(batch, channels, time, layout);
+}
+int kpr_add_noise_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, const float* noise, int n_noise,
+                      int64_t stride, const int32_t* lengths, const int32_t* table, float* out, double* stats, void* workspace,
+                      size_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_add_noise(false, x, nullptr, batch, channels, time, layout, noise, n_noise, stride, lengths, table, nullptr, out, stats,
+                         workspace, workspace_bytes, stream);
+}
+int kpr_add_noise_bwd_f32(const float* gy, const float* x, int64_t batch, int channels, int64_t time, int layout, const float* noise,
+                          int n_noise, int64_t stride, const int32_t* lengths, const int32_t* table, const double* stats, float* gx,
+                          double* stats_out, void* workspace, size_t workspace_bytes, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_add_noise(true, gy, x, batch, channels, time, layout, noise, n_noise, stride, lengths, table, stats, gx, stats_out,
+                         workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

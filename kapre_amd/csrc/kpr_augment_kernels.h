@@ -71,6 +71,30 @@ __global__ __launch_bounds__(1024) void k_index_draw(int* __restrict__ out, int 
     if (threadIdx.x == 0) state[1] = calls + 1;
 }
 
+// One workgroup, the same state and the same generator again (augmentation.AddNoise: which noise, from where, how loud).  Entry
+// item: counter (item, 0, calls_lo, calls_hi), key (seed_lo, seed_hi) -> r0, r1, r2; the int32[4] row of the item is
+//   index  = mulhi(r0, n_noise)                       uniform in 0 .. n_noise - 1
+//   offset = mulhi(r1, lengths[index])                uniform in 0 .. L - 1 (a length below 1 counts as 1)
+//   snr    = (float)fma(snr_d, r2 2^-32, snr_lo)      as float32 bits; ONE float64 fma (r2 2^-32 is exact) rounded once to float32,
+//                                                     snr_d = the float64 difference snr_hi - snr_lo formed by the host
+//   0
+// One lane stores calls + 1 behind the barrier.
+__global__ __launch_bounds__(1024) void k_noise_draw(int* __restrict__ table, int n_items, unsigned n_noise,
+                                                     const int* __restrict__ lengths, double snr_lo, double snr_d,
+                                                     unsigned long long* state) {
+    const unsigned long long seed = state[0], calls = state[1];
+    for (int e = threadIdx.x; e < n_items; e += blockDim.x) {
+        unsigned c[4] = {(unsigned)e, 0u, (unsigned)calls, (unsigned)(calls >> 32)};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        const unsigned index = __umulhi(c[0], n_noise);
+        const unsigned offset = __umulhi(c[1], (unsigned)max(lengths[index], 1));
+        const float snr = (float)fma(snr_d, (double)c[2] * 0x1p-32, snr_lo);
+        reinterpret_cast<int4*>(table)[e] = make_int4((int)index, (int)offset, __float_as_int(snr), 0);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) state[1] = calls + 1;
+}
+
 // out = masked ? mask_value : x (tf.where, augmentation.py:264): a copy, bit for bit on the elements that pass.  x / out are n_items
 // blocks of n_time x n_freq floats (one channel: channels_first and channels_last are the same bytes).  A workgroup owns at most
 // kAugChunk consecutive floats of one item; it turns the item's intervals into two LDS bitmaps -- the rows its floats touch, the

@@ -11,13 +11,13 @@ static std::mutex g_mu;             // the caches of every family (device tables
 // Process-wide tuning switches (kpr_set_option): plain atomics, read on the launch path.  The
 // library never reads the process environment.
 enum { OPT_MEL_VARIANT, OPT_ISTFT_PATH, OPT_MIXED_RADIX, OPT_DB_CHUNKS, OPT_VERBOSE, OPT_STFT_VARIANT, OPT_DB_SLOTS, OPT_MEL_CL_STAGE, OPT_FB_VARIANT, OPT_MEL_PW_PLAIN,
-       OPT_CMVN_VARIANT, OPT_LFILTER_VARIANT, OPT_COUNT };
-static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {1}, {0}, {0}, {0}, {0}, {1}, {0}, {1}, {0}, {0}};
+       OPT_CMVN_VARIANT, OPT_LFILTER_VARIANT, OPT_ADDNOISE_VARIANT, OPT_COUNT };
+static std::atomic<int> g_opt[OPT_COUNT] = {{0}, {0}, {1}, {0}, {0}, {0}, {0}, {1}, {0}, {1}, {0}, {0}, {0}};
 static inline int opt(int id) { return g_opt[id].load(std::memory_order_relaxed); }
 
 static int option_id(const char* name) {
     static const char* const names[OPT_COUNT] = {"mel_variant", "istft_path", "mixed_radix", "db_chunks", "verbose", "stft_variant", "db_slots",
-                                                  "mel_cl_stage", "fb_variant", "mel_pw_plain", "cmvn_variant", "lfilter_variant"};
+                                                  "mel_cl_stage", "fb_variant", "mel_pw_plain", "cmvn_variant", "lfilter_variant", "addnoise_variant"};
     if (name)
         for (int i = 0; i < OPT_COUNT; ++i)
             if (std::strcmp(name, names[i]) == 0) return i;
