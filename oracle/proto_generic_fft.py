@@ -1,7 +1,10 @@
 """numpy model of the size-generic FFT engine of kapre_amd/csrc/kpr_generic_kernels.h (k_stft_gen / k_irfft_gen): the
 run-time radix plan, the Stockham pass formula with its twiddle indices, the real-FFT packing of even sizes and the
 float-reciprocal index arithmetic -- the same formulas, checked on the CPU against numpy.fft
-(tests/test_proto_generic.py).  TEST INFRASTRUCTURE (lives under oracle/): nothing in kapre_amd/ imports it."""
+(tests/test_proto_generic.py).  gen_fft here is the butterfly form with a DFT matrix in float64; the index-level emulation in the
+element type -- the register butterflies of gen_dft, the direct form gen_pass / gen_output of radix 7 and the run-time radices,
+the frame load, the output modes, k_ola -- is tests/generic_model.py, which imports gen_plan, gen_fft_len and float_div from here.
+TEST INFRASTRUCTURE (lives under oracle/): nothing in kapre_amd/ imports it."""
 import numpy as np
 
 
