@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("KAPRE_AMD_LIB") or os.path.join(_HERE, "lib", "libkap
 
 CHANNELS_FIRST, CHANNELS_LAST = 0, 1
 OUT_COMPLEX, OUT_MAGNITUDE, OUT_PHASE = 0, 1, 2
+# the KPR_E_* return codes (include/kapre_hip.h)
+E_BADARG, E_UNSUPPORTED, E_HIP, E_WORKSPACE, E_DEVICE = -1, -2, -3, -4, -5
 
 
 class StftGeom(ctypes.Structure):
@@ -278,6 +280,14 @@ def check(rc: int, what: str):
         raise RuntimeError("kapre_amd: %s failed (code %d): %s" % (what, rc, msg))
 
 
+def checked_size(n, what: str) -> int:
+    """The count an entry point of the ``*_bytes`` / ``*_count`` kind returned; a negative one is its error."""
+    n = int(n)
+    if n < 0:
+        check(E_BADARG, what)
+    return n
+
+
 def set_option(name: str, value: int) -> int:
     """kpr_set_option; returns the previous value (so tests can restore it)."""
     old = ctypes.c_int(0)
@@ -319,8 +329,15 @@ PACK_HEADER_FLOATS = 64
 FFT_DFT_GEMM, FFT_POW2, FFT_MIXED_RADIX, FFT_TWO_PASS, FFT_BLUESTEIN, FFT_SUB_FFT, FFT_GENERIC = range(7)
 
 
-def layout(data_format: str) -> int:
-    return CHANNELS_LAST if data_format == "channels_last" else CHANNELS_FIRST
+def layout(fmt) -> int:
+    """The layout enum of a data-format string; an enum is returned as it is."""
+    if isinstance(fmt, int):
+        return fmt
+    return CHANNELS_LAST if fmt == "channels_last" else CHANNELS_FIRST
+
+
+def is_channels_last(fmt) -> bool:
+    return fmt in ("channels_last", CHANNELS_LAST)
 
 
 def current_stream_ptr():
@@ -364,14 +381,54 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(0)
 
 
+class DeviceConstants:
+    """Constants (windows, filterbanks, tables) uploaded once per (key, device) and kept.  Without ``max_entries`` nothing is
+    ever dropped: a captured graph replays the addresses it recorded.  With it the oldest entry goes first."""
+
+    def __init__(self, max_entries=None):
+        self._cache = {}
+        self._lock = threading.RLock()
+        self._max_entries = max_entries
+
+    def get(self, key, device, make, on_new=None):
+        """The tensor on ``device`` of the numpy array ``make()`` returns, or the tuple of tensors of its tuple of arrays
+        (what is no array -- a tensor, a ``ResamplePlan`` -- moves itself: its ``to(device)`` is kept).  A hit is one dict
+        lookup; a miss builds and uploads under the lock, so ``make`` runs once per (key, device) however many threads ask,
+        and ``on_new(value)`` once, right after the upload."""
+        k = (key, str(device))
+        value = self._cache.get(k)
+        if value is None:
+            with self._lock:
+                value = self._cache.get(k)
+                if value is None:
+                    import torch
+
+                    def upload(a):
+                        return (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(device)
+
+                    made = make()
+                    value = tuple(upload(a) for a in made) if isinstance(made, tuple) else upload(made)
+                    if on_new is not None:
+                        on_new(value)
+                    while self._max_entries is not None and len(self._cache) >= self._max_entries:
+                        self._cache.pop(next(iter(self._cache)))
+                    self._cache[k] = value
+        return value
+
+    def clear(self):
+        with self._lock:
+            self._cache.clear()
+
+    def __len__(self):
+        return len(self._cache)
+
+
 def filterbank_pack(fb_host: np.ndarray, kranges: np.ndarray) -> np.ndarray:
     """Host copy of the filterbank in the MFMA-fragment order the fused kernel streams."""
     fb_host = np.ascontiguousarray(fb_host, dtype=np.float32)
     n_freq, n_filt = fb_host.shape
     kr = kranges.ctypes.data_as(ctypes.c_void_p) if kranges is not None else ctypes.c_void_p(0)
-    n = int(lib().kpr_filterbank_pack_floats(n_freq, n_filt, kr))
-    if n < 0:
-        check(-1, "kpr_filterbank_pack_floats")
+    n = checked_size(lib().kpr_filterbank_pack_floats(n_freq, n_filt, kr), "kpr_filterbank_pack_floats")
     out = np.zeros(n, dtype=np.float32)
     check(lib().kpr_filterbank_pack(fb_host.ctypes.data_as(ctypes.c_void_p), n_freq, n_filt, kr,
                                     out.ctypes.data_as(ctypes.c_void_p)), "kpr_filterbank_pack")
@@ -402,14 +459,14 @@ def filterbank_kranges(fb_host: np.ndarray) -> np.ndarray:
 def dims_of(shape, fmt):
     """(b, *inner, c) for channels_last, (b, c, *inner) for channels_first -> (b, c, *inner).  ``fmt`` is a data-format
     string or a layout enum."""
-    if fmt in ("channels_last", CHANNELS_LAST):
+    if is_channels_last(fmt):
         return (shape[0], shape[-1], *shape[1:-1])
     return tuple(shape)
 
 
 def shape_of(fmt, b, c, *inner):
     """The inverse of ``dims_of``."""
-    return (b, *inner, c) if fmt in ("channels_last", CHANNELS_LAST) else (b, c, *inner)
+    return (b, *inner, c) if is_channels_last(fmt) else (b, c, *inner)
 
 
 def workspace(nbytes: int, device):
@@ -427,18 +484,12 @@ def _call(name: str, device, *args):
 def mel_workspace_bytes(g_ref, n_filt: int, db_ref, packed: bool) -> int:
     """kpr_mel_f32's scratch: without a packed filterbank it takes its two-kernel path, which stages the spectrum."""
     L = lib()
-    n = int(L.kpr_mel_workspace_bytes(g_ref, n_filt, db_ref) if packed
-            else L.kpr_mel_workspace_bytes_unpacked(g_ref, n_filt))
-    if n < 0:
-        check(-1, "kpr_mel_workspace_bytes")
-    return n
+    return checked_size(L.kpr_mel_workspace_bytes(g_ref, n_filt, db_ref) if packed
+                        else L.kpr_mel_workspace_bytes_unpacked(g_ref, n_filt), "kpr_mel_workspace_bytes")
 
 
 def num_frames(geom: StftGeom) -> int:
-    n = int(lib().kpr_num_frames(ctypes.byref(geom)))
-    if n < 0:
-        check(-1, "kpr_num_frames")
-    return n
+    return checked_size(lib().kpr_num_frames(ctypes.byref(geom)), "kpr_num_frames")
 
 
 def stft(x, geom: StftGeom, n_frames: int, window, mode: int):
@@ -483,7 +534,7 @@ def edge_scale(spec, n_fft: int, fmt, s_edge: float, s_mid: float, out=None):
     if out is None:
         out = torch.empty_like(spec)
     b, c, f, k = dims_of(spec.shape, fmt)
-    inner = c if fmt in ("channels_last", CHANNELS_LAST) else 1
+    inner = c if is_channels_last(fmt) else 1
     _call("kpr_spec_edge_scale_c128" if spec.dtype == torch.complex128 else "kpr_spec_edge_scale_c64", spec.device,
           ptr(spec), spec.numel(), int(k), int(inner), int(n_fft), float(s_edge), float(s_mid), ptr(out))
     return out
@@ -572,10 +623,7 @@ def mag_to_db_bwd(x, g, ref_value: float, amin: float, dynamic_range: float):
 
 # float32-only signal operations (kapre_amd/signal.py, Delta)
 def _frame_count(t, frame_length, hop_length, pad_end) -> int:
-    n = int(lib().kpr_frame_count(t, frame_length, hop_length, int(bool(pad_end))))
-    if n < 0:
-        check(-1, "kpr_frame_count")
-    return n
+    return checked_size(lib().kpr_frame_count(t, frame_length, hop_length, int(bool(pad_end))), "kpr_frame_count")
 
 
 def frame(x, fmt, frame_length, hop_length, pad_end, pad_value):
@@ -722,7 +770,7 @@ def _time_geometry(shape, fmt):
     """(outer, frames, inner, band_div, n_bands) of a rank-4 ``shape``: the contiguous (outer, frames, inner) problem that the
     time-tiled launchers (PCEN, CMVN, TimeStretch) hand to the library; the band of inner index i is i // band_div"""
     b, c, t, m = dims_of(shape, fmt)
-    if fmt in ("channels_last", CHANNELS_LAST):
+    if is_channels_last(fmt):
         return b, t, m * c, c, m
     return b * c, t, m, 1, m
 
@@ -798,9 +846,6 @@ def cmvn_bwd(y, rstd, g, fmt, norm_vars: bool):
 
 
 # Resample (kapre_amd/signal.py)
-E_UNSUPPORTED = -2
-
-
 def resample_table_size(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint: bool):
     """(n_phases, n_taps, step) of one direction's polyphase table (host only).  ``ValueError`` naming the table's size when
     the library does not support it, ``RuntimeError`` for any other failure."""
@@ -833,32 +878,27 @@ def resample_plan(n_phases: int, n_taps: int, step: int) -> int:
 
 
 class ResamplePlan:
-    """One direction of a rate conversion on one device: the table and the offsets there, and their shape."""
+    """One direction of a rate conversion: the table and the offsets (as ``resample_table`` made them, or on one device), and
+    their shape."""
     __slots__ = ("table", "first", "n_phases", "n_taps", "step")
 
     def __init__(self, table, first, step):
         self.table, self.first, self.step = table, first, int(step)
         self.n_phases, self.n_taps = int(table.shape[0]), int(table.shape[1])
 
+    def to(self, device):
+        import torch
+        return ResamplePlan(torch.as_tensor(self.table).to(device), torch.as_tensor(self.first).to(device), self.step)
 
-_resample_plans = {}
+
+_RESAMPLE_CONSTS = DeviceConstants()
 
 
 def resample_plans(orig_freq, new_freq, lowpass_filter_width, rolloff, device):
     """(forward, adjoint) ``ResamplePlan`` of the conversion on ``device``, built and uploaded on first use and kept."""
-    import torch
-    key = (int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), str(device))
-    plans = _resample_plans.get(key)
-    if plans is None:
-        with _lock:
-            plans = _resample_plans.get(key)
-            if plans is None:
-                made = []
-                for adjoint in (False, True):
-                    table, first, step = resample_table(*key[:4], adjoint)
-                    made.append(ResamplePlan(torch.from_numpy(table).to(device), torch.from_numpy(first).to(device), step))
-                plans = _resample_plans[key] = tuple(made)
-    return plans
+    key = (int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff))
+    return _RESAMPLE_CONSTS.get(key, device, lambda: tuple(ResamplePlan(*resample_table(*key, adjoint))
+                                                           for adjoint in (False, True)))
 
 
 def resample(x, fmt, plan: ResamplePlan, out_len: int):
@@ -874,7 +914,6 @@ def resample(x, fmt, plan: ResamplePlan, out_len: int):
 
 # LFilter (kapre_amd/signal.py)
 LFILTER_WHOLE, LFILTER_SEGMENTED = 1, 2
-E_BADARG = -1
 
 
 def _coef5(coef):
@@ -889,8 +928,7 @@ def lfilter_plan(batch: int, channels: int, length: int, fmt):
     """(samples_per_lane, samples_per_wave, samples_per_step, samples_per_segment, form) of kpr_lfilter_f32's dispatch for
     this shape under the current ``lfilter_variant``; form is LFILTER_WHOLE or LFILTER_SEGMENTED (host only)."""
     out = (ctypes.c_int * 5)()
-    check(lib().kpr_lfilter_plan(int(batch), int(channels), int(length), fmt if isinstance(fmt, int) else layout(fmt), out),
-          "kpr_lfilter_plan")
+    check(lib().kpr_lfilter_plan(int(batch), int(channels), int(length), layout(fmt), out), "kpr_lfilter_plan")
     return tuple(int(v) for v in out)
 
 
@@ -911,9 +949,7 @@ def lfilter(x, fmt, coef, reverse: bool):
     import torch
     b, c, t = dims_of(x.shape, fmt)
     out = torch.empty_like(x)
-    ws_bytes = int(lib().kpr_lfilter_workspace_bytes(b, c, t, layout(fmt)))
-    if ws_bytes < 0:
-        check(-1, "kpr_lfilter_workspace_bytes")
+    ws_bytes = checked_size(lib().kpr_lfilter_workspace_bytes(b, c, t, layout(fmt)), "kpr_lfilter_workspace_bytes")
     ws = workspace(ws_bytes, x.device)
     _call("kpr_lfilter_f32", x.device, ptr(x), b, c, t, layout(fmt), _coef5(coef), int(bool(reverse)), ptr(out), ptr(ws), ws_bytes)
     return out
@@ -959,10 +995,8 @@ def gl_init(M, fmt, power: float, init_mode: int, state=None):
 
 
 def griffin_lim_workspace_bytes(geom: StftGeom, n_frames: int, momentum: float, power: float) -> int:
-    n = int(lib().kpr_griffin_lim_workspace_bytes(ctypes.byref(geom), int(n_frames), int(momentum != 0), int(power != 1)))
-    if n < 0:
-        check(-1, "kpr_griffin_lim_workspace_bytes")
-    return n
+    return checked_size(lib().kpr_griffin_lim_workspace_bytes(ctypes.byref(geom), int(n_frames), int(momentum != 0),
+                                                              int(power != 1)), "kpr_griffin_lim_workspace_bytes")
 
 
 def griffin_lim(mag, window, synth_window, n_fft: int, win_length: int, hop_length: int, wave_fmt, spec_fmt, n_iter: int,
@@ -1032,15 +1066,15 @@ def hpss(x, fmt, kh: int, kp: int, power: float, margin_h: float, margin_p: floa
     at = lambda ten, off: ctypes.c_void_p(ten.data_ptr() + off * ten.element_size()) if ten.numel() else ctypes.c_void_p(0)
     if output == "both":
         res = new(2 * c)
-        out_ch, ph, pp = 2 * c, at(res, 0), at(res, c if fmt in ("channels_last", CHANNELS_LAST) else c * t * m)
+        out_ch, ph, pp = 2 * c, at(res, 0), at(res, c if is_channels_last(fmt) else c * t * m)
     elif output == "pair":
         res = (new(c), new(c))
         out_ch, ph, pp = c, ptr(res[0]), ptr(res[1])
     else:
         res = new(c)
         out_ch, ph, pp = (c, ptr(res), ctypes.c_void_p(0)) if output == "harmonic" else (c, ctypes.c_void_p(0), ptr(res))
-    _call("kpr_hpss_c64" if cplx else "kpr_hpss_f32", x.device, ptr(x), b, c, t, m, layout(fmt) if isinstance(fmt, str) else int(fmt),
-          int(kh), int(kp), float(power), float(margin_h), float(margin_p), int(mode), ph, pp, out_ch)
+    _call("kpr_hpss_c64" if cplx else "kpr_hpss_f32", x.device, ptr(x), b, c, t, m, layout(fmt), int(kh), int(kp),
+          float(power), float(margin_h), float(margin_p), int(mode), ph, pp, out_ch)
     return res
 
 
@@ -1085,17 +1119,14 @@ def add_noise_plan(batch: int, channels: int, time: int, fmt):
     """(chunk_floats, chunks_per_item, resident_limit_floats, form) of kpr_add_noise_f32's dispatch for this shape under the
     current ``addnoise_variant``; form is ADDNOISE_STREAMED or ADDNOISE_RESIDENT (host only)."""
     out = (ctypes.c_int * 4)()
-    check(lib().kpr_add_noise_plan(int(batch), int(channels), int(time), fmt if isinstance(fmt, int) else layout(fmt), out),
-          "kpr_add_noise_plan")
+    check(lib().kpr_add_noise_plan(int(batch), int(channels), int(time), layout(fmt), out), "kpr_add_noise_plan")
     return tuple(int(v) for v in out)
 
 
 def add_noise_workspace_bytes(batch: int, channels: int, time: int, fmt) -> int:
     """Bytes of workspace the streamed form of kpr_add_noise_f32 / kpr_add_noise_bwd_f32 needs for this shape (host only)."""
-    n = int(lib().kpr_add_noise_workspace_bytes(int(batch), int(channels), int(time), fmt if isinstance(fmt, int) else layout(fmt)))
-    if n < 0:
-        check(-1, "kpr_add_noise_workspace_bytes")
-    return n
+    return checked_size(lib().kpr_add_noise_workspace_bytes(int(batch), int(channels), int(time), layout(fmt)),
+                        "kpr_add_noise_workspace_bytes")
 
 
 def add_noise(x, fmt, bank, lengths, table):

@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _ffi, autograd, backend
-from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
+from .backend import _CH_FIRST_STR, _CH_LAST_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = ['SpecAugment', 'ChannelSwap', 'Reverb', 'AddNoise', 'set_seed']
@@ -60,7 +60,7 @@ def _resolve_format(data_format):
     backend.validate_data_format_str(data_format)
     if isinstance(data_format, dict):           # (the reference's workaround for a Keras deserialisation bug)
         data_format = data_format['config']
-    return backend.image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    return backend.resolve_data_format(data_format)
 
 
 def _config_format(data_format):
@@ -246,13 +246,8 @@ class Reverb(Layer):
     def call(self, x, training=None):
         if training in (None, False):
             return x
-        if len(x.shape) != 3:
-            raise ValueError('Reverb expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-        if _ffi.is_f64(x):
-            raise TypeError('Reverb has float32 kernels only; got a float64 input (cast it to float32)')
-        import torch
-
-        x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+        x, _ = autograd.intake(x, 3, 'float32', 'Reverb expects a rank-3 waveform batch, got shape %s', TypeError,
+                               'Reverb has float32 kernels only; got a float64 input (cast it to float32)')
         t = _ffi.dims_of(x.shape, self.input_data_format)[2]
         self.last_index = _ffi.index_draw(device_state(x.device), x.shape[0], self._plan.n_ir)
         return backend._convolve_run(x, self._plan, self.input_data_format, 'full', index=self.last_index, out_len=t)
@@ -304,13 +299,8 @@ class AddNoise(Layer):
     def call(self, x, training=None):
         if training in (None, False):
             return x
-        if len(x.shape) != 3:
-            raise ValueError('AddNoise expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-        if _ffi.is_f64(x):
-            raise TypeError('AddNoise has float32 kernels only; got a float64 input (cast it to float32)')
-        import torch
-
-        x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+        x, _ = autograd.intake(x, 3, 'float32', 'AddNoise expects a rank-3 waveform batch, got shape %s', TypeError,
+                               'AddNoise has float32 kernels only; got a float64 input (cast it to float32)')
         _, lengths = self._plan.device(x.device)
         self.last_draw = _ffi.noise_draw(device_state(x.device), x.shape[0], lengths, *self._snr)
         y, self.last_stats = backend._add_noise_run(x, self._plan, self.last_draw, self.input_data_format)

@@ -62,6 +62,31 @@ def prep(x, dtype_name: str):
     return x.contiguous()
 
 
+def refuse(x, rank: int, rank_text: str, f64_error, f64_text: str):
+    """The two refusals of a float32-only operation, asked of the input as given, before anything touches a device:
+    ``ValueError(rank_text % shape)`` for a rank other than ``rank``, then ``f64_error(f64_text)`` for float64 / complex128."""
+    if len(x.shape) != rank:
+        raise ValueError(rank_text % (tuple(x.shape),))
+    if _ffi.is_f64(x):
+        raise f64_error(f64_text)
+
+
+def to_device(x, dtype_name: str):
+    """(tensor, recorded): ``x`` as a contiguous tensor of that dtype on the GPU -- through ``prep`` when the call is to be
+    recorded for autograd, else through ``_ffi.as_device`` -- and which of the two it was."""
+    import torch
+
+    if needs_grad(x):
+        return prep(x, dtype_name), True
+    return _ffi.as_device(x, getattr(torch, dtype_name)), False
+
+
+def intake(x, rank: int, dtype_name: str, rank_text: str, f64_error, f64_text: str):
+    """``refuse``, then ``to_device``: the whole intake of an operation that has nothing to do in between."""
+    refuse(x, rank, rank_text, f64_error, f64_text)
+    return to_device(x, dtype_name)
+
+
 def _scaled_window(layer, key, device, f64: bool, scale: float):
     """``scale * layer.window_fn(win_length)`` on the device, cached on the layer."""
     from . import backend

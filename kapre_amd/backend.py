@@ -42,6 +42,11 @@ def _get_image_data_format() -> str:
     return image_data_format()
 
 
+def resolve_data_format(data_format):
+    """``'default'`` becomes the global ``image_data_format()``; anything else is returned as it is."""
+    return image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+
+
 def _get_floatx() -> str:
     return 'float32'
 
@@ -368,14 +373,10 @@ def _pcen_run(x, table_of, eps, data_format, tensors=None):
     import torch
 
     from . import autograd
-    if len(x.shape) != 4:
-        raise ValueError('PCEN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise NotImplementedError('PCEN has float32 kernels only; got a float64 input (cast it to float32)')
+    x, grad = autograd.intake(x, 4, 'float32', 'PCEN expects a rank-4 input, got shape %s', NotImplementedError,
+                              'PCEN has float32 kernels only; got a float64 input (cast it to float32)')
     tensors = tuple(tensors) if tensors is not None else (None,) * 4
-    x_grad = autograd.needs_grad(x)
-    grad = x_grad or any(autograd.needs_grad(t) for t in tensors)
-    x = autograd.prep(x, 'float32') if x_grad else _ffi.as_device(x, torch.float32)
+    grad = grad or any(autograd.needs_grad(t) for t in tensors)
     n_bands = int(x.shape[2] if data_format == _CH_LAST_STR else x.shape[3])
     params = list(table_of(n_bands, x.device)) if n_bands > 0 else [None] * 4
     for i, (name, t) in enumerate(zip(('s', 'alpha', 'delta', 'r'), tensors)):
@@ -415,7 +416,7 @@ def pcen(x, s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6, data_format='defaul
     # (a tensor's place in the table is overwritten: any valid number stands in for it in the validation)
     numbers = [d if t is not None else v for v, t, d in zip(given, tensors, (0.025, 0.98, 2.0, 0.5))]
     *params, eps = pcen_parameters(*numbers, eps)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return _pcen_run(x, lambda n, device: torch.from_numpy(pcen_band_table(params, n)).to(device), eps, fmt,
                      tensors if any(t is not None for t in tensors) else None)
 
@@ -437,16 +438,10 @@ def cmvn_parameters(norm_vars, eps):
 
 def _cmvn_run(x, norm_vars, eps, data_format):
     """CMVN of ``x`` (rank 4) in the resolved ``data_format``; recorded for autograd when ``x`` requires grad."""
-    import torch
-
     from . import autograd
-    if len(x.shape) != 4:
-        raise ValueError('CMVN expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise NotImplementedError('CMVN has float32 kernels only; got a float64 input (cast it to float32)')
-    if autograd.needs_grad(x):
-        return autograd.cmvn(autograd.prep(x, 'float32'), data_format, norm_vars, eps)
-    return _ffi.cmvn(_ffi.as_device(x, torch.float32), data_format, norm_vars, eps)
+    x, grad = autograd.intake(x, 4, 'float32', 'CMVN expects a rank-4 input, got shape %s', NotImplementedError,
+                              'CMVN has float32 kernels only; got a float64 input (cast it to float32)')
+    return (autograd.cmvn if grad else _ffi.cmvn)(x, data_format, norm_vars, eps)
 
 
 def cmvn(x, norm_vars=True, eps=1e-5, data_format='default'):
@@ -461,7 +456,7 @@ def cmvn(x, norm_vars=True, eps=1e-5, data_format='default'):
     ``_ffi.cmvn_plan``'s resident frame count (128), two reads beyond.  A tensor that ``requires_grad`` gets a ``grad_fn``."""
     validate_data_format_str(data_format)
     norm_vars, eps = cmvn_parameters(norm_vars, eps)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return _cmvn_run(x, norm_vars, eps, fmt)
 
 
@@ -498,17 +493,12 @@ _RESAMPLE_SUPPORTED = set()          # parameter tuples whose tables kpr_resampl
 
 def _resample_run(x, params, fmt):
     """``x`` (rank 3) through the conversion ``params`` = resample_parameters(...); ``fmt`` is resolved."""
-    import torch
-
     from . import autograd
-    if len(x.shape) != 3:
-        raise ValueError('resample expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('resample has float32 kernels only; got a float64 input (cast it to float32)')
+    autograd.refuse(x, 3, 'resample expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'resample has float32 kernels only; got a float64 input (cast it to float32)')
     if params[0] == params[1]:
         return x                                                     # nothing to convert, nothing launched
-    grad = autograd.needs_grad(x)
-    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
+    x, grad = autograd.to_device(x, 'float32')
     forward, adjoint = _ffi.resample_plans(*params, x.device)
     out_len = resample_length(_ffi.dims_of(x.shape, fmt)[2], params[0], params[1])
     if grad:
@@ -533,7 +523,7 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_
         for adjoint in (False, True):                      # an O(n_phases) walk on the host: once per conversion
             _ffi.resample_table_size(*params, adjoint)
         _RESAMPLE_SUPPORTED.add(params)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return _resample_run(x, params, fmt)
 
 
@@ -628,17 +618,12 @@ def biquad_sos(kind, sample_rate, freq, q=0.7071067811865476, gain_db=0.0):
 
 def _lfilter_run(x, plan, fmt):
     """``x`` (rank 3) through the launches ``plan`` = ((coef, reverse), ...); ``fmt`` is resolved."""
-    import torch
-
     from . import autograd
-    if len(x.shape) != 3:
-        raise ValueError('lfilter expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('lfilter takes float32 waveforms (its arithmetic is float64 inside); got a float64 input '
-                        '(cast it to float32)')
-    if autograd.needs_grad(x):
-        return autograd.lfilter(autograd.prep(x, 'float32'), fmt, plan)
-    x = _ffi.as_device(x, torch.float32)
+    x, grad = autograd.intake(x, 3, 'float32', 'lfilter expects a rank-3 waveform batch, got shape %s', TypeError,
+                              'lfilter takes float32 waveforms (its arithmetic is float64 inside); got a float64 input '
+                              '(cast it to float32)')
+    if grad:
+        return autograd.lfilter(x, fmt, plan)
     for coef, reverse in plan:
         x = _ffi.lfilter(x, fmt, coef, reverse)
     return x
@@ -658,7 +643,7 @@ def lfilter(x, sos, data_format='default', reverse=False):
     malformed or unstable ``sos`` (``lfilter_sections``), ``TypeError`` for a float64 input."""
     validate_data_format_str(data_format)
     sections = lfilter_sections(sos)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return _lfilter_run(x, tuple((c, bool(reverse)) for c in sections), fmt)
 
 
@@ -746,20 +731,8 @@ def convolve_table(ir, L, adjoint=False):
     return np.fft.rfft(padded.reshape(n_ir, P, L), n=2 * L, axis=-1).astype(np.complex64)
 
 
-_CONVOLVE_CONSTS = {}                    # (what, ..., device) -> device tensor
-_CONVOLVE_CONSTS_MAX = 32                # filter tables kept per process (a layer holds on to its own)
-
-
-def _convolve_const(key, device, make_numpy):
-    import torch
-
-    k = key + (str(device),)
-    t = _CONVOLVE_CONSTS.get(k)
-    if t is None:
-        while len(_CONVOLVE_CONSTS) >= _CONVOLVE_CONSTS_MAX:
-            _CONVOLVE_CONSTS.pop(next(iter(_CONVOLVE_CONSTS)))
-        t = _CONVOLVE_CONSTS[k] = torch.from_numpy(np.ascontiguousarray(make_numpy())).to(device)
-    return t
+# the tables, windows and index vectors of every convolution: 32 kept per process (a plan holds on to its own tables)
+_CONVOLVE_CONSTS = _ffi.DeviceConstants(max_entries=32)
 
 
 class ConvolvePlan:
@@ -775,21 +748,18 @@ class ConvolvePlan:
         self.n_part = -(-self.ir_len // self.L)
         _convolve_table_bytes(self.n_ir, self.n_part, self.L)
         self._digest = hashlib.sha1(self.h.tobytes()).hexdigest()
-        self._tables = {}
+        self._tables = _ffi.DeviceConstants()
 
     def table(self, device, adjoint=False):
-        k = (str(device), bool(adjoint))
-        t = self._tables.get(k)
-        if t is None:
-            t = self._tables[k] = _convolve_const(('table', self._digest, self.h.shape, self.L, bool(adjoint)), device,
-                                                   lambda: convolve_table(self.h, self.L, adjoint))
-        return t
+        # (the process-wide copy, shared by the plans of equal impulse responses, may be evicted; this plan's stays)
+        return self._tables.get(bool(adjoint), device, lambda: _CONVOLVE_CONSTS.get(
+            ('table', self._digest, self.h.shape, self.L, bool(adjoint)), device, lambda: convolve_table(self.h, self.L, adjoint)))
 
     def windows(self, device):
         """(analysis, synthesis): ones(2 L) and [0] * L + [1] * L"""
         L = self.L
-        return (_convolve_const(('ones', L), device, lambda: np.ones(2 * L, dtype=np.float32)),
-                _convolve_const(('tail', L), device, lambda: np.concatenate([np.zeros(L, np.float32), np.ones(L, np.float32)])))
+        return (_CONVOLVE_CONSTS.get(('ones', L), device, lambda: np.ones(2 * L, dtype=np.float32)),
+                _CONVOLVE_CONSTS.get(('tail', L), device, lambda: np.concatenate([np.zeros(L, np.float32), np.ones(L, np.float32)])))
 
 
 def convolve_length(t, ir_len, mode):
@@ -842,7 +812,7 @@ def _convolve_index(plan, index, batch, device):
         if plan.n_ir != batch:
             raise ValueError('convolve: %d impulse responses for a batch of %d: without index there must be one, or one per '
                              'batch item' % (plan.n_ir, batch))
-        return _convolve_const(('arange', batch), device, lambda: np.arange(batch, dtype=np.int32))
+        return _CONVOLVE_CONSTS.get(('arange', batch), device, lambda: np.arange(batch, dtype=np.int32))
     if isinstance(index, torch.Tensor) and index.is_cuda:
         if index.dtype != torch.int32 or tuple(index.shape) != (batch,):
             raise ValueError('convolve: a device index must be an int32 tensor of shape (%d,), got %s %s'
@@ -860,18 +830,13 @@ def _convolve_index(plan, index, batch, device):
 def _convolve_run(x, plan, fmt, mode, index=None, out_len=None):
     """``x`` (rank 3) convolved along time through ``plan``; ``fmt`` is resolved.  ``out_len``: keep that many samples from
     the mode's first one (Reverb: the first T of 'full')."""
-    import torch
-
     from . import autograd
-    if len(x.shape) != 3:
-        raise ValueError('convolve expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('convolve has float32 kernels only; got a float64 input (cast it to float32)')
+    autograd.refuse(x, 3, 'convolve expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'convolve has float32 kernels only; got a float64 input (cast it to float32)')
     b, _, t = _ffi.dims_of(x.shape, fmt)
     n_out = convolve_length(t, plan.ir_len, mode) if out_len is None else int(out_len)
     first = _convolve_offset(plan.ir_len, mode)
-    grad = autograd.needs_grad(x)
-    x = autograd.prep(x, 'float32') if grad else _ffi.as_device(x, torch.float32)
+    x, grad = autograd.to_device(x, 'float32')
     idx = _convolve_index(plan, index, b, x.device)
     if grad:
         return autograd.convolve(x, fmt, plan, idx, first, n_out)
@@ -898,7 +863,7 @@ def fftconvolve(x, ir, mode='full', index=None, data_format='default', block_siz
     validate_data_format_str(data_format)
     if mode not in CONVOLVE_MODES:
         raise ValueError("convolve: mode must be one of 'full', 'same', 'valid', got %r" % (mode,))
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return _convolve_run(x, ConvolvePlan(ir, block_size), fmt, mode, index)
 
 
@@ -950,15 +915,10 @@ class NoisePlan:
     def __init__(self, noises):
         self.bank, self.lengths = noise_bank(noises)
         self.n_noise = int(self.bank.shape[0])
-        self._dev = {}
+        self._consts = _ffi.DeviceConstants()
 
     def device(self, device):
-        import torch
-
-        t = self._dev.get(str(device))
-        if t is None:
-            t = self._dev[str(device)] = (torch.from_numpy(self.bank).to(device), torch.from_numpy(self.lengths).to(device))
-        return t
+        return self._consts.get('bank', device, lambda: (self.bank, self.lengths))
 
 
 def _noise_column(v, batch, device, what, dtype, np_dtype):
@@ -1026,17 +986,13 @@ def add_noise(x, noise, snr_db, index=None, offset=None, data_format='default'):
     (batch,); ``index`` / ``offset``: host integers, host sequences or int32 device tensors, 0 by default.  Noise and snr are
     constants; a waveform that ``requires_grad`` gets a ``grad_fn`` whose backward is exact (the gain depends on ``x``).
     ``TypeError`` for a float64 input, ``ValueError`` for a rank other than 3."""
-    import torch
-
     from . import autograd
     validate_data_format_str(data_format)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
-    if len(x.shape) != 3:
-        raise ValueError('add_noise expects a rank-3 waveform batch, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('add_noise has float32 kernels only; got a float64 input (cast it to float32)')
+    fmt = resolve_data_format(data_format)
+    autograd.refuse(x, 3, 'add_noise expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'add_noise has float32 kernels only; got a float64 input (cast it to float32)')
     plan = noise if isinstance(noise, NoisePlan) else NoisePlan(noise)
-    x = autograd.prep(x, 'float32') if autograd.needs_grad(x) else _ffi.as_device(x, torch.float32)
+    x, _ = autograd.to_device(x, 'float32')
     table = noise_table(int(x.shape[0]), x.device, plan.lengths, snr_db, index, offset)
     return _add_noise_run(x, plan, table, fmt)[0]
 
@@ -1077,10 +1033,10 @@ def griffin_lim(mag, n_fft=2048, win_length=None, hop_length=None, window_name=N
         win_length = n_fft
     if hop_length is None:
         hop_length = win_length // 4
-    resolve = lambda fmt: image_data_format() if fmt == _CH_DEFAULT_STR else fmt
     wave, sc = time_frequency._griffin_lim_run(
         mag, time_frequency._GL_CONSTS, int(n_fft), int(win_length), int(hop_length), window_name, get_window_fn(window_name),
-        n_iter, momentum, power, bool(rand_init), length, resolve(input_data_format), resolve(output_data_format), init)
+        n_iter, momentum, power, bool(rand_init), length, resolve_data_format(input_data_format),
+        resolve_data_format(output_data_format), init)
     return (wave, sc) if return_convergence else wave
 
 
@@ -1137,7 +1093,7 @@ def phase_vocoder(x, rate, data_format='default'):
 
     validate_data_format_str(data_format)
     rate = time_stretch_parameters(rate)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return time_frequency._time_stretch_run(x, rate, fmt, time_frequency._TS_CONSTS)
 
 
@@ -1183,5 +1139,5 @@ def hpss(x, kernel_size=31, power=2.0, margin=1.0, mask=False, data_format='defa
 
     validate_data_format_str(data_format)
     sizes, power, margins = hpss_parameters(kernel_size, power, margin)
-    fmt = image_data_format() if data_format == _CH_DEFAULT_STR else data_format
+    fmt = resolve_data_format(data_format)
     return time_frequency._hpss_run(x, sizes, power, margins, bool(mask), fmt, 'pair')

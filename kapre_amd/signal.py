@@ -12,15 +12,11 @@ import math
 import numpy as np
 
 from . import _ffi, autograd, backend
-from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
+from .backend import _CH_FIRST_STR, _CH_LAST_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample', 'LFilter', 'Preemphasis',
            'Deemphasis', 'Convolve']
-
-
-def _resolve_format(fmt):
-    return backend.image_data_format() if fmt == _CH_DEFAULT_STR else fmt
 
 
 def _as_waveform(x):
@@ -54,7 +50,7 @@ class Frame(Layer):
         self.pad_end = pad_end
         self.pad_value = pad_value
         self.data_format_str = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
 
     def compute_output_shape(self, input_shape):
@@ -101,7 +97,7 @@ class Energy(Layer):
         self.pad_end = pad_end
         self.pad_value = pad_value
         self.data_format_str = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
 
     def compute_output_shape(self, input_shape):
@@ -209,16 +205,12 @@ class LogmelToMFCC(Layer):
         backend.validate_data_format_str(data_format)
         self.n_mfccs = n_mfccs
         self.data_format_str = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.permutation = (0, 1, 3, 2) if self.data_format == _CH_LAST_STR else None
-        self._mats = {}
+        self._consts = _ffi.DeviceConstants()
 
     def _matrix(self, n_mels, device):
-        key = (n_mels, str(device))
-        if key not in self._mats:
-            import torch
-            self._mats[key] = torch.from_numpy(mfcc_matrix(n_mels, self.n_mfccs)).to(device)
-        return self._mats[key]
+        return self._consts.get(n_mels, device, lambda: mfcc_matrix(n_mels, self.n_mfccs))
 
     def compute_output_shape(self, input_shape):
         """the mel axis (3 for channels_first, 2 for channels_last) becomes n_mfccs"""
@@ -272,7 +264,7 @@ class Resample(Layer):
             for adjoint in (False, True):                    # ValueError for a table the library does not support
                 _ffi.resample_table_size(*self._params, adjoint)
         self.data_format_str = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
 
     def compute_output_shape(self, input_shape):
@@ -319,7 +311,7 @@ class LFilter(Layer):
         # zero_phase: the whole cascade forward, then the whole cascade from the last sample to the first
         self._plan = tuple((c, r) for r in ((False, True) if self.zero_phase else (False,)) for c in self._sections)
         self.data_format_str = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
 
     def compute_output_shape(self, input_shape):
@@ -396,7 +388,7 @@ class Convolve(Layer):
         self.mode = mode
         self.block_size = None if block_size is None else int(block_size)
         self.input_data_format_str = input_data_format
-        self.input_data_format = _resolve_format(input_data_format)
+        self.input_data_format = backend.resolve_data_format(input_data_format)
         self.time_axis = 2 if self.input_data_format == _CH_FIRST_STR else 1
 
     def compute_output_shape(self, input_shape):

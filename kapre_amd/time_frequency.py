@@ -16,12 +16,13 @@ pass when decibel scaling is on).
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import numpy as np
 
 from . import _ffi, autograd, backend
 from .augmentation import SpecAugment
-from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
+from .backend import _CH_FIRST_STR, _CH_LAST_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = [
@@ -41,32 +42,11 @@ __all__ = [
 ]
 
 
-def _resolve_format(fmt):
-    return backend.image_data_format() if fmt == _CH_DEFAULT_STR else fmt
-
-
 def _forget_packed(ptr):
     try:
         _ffi.filterbank_forget(ptr)
     except Exception:        # interpreter shutdown: the library may be gone already
         pass
-
-
-class _DeviceConstants:
-    """Per-device cache of small constant tensors (windows, filterbanks)."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def get(self, key, device, make_numpy):
-        import torch
-
-        k = (key, str(device))
-        t = self._cache.get(k)
-        if t is None:
-            t = torch.from_numpy(np.ascontiguousarray(make_numpy())).to(device)
-            self._cache[k] = t
-        return t
 
 
 class _WorkspacePool:
@@ -143,9 +123,9 @@ class STFT(Layer):
 
         self.input_data_format_original = input_data_format
         self.output_data_format_original = output_data_format
-        self.output_data_format = _resolve_format(output_data_format)
-        self.input_data_format = _resolve_format(input_data_format)
-        self._consts = _DeviceConstants()
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self._consts = _ffi.DeviceConstants()
 
     # -- helpers -----------------------------------------------------------------------------
     def _geom(self, x) -> _ffi.StftGeom:
@@ -278,9 +258,9 @@ class InverseSTFT(Layer):
 
         self.input_data_format_original = input_data_format
         self.output_data_format_original = output_data_format
-        self.output_data_format = _resolve_format(output_data_format)
-        self.input_data_format = _resolve_format(input_data_format)
-        self._consts = _DeviceConstants()
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self._consts = _ffi.DeviceConstants()
 
     def compute_output_shape(self, input_shape):
         """(b, frame, freq, ch) / (b, ch, frame, freq) -> (b, (frame - 1) hop + win, ch) / (b, ch, ...): untrimmed, as upstream"""
@@ -446,7 +426,7 @@ class ApplyFilterbank(Layer):
 
         self.type = type
         self.filterbank_kwargs = filterbank_kwargs
-        self._consts = _DeviceConstants()
+        self._consts = _ffi.DeviceConstants()
         self._kranges = None
         self._fb_version = 0
 
@@ -456,7 +436,7 @@ class ApplyFilterbank(Layer):
             self.filterbank = _mel_filterbank = backend.filterbank_mel(**filterbank_kwargs)
 
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
 
         if self.data_format == _CH_FIRST_STR:
             self.freq_axis = 3
@@ -480,7 +460,7 @@ class ApplyFilterbank(Layer):
         self.__dict__['_filterbank'] = value
         self._fb_version += 1
         self._kranges = None
-        self._consts._cache.clear()
+        self._consts.clear()
 
     def _fb_device(self, device):
         return self._consts.get('fb', device, lambda: np.asarray(self.filterbank, np.float32))
@@ -489,13 +469,9 @@ class ApplyFilterbank(Layer):
         """Filterbank in MFMA-fragment order (kpr_filterbank_pack), built once per device.  When the tensor is released
         (layer dropped, filterbank replaced) the library is told to forget the address: its header check is cached per
         address, and the allocator hands freed addresses out again."""
-        fresh = []
-        t = self._consts.get('fb_packed', device, lambda: fresh.append(1) or _ffi.filterbank_pack(
-            np.asarray(self.filterbank, np.float32), self._fb_kranges()))
-        if fresh:
-            import weakref
-            weakref.finalize(t, _forget_packed, t.data_ptr())
-        return t
+        return self._consts.get('fb_packed', device,
+                                lambda: _ffi.filterbank_pack(np.asarray(self.filterbank, np.float32), self._fb_kranges()),
+                                on_new=lambda t: weakref.finalize(t, _forget_packed, t.data_ptr()))
 
     def _fb_kranges(self):
         """Host int32 [lo, hi) row ranges per 16-filter tile (exact zeros outside)."""
@@ -581,7 +557,7 @@ class Delta(Layer):
                 'mode.lower() should be one of {}'.format(str(('symmetric', 'reflect', 'constant')))
                 + 'but it is {}'.format(mode))
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
         self.win_length = win_length
         self.mode = mode
         self.n = (self.win_length - 1) // 2
@@ -621,7 +597,7 @@ class ConcatenateFrequencyMap(Layer):
         if isinstance(data_format, dict):           # (the reference's workaround for a Keras deserialisation bug)
             data_format = data_format['config']
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
 
     def compute_output_shape(self, input_shape):
         shape = list(input_shape)
@@ -698,8 +674,8 @@ class PCEN(Layer):
         self.smooth_coef, self.alpha, self.delta, self.r = (
             np.asarray(v, dtype=np.float64).tolist() for v in (smooth_coef, alpha, delta, r))     # JSON-ready
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
-        self._consts = _DeviceConstants()
+        self.data_format = backend.resolve_data_format(data_format)
+        self._consts = _ffi.DeviceConstants()
         if isinstance(trainable_params, bool):
             names = self.PARAM_NAMES if trainable_params else ()
         elif isinstance(trainable_params, (list, tuple)) and all(isinstance(n, str) for n in trainable_params):
@@ -821,7 +797,7 @@ class CMVN(Layer):
             data_format = data_format['config']
         self.norm_vars, self.eps = backend.cmvn_parameters(norm_vars, eps)
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
 
     def compute_output_shape(self, input_shape):
         return tuple(input_shape)
@@ -837,7 +813,7 @@ class CMVN(Layer):
         return config
 
 
-_GL_CONSTS = _DeviceConstants()          # the windows of backend.griffin_lim (the layer keeps its own)
+_GL_CONSTS = _ffi.DeviceConstants()          # the windows of backend.griffin_lim (the layer keeps its own)
 
 
 def _griffin_lim_run(x, consts, n_fft, win_length, hop_length, window_name, window_fn, n_iter, momentum, power, rand_init,
@@ -847,13 +823,9 @@ def _griffin_lim_run(x, consts, n_fft, win_length, hop_length, window_name, wind
     import torch
 
     from .augmentation import device_state
-    if len(x.shape) != 4:
-        raise ValueError('GriffinLim expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('GriffinLim has float32 kernels only; got a float64 input (cast it to float32)')
-    if isinstance(x, torch.Tensor):
-        x = x.detach()
-    x = _ffi.as_device(x, torch.float32)
+    x, _ = autograd.intake(x.detach() if isinstance(x, torch.Tensor) else x, 4, 'float32',
+                           'GriffinLim expects a rank-4 input, got shape %s', TypeError,
+                           'GriffinLim has float32 kernels only; got a float64 input (cast it to float32)')
     k = _ffi.dims_of(x.shape, spec_fmt)[3]
     if k != n_fft // 2 + 1:
         raise ValueError('GriffinLim: the frequency axis has %d bins, n_fft = %d needs %d' % (k, n_fft, n_fft // 2 + 1))
@@ -936,9 +908,9 @@ class GriffinLim(Layer):
         self.length = None if length is None else int(length)
         self.input_data_format_original = input_data_format
         self.output_data_format_original = output_data_format
-        self.input_data_format = _resolve_format(input_data_format)
-        self.output_data_format = _resolve_format(output_data_format)
-        self._consts = _DeviceConstants()
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self._consts = _ffi.DeviceConstants()
         self.last_convergence = None
 
     def compute_output_shape(self, input_shape):
@@ -978,7 +950,7 @@ class GriffinLim(Layer):
         return config
 
 
-_TS_CONSTS = _DeviceConstants()          # the tables of backend.phase_vocoder (the layer keeps its own)
+_TS_CONSTS = _ffi.DeviceConstants()          # the tables of backend.phase_vocoder (the layer keeps its own)
 
 
 def _time_stretch_run(x, rate, fmt, consts):
@@ -986,16 +958,12 @@ def _time_stretch_run(x, rate, fmt, consts):
     ``consts``, one pair per (frames, rate, device)."""
     import torch
 
-    if len(x.shape) != 4:
-        raise ValueError('TimeStretch expects a rank-4 input, got shape %s' % (tuple(x.shape),))
     cplx = x.is_complex() if isinstance(x, torch.Tensor) else np.iscomplexobj(x)
-    if not cplx:
+    if len(x.shape) == 4 and not cplx:                   # (behind the rank refusal, ahead of the 64-bit one)
         raise TypeError('TimeStretch expects a complex spectrogram (the output of STFT), got dtype %s' % (x.dtype,))
-    if _ffi.is_f64(x):
-        raise TypeError('TimeStretch has float32 kernels only; got a complex128 input (cast it to complex64)')
-    if isinstance(x, torch.Tensor):
-        x = x.detach()
-    x = _ffi.as_device(x, torch.complex64)
+    x, _ = autograd.intake(x.detach() if isinstance(x, torch.Tensor) else x, 4, 'complex64',
+                           'TimeStretch expects a rank-4 input, got shape %s', TypeError,
+                           'TimeStretch has float32 kernels only; got a complex128 input (cast it to complex64)')
     frames = int(_ffi.dims_of(x.shape, fmt)[2])
     frames_out = backend.time_stretch_length(frames, rate)
     table = lambda which: (lambda: backend.time_stretch_table(frames, rate)[which])
@@ -1040,8 +1008,8 @@ class TimeStretch(Layer):
             data_format = data_format['config']
         self.rate = backend.time_stretch_parameters(rate)
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
-        self._consts = _DeviceConstants()
+        self.data_format = backend.resolve_data_format(data_format)
+        self._consts = _ffi.DeviceConstants()
 
     def compute_output_shape(self, input_shape):
         """frames -> ceil(frames / rate); ``None`` stays ``None``"""
@@ -1064,14 +1032,10 @@ def _hpss_run(x, sizes, power, margins, mask, fmt, output):
     ``_ffi.hpss``."""
     import torch
 
-    if len(x.shape) != 4:
-        raise ValueError('HPSS expects a rank-4 input, got shape %s' % (tuple(x.shape),))
-    if _ffi.is_f64(x):
-        raise TypeError('HPSS has float32 kernels only; got a %s input (cast it to float32 / complex64)' % (x.dtype,))
     cplx = x.is_complex() if isinstance(x, torch.Tensor) else np.iscomplexobj(x)
-    if isinstance(x, torch.Tensor):
-        x = x.detach()
-    x = _ffi.as_device(x, torch.complex64 if cplx else torch.float32)
+    x, _ = autograd.intake(x.detach() if isinstance(x, torch.Tensor) else x, 4, 'complex64' if cplx else 'float32',
+                           'HPSS expects a rank-4 input, got shape %s', TypeError,
+                           'HPSS has float32 kernels only; got a %s input (cast it to float32 / complex64)' % (x.dtype,))
     return _ffi.hpss(x, fmt, sizes[0], sizes[1], power, margins[0], margins[1], _ffi.HPSS_MASKS if mask else _ffi.HPSS_VALUES, output)
 
 
@@ -1114,7 +1078,7 @@ class HPSS(Layer):
         self.output = output
         self.mask = bool(mask)
         self.data_format_original = data_format
-        self.data_format = _resolve_format(data_format)
+        self.data_format = backend.resolve_data_format(data_format)
 
     def compute_output_shape(self, input_shape):
         """the input's shape; 'both' doubles the channel axis (``None`` stays ``None``)"""
@@ -1209,7 +1173,7 @@ def fused_melspectrogram(stft: STFT, fb_layer: ApplyFilterbank, db_layer, x):
             rc = launch()
     else:
         rc = launch()
-    if rc == -4 and plan.fbp is not None:
+    if rc == _ffi.E_WORKSPACE and plan.fbp is not None:
         # KPR_E_WORKSPACE: a bank whose schedule none of the fused kernels holds (dense matrices): the two-launch path stages the
         # spectrum and needs the unpacked workspace -- the plan is upgraded once and keeps the larger workspace
         ws_bytes = _ffi.mel_workspace_bytes(plan.g_ref, plan.n_filt, plan.db_ref, False)

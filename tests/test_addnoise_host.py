@@ -347,3 +347,20 @@ def test_install_as_kapre_reaches_the_layer():
     code = ("import kapre_amd; kapre_amd.install_as_kapre(); from kapre.augmentation import AddNoise; import kapre; "
             "assert AddNoise is kapre_amd.AddNoise and kapre.AddNoise is AddNoise")
     subprocess.run([sys.executable, "-c", code], check=True, cwd=REPO)
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='add_noise expects a rank-3 waveform batch'):
+        backend.add_noise(np.zeros((2, 100), np.float32), np.ones(4), 10.0)
+    with pytest.raises(TypeError, match='add_noise has float32 kernels only; got a float64 input'):
+        backend.add_noise(np.zeros((2, 100, 1), np.float64), np.ones(4), 10.0)
+    with pytest.raises(ValueError, match='add_noise expects a rank-3 waveform batch'):
+        backend.add_noise(np.zeros((2, 100), np.float64), np.ones(4), 10.0)
+    with pytest.raises(ValueError, match='AddNoise expects a rank-3 waveform batch'):
+        kapre.AddNoise(np.ones(4))(np.zeros((2, 100), np.float32), training=True)
+    with pytest.raises(TypeError, match='AddNoise has float32 kernels only; got a float64 input'):
+        kapre.AddNoise(np.ones(4))(np.zeros((2, 100, 1), np.float64), training=True)
+    with pytest.raises(ValueError, match='AddNoise expects a rank-3 waveform batch'):
+        kapre.AddNoise(np.ones(4))(np.zeros((2, 100), np.float64), training=True)

@@ -227,3 +227,20 @@ def test_host_only_argument_checks():
     # frames * inner reaches 2^31: refused (one element below is not: that call would launch and is not made here)
     assert fwd(frames=1 << 20, inner=1 << 11) == -2 and b"2^31" in L.kpr_last_error()
     assert bwd(frames=1 << 21, inner=1 << 10) == -2
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='CMVN expects a rank-4 input'):
+        kapre.CMVN()(np.zeros((4, 3, 1), np.float32))
+    with pytest.raises(NotImplementedError, match='CMVN has float32 kernels only; got a float64 input'):
+        kapre.CMVN()(np.zeros((1, 4, 3, 1), np.float64))
+    with pytest.raises(ValueError, match='CMVN expects a rank-4 input'):
+        kapre.CMVN()(np.zeros((4, 3, 1), np.float64))
+    with pytest.raises(ValueError, match='CMVN expects a rank-4 input'):
+        backend.cmvn(np.zeros((4, 3, 1), np.float32))
+    with pytest.raises(NotImplementedError, match='CMVN has float32 kernels only; got a float64 input'):
+        backend.cmvn(np.zeros((1, 4, 3, 1), np.float64))
+    with pytest.raises(ValueError, match='CMVN expects a rank-4 input'):
+        backend.cmvn(np.zeros((4, 3, 1), np.float64))

@@ -268,3 +268,26 @@ def test_readme_and_design_name_the_new_kernel():
     assert "kpr_spec_fir_kernels.h" in readme and "Convolve" in readme and "Reverb" in readme
     design = open(os.path.join(REPO, "DESIGN.md")).read()
     assert "4.18" in design and "k_spec_fir" in design
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='convolve expects a rank-3 waveform batch'):
+        kapre.Convolve(np.ones(4))(np.zeros((2, 100), np.float32))
+    with pytest.raises(TypeError, match='convolve has float32 kernels only; got a float64 input'):
+        kapre.Convolve(np.ones(4))(np.zeros((2, 100, 1), np.float64))
+    with pytest.raises(ValueError, match='convolve expects a rank-3 waveform batch'):
+        kapre.Convolve(np.ones(4))(np.zeros((2, 100), np.float64))
+    with pytest.raises(ValueError, match='convolve expects a rank-3 waveform batch'):
+        backend.fftconvolve(np.zeros((2, 100), np.float32), np.ones(4))
+    with pytest.raises(TypeError, match='convolve has float32 kernels only; got a float64 input'):
+        backend.fftconvolve(np.zeros((2, 100, 1), np.float64), np.ones(4))
+    with pytest.raises(ValueError, match='convolve expects a rank-3 waveform batch'):
+        backend.fftconvolve(np.zeros((2, 100), np.float64), np.ones(4))
+    with pytest.raises(ValueError, match='Reverb expects a rank-3 waveform batch'):
+        kapre.Reverb(np.ones((2, 4)))(np.zeros((2, 100), np.float32), training=True)
+    with pytest.raises(TypeError, match='Reverb has float32 kernels only; got a float64 input'):
+        kapre.Reverb(np.ones((2, 4)))(np.zeros((2, 100, 1), np.float64), training=True)
+    with pytest.raises(ValueError, match='Reverb expects a rank-3 waveform batch'):
+        kapre.Reverb(np.ones((2, 4)))(np.zeros((2, 100), np.float64), training=True)

@@ -179,3 +179,20 @@ def test_philox_phase_is_independent_of_the_layout():
     # uniform enough: 16 sectors of 210 draws, none empty and none with a third of them
     hist = np.histogram(first, bins=16, range=(0, 2 * np.pi))[0]
     assert hist.min() > 0 and hist.max() < first.size // 3
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='GriffinLim expects a rank-4 input'):
+        kapre.GriffinLim(n_fft=256, hop_length=64)(np.zeros((9, 129, 1), np.float32))
+    with pytest.raises(TypeError, match='GriffinLim has float32 kernels only; got a float64 input'):
+        kapre.GriffinLim(n_fft=256, hop_length=64)(np.zeros((1, 9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='GriffinLim expects a rank-4 input'):
+        kapre.GriffinLim(n_fft=256, hop_length=64)(np.zeros((9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='GriffinLim expects a rank-4 input'):
+        backend.griffin_lim(np.zeros((9, 129, 1), np.float32), n_fft=256, hop_length=64)
+    with pytest.raises(TypeError, match='GriffinLim has float32 kernels only; got a float64 input'):
+        backend.griffin_lim(np.zeros((1, 9, 129, 1), np.float64), n_fft=256, hop_length=64)
+    with pytest.raises(ValueError, match='GriffinLim expects a rank-4 input'):
+        backend.griffin_lim(np.zeros((9, 129, 1), np.float64), n_fft=256, hop_length=64)

@@ -200,6 +200,8 @@ def test_library_exports_every_header_symbol():
     for n in names:
         assert hasattr(handle, n), "missing export %s" % n
     assert set(names) == set(_ffi.EXPORTS), "ctypes table and header disagree"
+    codes = {k: int(v) for k, v in re.findall(r"\bKPR_(E_[A-Z]+)\s*=\s*(-?\d+)", open(os.path.join(REPO, "include", "kapre_hip.h")).read())}
+    assert len(codes) == 5 and codes == {k: v for k, v in vars(_ffi).items() if k.startswith("E_")}, "error codes and header disagree"
     assert _ffi.lib().kpr_version() == 120
 
 

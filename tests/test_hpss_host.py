@@ -258,3 +258,24 @@ def test_output_shapes():
     assert hp.output == 'harmonic' and hp.kernel_size == (31, 31) and hp.power == 2.0 and hp.margin == (1.0, 1.0)
     stft = kapre.get_hpss_layer(n_fft=1024, win_length=800).layers[0]
     assert stft.win_length == 800 and stft.hop_length == 200
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='HPSS expects a rank-4 input'):
+        kapre.HPSS()(np.zeros((9, 129, 1), np.float32))
+    with pytest.raises(TypeError, match='HPSS has float32 kernels only; got a float64 input'):
+        kapre.HPSS()(np.zeros((1, 9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='HPSS expects a rank-4 input'):
+        kapre.HPSS()(np.zeros((9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='HPSS expects a rank-4 input'):
+        backend.hpss(np.zeros((9, 129, 1), np.float32))
+    with pytest.raises(TypeError, match='HPSS has float32 kernels only; got a float64 input'):
+        backend.hpss(np.zeros((1, 9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='HPSS expects a rank-4 input'):
+        backend.hpss(np.zeros((9, 129, 1), np.float64))
+    with pytest.raises(TypeError, match='HPSS has float32 kernels only; got a complex128 input'):
+        kapre.HPSS()(np.zeros((1, 9, 129, 1), np.complex128))
+    with pytest.raises(ValueError, match='HPSS expects a rank-4 input'):
+        kapre.HPSS()(np.zeros((9, 129, 1), np.complex128))

@@ -383,3 +383,20 @@ def test_header_prototypes_exports_and_documents():
     assert "lfilter_variant" in text and _ffi.lib().kpr_version() == 120
     readme = open(os.path.join(REPO, "README.md")).read()
     assert "kpr_lfilter_kernels.h" in readme and "lfilter_variant" in readme
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='lfilter expects a rank-3 waveform batch'):
+        kapre.LFilter([1.0, 0.0, 0.0, 1.0, 0.5, 0.0])(np.zeros((8, 1), np.float32))
+    with pytest.raises(TypeError, match='lfilter takes float32 waveforms'):
+        kapre.LFilter([1.0, 0.0, 0.0, 1.0, 0.5, 0.0])(np.zeros((1, 8, 1), np.float64))
+    with pytest.raises(ValueError, match='lfilter expects a rank-3 waveform batch'):
+        kapre.LFilter([1.0, 0.0, 0.0, 1.0, 0.5, 0.0])(np.zeros((8, 1), np.float64))
+    with pytest.raises(ValueError, match='lfilter expects a rank-3 waveform batch'):
+        backend.lfilter(np.zeros((8, 1), np.float32), [1.0, 0.0, 0.0, 1.0, 0.5, 0.0])
+    with pytest.raises(TypeError, match='lfilter takes float32 waveforms'):
+        backend.lfilter(np.zeros((1, 8, 1), np.float64), [1.0, 0.0, 0.0, 1.0, 0.5, 0.0])
+    with pytest.raises(ValueError, match='lfilter expects a rank-3 waveform batch'):
+        backend.lfilter(np.zeros((8, 1), np.float64), [1.0, 0.0, 0.0, 1.0, 0.5, 0.0])

@@ -233,3 +233,26 @@ def test_header_prototypes_and_exports():
         assert name in _ffi.EXPORTS and hasattr(handle, name), name
     assert _ffi.EXPORTS["kpr_resample_f32"][1][-1] is ctypes.c_void_p          # the stream comes last
     assert re.search(r"#define\s+KPR_VERSION\s+120\b", text) and _ffi.lib().kpr_version() == 120
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        kapre.Resample(2, 1)(np.zeros((8, 1), np.float32))
+    with pytest.raises(TypeError, match='resample has float32 kernels only; got a float64 input'):
+        kapre.Resample(2, 1)(np.zeros((1, 8, 1), np.float64))
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        kapre.Resample(2, 1)(np.zeros((8, 1), np.float64))
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        backend.resample(np.zeros((8, 1), np.float32), 2, 1)
+    with pytest.raises(TypeError, match='resample has float32 kernels only; got a float64 input'):
+        backend.resample(np.zeros((1, 8, 1), np.float64), 2, 1)
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        backend.resample(np.zeros((8, 1), np.float64), 2, 1)
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        backend.resample(np.zeros((8, 1), np.float32), 2, 2)
+    with pytest.raises(TypeError, match='resample has float32 kernels only; got a float64 input'):
+        backend.resample(np.zeros((1, 8, 1), np.float64), 2, 2)
+    with pytest.raises(ValueError, match='resample expects a rank-3 waveform batch'):
+        backend.resample(np.zeros((8, 1), np.float64), 2, 2)

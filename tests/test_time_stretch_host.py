@@ -200,3 +200,24 @@ def test_output_shapes():
     assert stft.n_fft == 2048 and stft.hop_length == 512 and stft.win_length == 2048 and stft.window_name == 'hann_window'
     assert not stft.pad_begin and not stft.pad_end
     assert kapre.get_time_stretch_layer(0.5).layers[2].forward_window_name == 'hann_window'
+
+
+def test_refusal_table_rank_first_then_64_bit():
+    """each intake of this operation: the rank error, the 64-bit refusal with its exception class, and the rank error when both
+    apply -- all raised on the input as given, before a device is looked for"""
+    with pytest.raises(ValueError, match='TimeStretch expects a rank-4 input'):
+        kapre.TimeStretch(0.8)(np.zeros((9, 129, 1), np.complex64))
+    with pytest.raises(TypeError, match='TimeStretch has float32 kernels only; got a complex128 input'):
+        kapre.TimeStretch(0.8)(np.zeros((1, 9, 129, 1), np.complex128))
+    with pytest.raises(ValueError, match='TimeStretch expects a rank-4 input'):
+        kapre.TimeStretch(0.8)(np.zeros((9, 129, 1), np.complex128))
+    with pytest.raises(ValueError, match='TimeStretch expects a rank-4 input'):
+        backend.phase_vocoder(np.zeros((9, 129, 1), np.complex64), 0.8)
+    with pytest.raises(TypeError, match='TimeStretch has float32 kernels only; got a complex128 input'):
+        backend.phase_vocoder(np.zeros((1, 9, 129, 1), np.complex128), 0.8)
+    with pytest.raises(ValueError, match='TimeStretch expects a rank-4 input'):
+        backend.phase_vocoder(np.zeros((9, 129, 1), np.complex128), 0.8)
+    with pytest.raises(TypeError, match='TimeStretch expects a complex spectrogram'):
+        kapre.TimeStretch(0.8)(np.zeros((1, 9, 129, 1), np.float64))
+    with pytest.raises(ValueError, match='TimeStretch expects a rank-4 input'):
+        kapre.TimeStretch(0.8)(np.zeros((9, 129, 1), np.float64))
