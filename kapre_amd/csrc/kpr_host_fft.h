@@ -70,6 +70,8 @@ static void build_bluestein(int n_fft, std::vector<float2>& h) {
 }
 
 // forward DFT matrix [n_fft rows n][2K cols]: col 2k = cos(2 pi k n/N), col 2k+1 = -sin(...)
+// A sine whose exact value is 0 (k n mod N = 0 or N/2: the DC column, and the Nyquist column of an even N) is stored as 0, not as
+// (float)sin(pi) = 1.2e-16: the imaginary parts of the DC and Nyquist bins of a real frame are then exact zeros, as rfft's are.
 static void build_dft_fwd(int n_fft, std::vector<float>& h) {
     const int K = n_fft / 2 + 1;
     h.resize((size_t)n_fft * 2 * K);
@@ -78,7 +80,7 @@ static void build_dft_fwd(int n_fft, std::vector<float>& h) {
             long long kn = ((long long)k * n) % n_fft;     // exact angle reduction
             double a = 2.0 * M_PI * (double)kn / (double)n_fft;
             h[(size_t)n * 2 * K + 2 * k] = (float)std::cos(a);
-            h[(size_t)n * 2 * K + 2 * k + 1] = (float)(-std::sin(a));
+            h[(size_t)n * 2 * K + 2 * k + 1] = (2 * kn) % n_fft == 0 ? 0.0f : (float)(-std::sin(a));
         }
 }
 
@@ -94,7 +96,7 @@ static void build_dft_inv(int n_fft, std::vector<float>& h) {
             long long kn = ((long long)k * n) % n_fft;
             double a = 2.0 * M_PI * (double)kn / (double)n_fft;
             h[(size_t)(2 * k) * n_fft + n] = (float)(ck * std::cos(a));
-            h[(size_t)(2 * k + 1) * n_fft + n] = edge ? 0.0f : (float)(-ck * std::sin(a));
+            h[(size_t)(2 * k + 1) * n_fft + n] = (edge || (2 * kn) % n_fft == 0) ? 0.0f : (float)(-ck * std::sin(a));
         }
     }
 }
