@@ -600,6 +600,31 @@ int kpr_resample_plan(int n_phases, int n_taps, int step, int* outputs_per_tile)
 int kpr_resample_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout, const float* table_dev,
                      const int32_t* first_dev, int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream);
 
+/* ---- Resample without a table: any pair of rates, backend.resample(method='direct'), kapre_amd.signal.PitchShift ------
+ * The same h and the same outputs as the block above, with the taps computed on the device where they are used: no table, no
+ * phase count, nothing cached or allocated.  With the rates reduced by their gcd, L = lowpass_filter_width:
+ *   out[i] = s sum_j in[j] w(c (j P - i Q)),  in[j] = 0 outside 0 .. in_len - 1
+ *   w(t)   = sinc(t) cos^2(pi t / (2 L)) for |t| < L, else 0;  c = rolloff / max(orig, new);  s = rolloff min(orig, new) / orig
+ * forward (adjoint = 0): (P, Q) = (new, orig); adjoint (1): (orig, new).  The position i Q = a P + r of an output is exact 64-bit
+ * integer arithmetic; only r / P becomes a float.  Every output sums a window of n_taps = 2 ceil(L max / (rolloff P)) inputs
+ * from in[a - n_taps / 2 + 1] on, which holds its support and at most one input more at either end (tap exactly 0).
+ * kpr_resample_direct_plan is host only and touches no device.
+ *  _plan:  *n_taps as above, *outputs_per_tile = the consecutive outputs of one signal that a workgroup's staged input span
+ *          serves: tile seams for tests.  Supported: n_taps <= 128, else KPR_E_UNSUPPORTED (the text names the tap count);
+ *          rates <= 0, lowpass_filter_width < 1, rolloff outside (0, 1], adjoint outside 0 / 1: KPR_E_BADARG.
+ *  _f32:   x: float32 (batch, in_len, channels) [LAST] or (batch, channels, in_len) [FIRST]; out: the same with out_len, a free
+ *          argument >= 0 (forward: ceil(new in_len / orig) is the natural length; an index past it is the same sum: the filter's
+ *          tail, then +0.0; adjoint: the forward's input length).  One launch.  A tap is a float32 function of (i, k, the rates)
+ *          alone and the sum of an output runs over k in ascending order in float32 FMAs: the same inputs give the same bits,
+ *          whatever the batch position, layout or channel count (no atomics).  4-byte aligned pointers; x and out must not
+ *          overlap; 2^30 elements or more per signal (per batch item for LAST): KPR_E_UNSUPPORTED.
+ *          batch == 0 or out_len == 0: returns 0, launches nothing. */
+int kpr_resample_direct_plan(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint,
+                             int* n_taps, int* outputs_per_tile);
+int kpr_resample_direct_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout,
+                            int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint,
+                            int64_t out_len, float* out, kpr_stream_t stream);
+
 /* ---- Griffin-Lim: magnitude spectrogram -> waveform, kapre_amd.time_frequency.GriffinLim ------------------------------
  * Phase reconstruction by alternating projections (Griffin & Lim 1984) with the momentum term of the fast variant (Perraudin,
  * Balazs & Sondergaard 2013), as librosa.griffinlim and torchaudio's GriffinLim run it, on this library's own transforms:

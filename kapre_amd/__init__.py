@@ -29,7 +29,7 @@ from .time_frequency import (
 )
 
 from . import signal
-from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve, PitchShift
 
 from . import augmentation
 from .augmentation import SpecAugment, ChannelSwap, Reverb, AddNoise
@@ -104,6 +104,7 @@ __all__ = [
     'MuLawDecoding',
     'LogmelToMFCC',
     'Resample',
+    'PitchShift',
     'LFilter',
     'Preemphasis',
     'Deemphasis',

@@ -190,6 +190,11 @@ EXPORTS = {
     "kpr_resample_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_resample_direct_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "kpr_resample_direct_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     # Griffin-Lim (kapre_amd/time_frequency.py)
     "kpr_griffin_lim_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "kpr_gl_project_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
@@ -909,6 +914,30 @@ def resample(x, fmt, plan: ResamplePlan, out_len: int):
     out = torch.empty(shape_of(fmt, b, c, int(out_len)), dtype=torch.float32, device=x.device)
     _call("kpr_resample_f32", x.device, ptr(x), b, c, t, layout(fmt), ptr(plan.table), ptr(plan.first), plan.n_phases,
           plan.n_taps, plan.step, int(out_len), ptr(out))
+    return out
+
+
+def resample_direct_plan(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint: bool):
+    """(n_taps, outputs_per_tile) of one direction of the table-free conversion (host only).  ``ValueError`` naming the tap
+    count when the library does not support it, ``RuntimeError`` for any other failure."""
+    n, tile = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().kpr_resample_direct_plan(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff),
+                                        int(bool(adjoint)), ctypes.byref(n), ctypes.byref(tile))
+    if rc == E_UNSUPPORTED:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_resample_direct_plan")
+    return n.value, tile.value
+
+
+def resample_direct(x, fmt, params, adjoint: bool, out_len: int):
+    """The table-free conversion ``params`` = (orig_freq, new_freq, lowpass_filter_width, rolloff) of the float32 waveform
+    ``x`` along time, or with ``adjoint`` its adjoint: ``out_len`` samples per signal, whatever the natural length is."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    out = torch.empty(shape_of(fmt, b, c, int(out_len)), dtype=torch.float32, device=x.device)
+    orig_freq, new_freq, width, rolloff = params
+    _call("kpr_resample_direct_f32", x.device, ptr(x), b, c, t, layout(fmt), int(orig_freq), int(new_freq), int(width),
+          float(rolloff), int(bool(adjoint)), int(out_len), ptr(out))
     return out
 
 

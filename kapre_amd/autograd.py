@@ -412,6 +412,21 @@ def _functions():
             g = g.contiguous().to(torch.float32)
             return _ffi.resample(g, ctx.data_format, ctx.adjoint_plan, ctx.in_len), None, None, None, None
 
+    class ResampleDirectFn(torch.autograd.Function):
+        """y = R x with the taps computed on the device, ``out_len`` outputs: backward = the same launch with ``adjoint=1``
+        and the input's length."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, params, out_len):
+            ctx.data_format, ctx.params = data_format, params
+            ctx.in_len = _ffi.dims_of(x.shape, data_format)[2]
+            return _ffi.resample_direct(x.detach(), data_format, params, False, out_len)
+
+        @staticmethod
+        def backward(ctx, g):
+            g = g.contiguous().to(torch.float32)
+            return _ffi.resample_direct(g, ctx.data_format, ctx.params, True, ctx.in_len), None, None, None
+
     class LFilterFn(torch.autograd.Function):
         """y = F x, a cascade of biquad sections, each a linear map whose adjoint is the same section run in the other
         direction: backward = the sections in reverse order, each one launch sequence of the forward kernel with ``reverse``
@@ -482,7 +497,8 @@ def _functions():
 
     _FN = dict(add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
-               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn)
+               mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn,
+               resample_direct=ResampleDirectFn)
     return _FN
 
 
@@ -555,6 +571,10 @@ def cmvn(x, data_format, norm_vars, eps):
 
 def resample(x, data_format, forward_plan, adjoint_plan, out_len):
     return _functions()['resample'].apply(x, data_format, forward_plan, adjoint_plan, out_len)
+
+
+def resample_direct(x, data_format, params, out_len):
+    return _functions()['resample_direct'].apply(x, data_format, params, out_len)
 
 
 def lfilter(x, data_format, plan):

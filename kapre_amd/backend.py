@@ -489,24 +489,62 @@ def resample_length(t, orig_freq: int, new_freq: int):
 
 
 _RESAMPLE_SUPPORTED = set()          # parameter tuples whose tables kpr_resample_table_size has accepted
+_RESAMPLE_DIRECT_SUPPORTED = set()   # parameter tuples whose tap counts kpr_resample_direct_plan has accepted
+RESAMPLE_METHODS = ('polyphase', 'direct')
 
 
-def _resample_run(x, params, fmt):
-    """``x`` (rank 3) through the conversion ``params`` = resample_parameters(...); ``fmt`` is resolved."""
+def resample_method(method, length=None):
+    """Validated (method, length): ``method`` is 'polyphase' (the table kernel) or 'direct' (taps computed on the device, any
+    pair of rates); ``length``, for 'direct' only, is ``None`` or an integer >= 0 that replaces the natural output length
+    (``ValueError``)."""
+    if method not in RESAMPLE_METHODS:
+        raise ValueError("resample: method must be 'polyphase' or 'direct', got %r" % (method,))
+    if length is not None:
+        if method != 'direct':
+            raise ValueError("resample: length is for method='direct' only, got method=%r" % (method,))
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+            raise ValueError('resample: length must be None or an integer >= 0, got %r' % (length,))
+        length = int(length)
+    return method, length
+
+
+def resample_supported(params, method):
+    """``ValueError`` for a conversion that ``method`` does not support (an O(n_phases) walk on the host for 'polyphase', a
+    formula for 'direct'): once per conversion."""
+    seen = _RESAMPLE_DIRECT_SUPPORTED if method == 'direct' else _RESAMPLE_SUPPORTED
+    if params in seen or (method != 'direct' and params[0] == params[1]):
+        return
+    for adjoint in (False, True):
+        if method == 'direct':
+            _ffi.resample_direct_plan(*params, adjoint)
+        else:
+            _ffi.resample_table_size(*params, adjoint)
+    seen.add(params)
+
+
+def _resample_run(x, params, fmt, method='polyphase', length=None):
+    """``x`` (rank 3) through the conversion ``params`` = resample_parameters(...); ``fmt`` is resolved, ``method`` and
+    ``length`` are validated."""
     from . import autograd
     autograd.refuse(x, 3, 'resample expects a rank-3 waveform batch, got shape %s', TypeError,
                     'resample has float32 kernels only; got a float64 input (cast it to float32)')
-    if params[0] == params[1]:
+    t = _ffi.dims_of(x.shape, fmt)[2]
+    if params[0] == params[1] and (length is None or length == t):
         return x                                                     # nothing to convert, nothing launched
     x, grad = autograd.to_device(x, 'float32')
+    out_len = resample_length(t, params[0], params[1]) if length is None else length
+    if method == 'direct':
+        if grad:
+            return autograd.resample_direct(x, fmt, params, out_len)
+        return _ffi.resample_direct(x, fmt, params, False, out_len)
     forward, adjoint = _ffi.resample_plans(*params, x.device)
-    out_len = resample_length(_ffi.dims_of(x.shape, fmt)[2], params[0], params[1])
     if grad:
         return autograd.resample(x, fmt, forward, adjoint, out_len)
     return _ffi.resample(x, fmt, forward, out_len)
 
 
-def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default'):
+def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default', method='polyphase',
+             length=None):
     """Sample-rate conversion of a waveform batch on the GPU by the rational ratio new_freq / orig_freq: band-limited
     interpolation with a Hann-windowed sinc (the "sinc_interp_hann" method).  (b, time, ch) for ``channels_last``,
     (b, ch, time) for ``channels_first``; float32 out with ceil(new_freq time / orig_freq) samples.
@@ -514,17 +552,102 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_
         h(tau) = (base / orig) sinc(base tau) cos^2(pi base tau / (2 L)) for |base tau| < L,   y[m] = sum_n x[n] h(n / orig - m / new)
 
     with the rates reduced by their gcd, base = rolloff min(orig, new), L = lowpass_filter_width.  One kernel launch; a
-    tensor that ``requires_grad`` gets a ``grad_fn`` whose backward is one launch of the same kernel with the adjoint table.
-    ``orig_freq == new_freq`` returns ``x`` itself.  ``ValueError`` for a ratio whose polyphase table the library does not
-    support (more than 128 taps or 1 MiB), ``TypeError`` for a float64 input."""
+    tensor that ``requires_grad`` gets a ``grad_fn`` whose backward is one launch of the same kernel in its adjoint form.
+    ``orig_freq == new_freq`` returns ``x`` itself (with ``length`` None or the input's).  ``TypeError`` for a float64 input.
+
+    ``method='polyphase'`` reads a table of new / gcd rows: ``ValueError`` for a ratio whose table the library does not
+    support (more than 128 taps or 1 MiB).  ``method='direct'`` computes the taps on the device from an exact integer
+    position: any pair of rates below 2^31 whose support is at most 128 taps, the same outputs up to float32 rounding
+    (DESIGN 4.20), at several times the arithmetic.  ``length`` (``'direct'`` only) replaces the natural output length:
+    an index past it is the same sum -- the filter's tail, then exact zeros."""
     validate_data_format_str(data_format)
     params = resample_parameters(orig_freq, new_freq, lowpass_filter_width, rolloff)
-    if params[0] != params[1] and params not in _RESAMPLE_SUPPORTED:
-        for adjoint in (False, True):                      # an O(n_phases) walk on the host: once per conversion
-            _ffi.resample_table_size(*params, adjoint)
-        _RESAMPLE_SUPPORTED.add(params)
+    method, length = resample_method(method, length)
+    resample_supported(params, method)
     fmt = resolve_data_format(data_format)
-    return _resample_run(x, params, fmt)
+    return _resample_run(x, params, fmt, method, length)
+
+
+# --------------------------------------------------------------------------------------
+# pitch shifting
+# --------------------------------------------------------------------------------------
+def pitch_shift_parameters(sample_rate, n_steps, bins_per_octave=12):
+    """(rate, orig_freq) of a shift by ``n_steps`` steps of 1 / ``bins_per_octave`` octave at ``sample_rate``:
+    rate = 2 ** (-n_steps / bins_per_octave) in float64, the factor of the time stretch, and orig_freq =
+    int(sample_rate / rate), the rate the stretched signal is resampled from (``torchaudio``'s truncation).  ``n_steps`` is a
+    finite number (a float is allowed, a bool is not); ``n_steps != 0`` with orig_freq == sample_rate is a ``ValueError``: the
+    shift is too small to represent at that rate."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or sample_rate <= 0:
+        raise ValueError('PitchShift: sample_rate must be a positive integer, got %r' % (sample_rate,))
+    if (isinstance(bins_per_octave, bool) or not isinstance(bins_per_octave, (int, np.integer)) or bins_per_octave < 1):
+        raise ValueError('PitchShift: bins_per_octave must be an integer >= 1, got %r' % (bins_per_octave,))
+    if (isinstance(n_steps, (bool, np.bool_)) or not isinstance(n_steps, (int, float, np.integer, np.floating))
+            or not np.isfinite(float(n_steps))):
+        raise ValueError('PitchShift: n_steps must be a finite number, got %r' % (n_steps,))
+    rate = 2.0 ** (-float(n_steps) / int(bins_per_octave))
+    if not (np.isfinite(rate) and rate > 0.0 and int(sample_rate) / rate < 2.0 ** 31):
+        raise ValueError('PitchShift: n_steps = %r at %d Hz gives no rate below 2^31' % (n_steps, sample_rate))
+    orig_freq = int(int(sample_rate) / rate)
+    if orig_freq < 1:
+        raise ValueError('PitchShift: n_steps = %r at %d Hz gives no positive rate' % (n_steps, sample_rate))
+    if float(n_steps) != 0.0 and orig_freq == int(sample_rate):
+        raise ValueError('PitchShift: n_steps = %r is too small a shift to represent at %d Hz' % (n_steps, sample_rate))
+    return rate, orig_freq
+
+
+def _pitch_shift_run(x, stretch, n_fft, params, fmt):
+    """``x`` through the time stretch ``stretch`` (``get_time_stretch_layer`` of ``n_fft``; a callable that returns it is
+    called when it is needed) and the table-free resampler ``params`` back to the input's length; ``params`` None is the shift
+    by zero steps."""
+    import torch
+    from . import autograd
+    autograd.refuse(x, 3, 'PitchShift expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'PitchShift has float32 kernels only; got a float64 input (cast it to float32)')
+    if params is None:
+        return x                                                     # nothing to shift, nothing launched
+    t = _ffi.dims_of(x.shape, fmt)[2]
+    if t < n_fft:
+        raise ValueError('PitchShift: %d samples give no frame of n_fft = %d' % (t, n_fft))
+    x = _ffi.as_device(x.detach() if isinstance(x, torch.Tensor) else x, torch.float32)
+    from .keras_shim import Layer
+    if not isinstance(stretch, Layer):
+        stretch = stretch()
+    return _ffi.resample_direct(stretch(x).detach().contiguous(), fmt, params, False, t)
+
+
+_PITCH_SHIFT_CHAINS = {}             # (rate, n_fft, hop_length, data_format) -> get_time_stretch_layer(...), the last 16 used
+
+
+def _pitch_shift_chain(rate, n_fft, hop_length, data_format):
+    """the time-stretch chain of ``pitch_shift``, built once per parameter set (its layers keep their device constants)"""
+    from . import composed
+    key = (rate, n_fft, hop_length, data_format)
+    chain = _PITCH_SHIFT_CHAINS.pop(key, None)
+    if chain is None:
+        chain = composed.get_time_stretch_layer(rate, n_fft=n_fft, hop_length=hop_length, input_data_format=data_format)
+        while len(_PITCH_SHIFT_CHAINS) >= 16:
+            _PITCH_SHIFT_CHAINS.pop(next(iter(_PITCH_SHIFT_CHAINS)))
+    _PITCH_SHIFT_CHAINS[key] = chain                                 # (most recently used last)
+    return chain
+
+
+def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=2048, hop_length=None, data_format='default'):
+    """Pitch shift of a waveform batch by ``n_steps`` steps of 1 / ``bins_per_octave`` octave without a change of duration
+    (``kapre_amd.PitchShift`` as a function; ``torchaudio.transforms.PitchShift``, ``librosa.effects.pitch_shift``):
+    ``get_time_stretch_layer(rate, n_fft, hop_length)`` with rate = 2 ** (-n_steps / bins_per_octave), then
+    ``resample(orig_freq -> sample_rate, method='direct', length=time)`` with orig_freq = int(sample_rate / rate).  The
+    output has the input's shape and carries no ``grad_fn`` (the time stretch has none).  ``n_steps = 0`` returns ``x``
+    itself.  ``ValueError`` for fewer than ``n_fft`` samples, ``TypeError`` for a float64 input."""
+    validate_data_format_str(data_format)
+    rate, orig_freq = pitch_shift_parameters(sample_rate, n_steps, bins_per_octave)
+    fmt = resolve_data_format(data_format)
+    params = None
+    if float(n_steps) != 0.0:
+        params = resample_parameters(orig_freq, int(sample_rate), 6, 0.99)
+        resample_supported(params, 'direct')
+    if isinstance(n_fft, bool) or not isinstance(n_fft, (int, np.integer)) or n_fft < 1:
+        raise ValueError('PitchShift: n_fft must be a positive integer, got %r' % (n_fft,))
+    return _pitch_shift_run(x, lambda: _pitch_shift_chain(rate, int(n_fft), hop_length, data_format), int(n_fft), params, fmt)
 
 
 # --------------------------------------------------------------------------------------

@@ -37,6 +37,8 @@
 //                             registers up to 128 frames, two sweeps beyond
 //   kpr_resample_kernels.h    rational sample-rate conversion (signal.Resample): a polyphase gather over a staged input span,
 //                             forward and adjoint in one kernel
+//   kpr_resample_direct_kernels.h the same conversion without a table: taps computed per output from an exact integer position,
+//                             any pair of rates (backend.resample(method='direct'), signal.PitchShift)
 //   kpr_griffin_lim_kernels.h Griffin-Lim phase reconstruction: the initial spectrum (zero or Philox phase), the projection onto the
 //                             given magnitude with the momentum term and the convergence sums, the per-item convergence figure
 //   kpr_time_stretch_kernels.h phase-vocoder time stretching of a complex spectrogram: a running sum of 32-bit angle words along time
@@ -99,6 +101,7 @@
 #include "kpr_pcen_kernels.h"
 #include "kpr_cmvn_kernels.h"
 #include "kpr_resample_kernels.h"
+#include "kpr_resample_direct_kernels.h"
 #include "kpr_griffin_lim_kernels.h"
 #include "kpr_time_stretch_kernels.h"
 #include "kpr_hpss_kernels.h"
@@ -509,6 +512,23 @@ int kpr_resample_f32(const float* x, int64_t batch, int channels, int64_t in_len
                      const int32_t* first_dev, int n_phases, int n_taps, int step, int64_t out_len, float* out, kpr_stream_t stream) {
     if (int e = api_enter()) return e;
     return run_resample(x, batch, channels, in_len, layout, table_dev, first_dev, n_phases, n_taps, step, out_len, out, stream);
+}
+
+/* ---- Resample without a table (kpr_resample_direct_kernels.h) ------------------------------------ */
+int kpr_resample_direct_plan(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint, int* n_taps,
+                             int* outputs_per_tile) {
+    ResampleDirectShape r;
+    if (!n_taps || !outputs_per_tile) return fail(KPR_E_BADARG, "n_taps / outputs_per_tile must not be NULL");
+    if (int e = resample_direct_shape(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint, &r)) return e;
+    *n_taps = r.n_taps;
+    *outputs_per_tile = r.threads * r.per_lane;
+    return 0;
+}
+int kpr_resample_direct_f32(const float* x, int64_t batch, int channels, int64_t in_len, int layout, int orig_freq, int new_freq,
+                            int lowpass_filter_width, double rolloff, int adjoint, int64_t out_len, float* out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_resample_direct(x, batch, channels, in_len, layout, orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint,
+                               out_len, out, stream);
 }
 
 /* ---- Griffin-Lim (kpr_griffin_lim_kernels.h) ---------------------------------------------------- */

@@ -2,7 +2,7 @@
 // Delta), augmentation, companding, PCEN, CMVN, Resample, TimeStretch and HPSS entry points, forward and backward, and the host-only
 // frame count and resample table (kpr_misc_kernels.h, kpr_generic_kernels.h, kpr_grad_kernels.h, kpr_signal_kernels.h,
 // kpr_augment_kernels.h, kpr_companding_kernels.h, kpr_pcen_kernels.h, kpr_cmvn_kernels.h, kpr_resample_kernels.h,
-// kpr_time_stretch_kernels.h, kpr_hpss_kernels.h).  No body restarts the launch log or reads the status word: the entry points do.
+// kpr_resample_direct_kernels.h, kpr_time_stretch_kernels.h, kpr_hpss_kernels.h).  No body restarts the launch log or reads the status word: the entry points do.
 // The three time-tiled launchers (PCEN, CMVN, TimeStretch) take their launch shape from col_launch (kpr_host.h; device side: kpr_cols.h).
 // Part of the single translation unit kapre_hip.hip (included there after kpr_host_mel.h; not stand-alone).
 #pragma once
@@ -468,6 +468,102 @@ static int run_resample(const float* x, int64_t batch, int channels, int64_t in_
                 "(%d outputs), %d block groups, %d lanes\n", nch, grid, lds, n_phases, n_taps, step, pl.pt, pl.nb, pl.nb * n_phases, pl.ng, pl.threads);
     with_vec<2>(nch == 2, [&](auto n) { hipLaunchKernelGGL(k_resample<n>, dim3((unsigned)grid), dim3(pl.threads), lds, (hipStream_t)stream, a); });
     return launch_check("k_resample", nch);
+}
+
+// ---- Resample without a table (kpr_resample_direct_kernels.h): the window, the tile, the launch ----
+// The same h as above, evaluated per tap on the device.  Every output sums the window of n_taps = 2 H inputs,
+// H = ceil(U / P), U = L max / rolloff: it holds the support |j P - i Q| < U of every output.  No limit on the number of phases.
+struct ResampleDirectShape {
+    int P, Q, H, n_taps;
+    int orig, fnew, L;
+    double rolloff;
+    int threads, per_lane, span;        // the tile: threads x per_lane outputs over `span` staged inputs per channel
+};
+
+static int resample_direct_shape(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int adjoint,
+                                 ResampleDirectShape* r) {
+    if (orig_freq <= 0 || new_freq <= 0)
+        return fail(KPR_E_BADARG, "orig_freq and new_freq must be positive, got %d and %d", orig_freq, new_freq);
+    if (lowpass_filter_width < 1) return fail(KPR_E_BADARG, "lowpass_filter_width must be at least 1, got %d", lowpass_filter_width);
+    if (!(rolloff > 0.0 && rolloff <= 1.0)) return fail(KPR_E_BADARG, "rolloff must lie in (0, 1], got %g", rolloff);
+    if ((unsigned)adjoint > 1u) return fail(KPR_E_BADARG, "adjoint must be 0 or 1, got %d", adjoint);
+    int a = orig_freq, b = new_freq;
+    while (b) { const int t = a % b; a = b; b = t; }
+    r->orig = orig_freq / a;
+    r->fnew = new_freq / a;
+    r->L = lowpass_filter_width;
+    r->rolloff = rolloff;
+    r->P = adjoint ? r->orig : r->fnew;
+    r->Q = adjoint ? r->fnew : r->orig;
+    const double h = std::ceil((double)lowpass_filter_width * (double)std::max(r->orig, r->fnew) / rolloff / (double)r->P);
+    if (2.0 * h > (double)kRdMaxTaps)
+        return fail(KPR_E_UNSUPPORTED, "resample %d -> %d%s without a table: a support of %.0f taps; supported are at most %d taps",
+                    orig_freq, new_freq, adjoint ? " (adjoint)" : "", 2.0 * h, kRdMaxTaps);
+    r->H = (int)h;
+    r->n_taps = 2 * r->H;
+    // the largest tile whose span fits: (tile - 1) Q div P + 1 + n_taps staged inputs (Q / P <= 64 when the taps fit)
+    auto span_of = [&](int tile) -> long long { return ((long long)(tile - 1) * r->Q) / r->P + 1 + r->n_taps; };
+    r->threads = kRdMaxThreads;
+    r->per_lane = kRdMaxPerLane;
+    while (r->per_lane > 1 && span_of(r->threads * r->per_lane) > kRdLdsWords) --r->per_lane;
+    while (r->threads > 64 && span_of(r->threads * r->per_lane) > kRdLdsWords) r->threads /= 2;
+    r->span = (int)span_of(r->threads * r->per_lane);
+    if (r->span > kRdLdsWords)                                           // (cannot happen: 63 * 64 + 1 + 128 words)
+        return fail(KPR_E_UNSUPPORTED, "resample %d -> %d without a table: a tile of %d staged inputs", orig_freq, new_freq, r->span);
+    return 0;
+}
+
+static int run_resample_direct(const float* x, int64_t batch, int channels, int64_t in_len, int layout, int orig_freq, int new_freq,
+                               int lowpass_filter_width, double rolloff, int adjoint, int64_t out_len, float* out, kpr_stream_t stream) {
+    if (batch < 0 || channels <= 0 || in_len < 0 || out_len < 0 || (unsigned)layout > 1u)
+        return fail(KPR_E_BADARG, "bad batch/channels/in_len/out_len/layout");
+    ResampleDirectShape r;
+    if (int e = resample_direct_shape(orig_freq, new_freq, lowpass_filter_width, rolloff, adjoint, &r)) return e;
+    // one signal is addressed with 32-bit element offsets (as kpr_resample_f32); compared without a product that could overflow
+    const bool cl = layout == KPR_CHANNELS_LAST;
+    const long long reach = cl ? channels : 1;
+    const long long most = ((1LL << 30) - 1) / reach;                    // len * reach < 2^30  <=>  len <= most
+    if (in_len > most || out_len > most)
+        return fail(KPR_E_UNSUPPORTED, "resample: %lld -> %lld samples x %d channels: 2^30 elements or more per signal are not supported",
+                    (long long)in_len, (long long)out_len, channels);
+    if (batch == 0 || out_len == 0) return 0;
+    if ((!x && in_len > 0) || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
+    if ((((uintptr_t)x) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "the pointers must be 4-byte aligned");
+    if (ranges_overlap(x, (uintptr_t)batch * channels * in_len * 4, out, (uintptr_t)batch * channels * out_len * 4))
+        return fail(KPR_E_BADARG, "x and out overlap");
+    const int nch = cl && channels % 2 == 0 ? 2 : 1;
+    const int mx = std::max(r.orig, r.fnew), mn = std::min(r.orig, r.fnew);
+    ResampleDirectArgs a;
+    a.x = x; a.out = out;
+    a.P = r.P; a.Q = r.Q; a.n_taps = r.n_taps; a.H = r.H;
+    a.in_len = (int)in_len; a.out_len = (int)out_len;
+    a.estride = cl ? channels : 1;
+    a.groups = channels / nch;
+    a.in_item = (long long)channels * in_len; a.out_item = (long long)channels * out_len;
+    a.in_group = cl ? nch : in_len; a.out_group = cl ? nch : out_len;
+    a.per_lane = r.per_lane;
+    a.tile = r.threads * r.per_lane;
+    const long long tiles = (out_len + a.tile - 1) / a.tile;
+    a.tiles_per_signal = (int)tiles;
+    const long long stepq = (long long)r.threads * r.Q;
+    a.step_a = (int)(stepq / r.P);
+    a.step_r = (int)(stepq % r.P);
+    a.lds_stride = r.span;
+    a.inv_p = 1.0 / (double)r.P;
+    a.beta = (float)(rolloff * (double)r.P / (double)mx);
+    a.scale = (float)(rolloff * (double)mn / (double)r.orig);
+    a.inv_2l = (float)(1.0 / (2.0 * (double)r.L));
+    a.lim = (float)r.L;
+    const long long grid = tiles * batch * a.groups;
+    if (grid > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "resample: too many tiles (%lld)", grid);
+    const size_t lds = (size_t)nch * r.span * sizeof(float);
+    if (opt(OPT_VERBOSE))
+        fprintf(stderr, "[kapre_hip] k_resample_direct<%d>: grid %lld, lds %zu B, %d / %d, %d taps; tile %d lanes x %d outputs, "
+                "%d staged inputs\n", nch, grid, lds, r.P, r.Q, r.n_taps, r.threads, r.per_lane, r.span);
+    with_vec<2>(nch == 2, [&](auto n) {
+        hipLaunchKernelGGL(k_resample_direct<n>, dim3((unsigned)grid), dim3(r.threads), lds, (hipStream_t)stream, a);
+    });
+    return launch_check("k_resample_direct", nch);
 }
 
 // ---- TimeStretch (kpr_time_stretch_kernels.h): argument checks and the one launch of the phase vocoder ----

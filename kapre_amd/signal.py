@@ -5,8 +5,8 @@ libkapre_hip.so (kpr_frame_f32 / kpr_energy_f32 / kpr_apply_filterbank_f32 with 
 MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.mu_law_encoding / mu_law_decoding
 (kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32).  Resample has no counterpart in the reference: it is
 the step in front of every front end (kpr_resample_f32).  Neither have LFilter, Preemphasis and Deemphasis: biquad filtering of
-the waveform itself (kpr_lfilter_f32), and Convolve: convolution with a fixed impulse response (kpr_stft_f32, kpr_spec_fir_c64,
-kpr_istft_f32)."""
+the waveform itself (kpr_lfilter_f32), Convolve: convolution with a fixed impulse response (kpr_stft_f32, kpr_spec_fir_c64,
+kpr_istft_f32), and PitchShift: a time stretch and the table-free resampler (kpr_resample_direct_f32)."""
 import math
 
 import numpy as np
@@ -16,7 +16,7 @@ from .backend import _CH_FIRST_STR, _CH_LAST_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample', 'LFilter', 'Preemphasis',
-           'Deemphasis', 'Convolve']
+           'Deemphasis', 'Convolve', 'PitchShift']
 
 
 def _as_waveform(x):
@@ -245,24 +245,26 @@ class LogmelToMFCC(Layer):
 
 @register_keras_serializable(package='Kapre')
 class Resample(Layer):
-    """Sample-rate conversion from ``orig_freq`` to ``new_freq`` (positive integers; any rational ratio whose polyphase table
-    has at most 128 taps and 1 MiB -- every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz does): band-limited
-    interpolation with a Hann-windowed sinc of ``lowpass_filter_width`` zero crossings a side and cutoff ``rolloff`` times the
-    lower Nyquist frequency (``backend.resample``).
+    """Sample-rate conversion from ``orig_freq`` to ``new_freq`` (positive integers): band-limited interpolation with a
+    Hann-windowed sinc of ``lowpass_filter_width`` zero crossings a side and cutoff ``rolloff`` times the lower Nyquist
+    frequency (``backend.resample``).  ``method='polyphase'`` reads a table: any rational ratio whose polyphase table has at
+    most 128 taps and 1 MiB -- every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz does.  ``method='direct'``
+    computes the taps on the device: any pair of rates below 2^31 whose support is at most 128 taps, the same outputs up to
+    float32 rounding, at several times the arithmetic.
 
     (batch, time, ch) -> (batch, ceil(new_freq time / orig_freq), ch) for ``channels_last``;
     (batch, ch, time) -> (batch, ch, ceil(new_freq time / orig_freq)) for ``channels_first``.  numpy or torch, float32 (a
     float64 input raises ``TypeError``).  One launch; differentiable (one more launch of the same kernel).  ``orig_freq ==
     new_freq`` returns its input."""
 
-    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default', **kwargs):
+    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, data_format='default', method='polyphase',
+                 **kwargs):
         super(Resample, self).__init__(**kwargs)
         backend.validate_data_format_str(data_format)
         self._params = backend.resample_parameters(orig_freq, new_freq, lowpass_filter_width, rolloff)
         self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff = self._params
-        if self.orig_freq != self.new_freq:
-            for adjoint in (False, True):                    # ValueError for a table the library does not support
-                _ffi.resample_table_size(*self._params, adjoint)
+        self.method, _ = backend.resample_method(method)
+        backend.resample_supported(self._params, self.method)        # ValueError for a conversion the library does not support
         self.data_format_str = data_format
         self.data_format = backend.resolve_data_format(data_format)
         self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
@@ -273,13 +275,59 @@ class Resample(Layer):
         return _ffi.shape_of(self.data_format, b, c, backend.resample_length(t, self.orig_freq, self.new_freq))
 
     def call(self, x):
-        return backend._resample_run(x, self._params, self.data_format)
+        return backend._resample_run(x, self._params, self.data_format, self.method)
 
     def get_config(self):
         config = super(Resample, self).get_config()
         config.update({'orig_freq': self.orig_freq, 'new_freq': self.new_freq,
                        'lowpass_filter_width': self.lowpass_filter_width, 'rolloff': self.rolloff,
-                       'data_format': self.data_format_str})
+                       'data_format': self.data_format_str, 'method': self.method})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class PitchShift(Layer):
+    """Pitch shift by ``n_steps`` steps of 1 / ``bins_per_octave`` octave without a change of duration
+    (``torchaudio.transforms.PitchShift``, ``librosa.effects.pitch_shift``): ``get_time_stretch_layer(rate, n_fft,
+    hop_length)`` with rate = 2 ** (-n_steps / bins_per_octave) -- its windows, its edges --, then a resample from
+    orig_freq = int(sample_rate / rate) to ``sample_rate`` with the table-free kernel, cut or zero-extended to the input's
+    length inside that launch (``backend.pitch_shift``).  ``n_steps`` is any finite number, positive up, negative down; there
+    is one path and no step that raises for the size of a table.  ``hop_length`` defaults to ``n_fft // 4``.
+
+    (batch, time, ch) for ``channels_last``, (batch, ch, time) for ``channels_first``, any channel count; the output has the
+    input's shape.  numpy or torch, float32 (a float64 input raises ``TypeError``); fewer than ``n_fft`` samples raise
+    ``ValueError``.  ``n_steps = 0`` returns its input and launches nothing.  No gradient: ``TimeStretch`` carries none, so the
+    output is detached.  One step for the whole batch; a step drawn per item on the device would need per-item rates and
+    ragged lengths through the time stretch and the inverse STFT."""
+
+    def __init__(self, sample_rate, n_steps, bins_per_octave=12, n_fft=2048, hop_length=None, data_format='default', **kwargs):
+        from .composed import get_time_stretch_layer
+        super(PitchShift, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        self.rate, self.orig_freq = backend.pitch_shift_parameters(sample_rate, n_steps, bins_per_octave)
+        self.sample_rate, self.n_steps, self.bins_per_octave = int(sample_rate), n_steps, int(bins_per_octave)
+        self._params = None
+        if float(n_steps) != 0.0:
+            self._params = backend.resample_parameters(self.orig_freq, self.sample_rate, 6, 0.99)
+            backend.resample_supported(self._params, 'direct')
+        self.n_fft, self.hop_length = n_fft, hop_length
+        self._stretch = get_time_stretch_layer(self.rate, n_fft=n_fft, hop_length=hop_length, input_data_format=data_format,
+                                               name=self.name + '_stretch')
+        self.data_format_str = data_format
+        self.data_format = backend.resolve_data_format(data_format)
+        self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
+
+    def compute_output_shape(self, input_shape):
+        """the input's shape"""
+        return tuple(input_shape)
+
+    def call(self, x):
+        return backend._pitch_shift_run(x, self._stretch, self.n_fft, self._params, self.data_format)
+
+    def get_config(self):
+        config = super(PitchShift, self).get_config()
+        config.update({'sample_rate': self.sample_rate, 'n_steps': self.n_steps, 'bins_per_octave': self.bins_per_octave,
+                       'n_fft': self.n_fft, 'hop_length': self.hop_length, 'data_format': self.data_format_str})
         return config
 
 
