@@ -454,6 +454,11 @@ __global__ __launch_bounds__(64 * kStft3Waves, 4) void k_stft3(const float* __re
     }
 }
 
+// The phase of a finished bin in the epilogues of k_stft_big / k_stft_bs / k_stft_mr: atan2f with the sign of a zero real part
+// dropped (-0 + 0 = +0, every other x + 0 = x).  An all-zero frame leaves -0 in the bins whose last product had a negative
+// factor, and atan2f(+0, -0) is pi where the reference's angle of a zero bin is 0 (tests/test_tuned_fft_gate.py: zero input).
+KPR_DEV float bin_phase(f2 v) { return atan2f(v.y, v.x + 0.0f); }
+
 // ------------------------------------------------------------------------------------------
 // STFT for n_fft = 4096 / 8192 (NB = n_fft/2 = R * 1024 complex points, R = 2 / 4): one wave per
 // frame runs R sub-FFTs of 1024 points (decimation in time: sub-sequence r = points r, r + R, ...)
@@ -553,7 +558,7 @@ __global__ __launch_bounds__(R == 2 ? 256 : 128, 2) void k_stft_big(const float*
             for (int k = lane; k < K; k += 64) {
                 const f2 v = zrow[k];
                 out[(long long)k * ostride] = (mode == KPR_OUT_MAGNITUDE) ? __builtin_amdgcn_sqrtf(v.x * v.x + v.y * v.y)
-                                                                          : atan2f(v.y, v.x);
+                                                                          : bin_phase(v);
             }
         }
         KPR_LDS_FENCE_X();
@@ -660,7 +665,7 @@ __global__ __launch_bounds__(256, 2) void k_stft_bs(const float* __restrict__ x,
             if (k <= ncr) {
                 if (mode == KPR_OUT_COMPLEX) { stage[2 * k] = X.x; stage[2 * k + 1] = X.y; }
                 else stage[k] = (mode == KPR_OUT_MAGNITUDE) ? __builtin_amdgcn_sqrtf(X.x * X.x + X.y * X.y)
-                                                             : atan2f(X.y, X.x);
+                                                             : bin_phase(X);
             }
         }
         KPR_LDS_FENCE_R();          // (kpr_fft.h: the copy below reads other lanes' words)
@@ -812,7 +817,7 @@ __global__ __launch_bounds__(256, 3) void k_stft_mr(const float* __restrict__ x,
                 for (int k = lane; k < K; k += 64) {
                     const f2 v = src[k];
                     out[(long long)k * ostride] = (mode == KPR_OUT_MAGNITUDE) ? __builtin_amdgcn_sqrtf(v.x * v.x + v.y * v.y)
-                                                                              : atan2f(v.y, v.x);
+                                                                              : bin_phase(v);
                 }
             }
         }

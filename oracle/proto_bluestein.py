@@ -41,16 +41,18 @@ def tables(n_fft):
     return m, wt, bt, t
 
 
-def rfft_bluestein(x):
-    """x: (n_fft,) real (already windowed) -> (n_fft/2 + 1,) complex, following the device steps."""
+def rfft_bluestein(x, dtype=complex, fft=np.fft.fft):
+    """x: (n_fft,) real (already windowed) -> (n_fft/2 + 1,) complex, following the device steps.  dtype: the type the tables and
+    every value are held in; fft: the M-point transform (a float32 run passes complex64 and a transform that stays in it)."""
     n_fft = x.shape[0]
     ncr = n_fft // 2
     m, wt, bt, t = tables(n_fft)
-    z = np.zeros(m, dtype=complex)
+    wt, bt, t = wt.astype(dtype), bt.astype(dtype), t.astype(dtype)
+    z = np.zeros(m, dtype=dtype)
     z[:ncr] = x[0::2] + 1j * x[1::2]
     a = z * wt
-    big = np.fft.fft(a) * bt
-    c = np.conj(np.fft.fft(np.conj(big)))                 # unnormalised inverse (1/M is in bt)
+    big = fft(a) * bt
+    c = np.conj(fft(np.conj(big)))                        # unnormalised inverse (1/M is in bt)
     zz = c[:ncr] * wt[:ncr]                               # = Z / 2
     k = np.arange(ncr + 1)
     zk = zz[k % ncr]

@@ -58,16 +58,17 @@ def skew_exchange_indices(nc=1024):
 
 
 def _dft_small(v, sign):
-    """(R,) complex -> DFT along axis 0 (explicit; the device uses hard-coded butterflies)."""
+    """(R,) complex -> DFT along axis 0 (explicit; the device uses hard-coded butterflies).  In v's dtype."""
     r = v.shape[0]
     k = np.arange(r)
-    w = np.exp(sign * 2j * np.pi * np.outer(k, k) / r)
+    w = np.exp(sign * 2j * np.pi * np.outer(k, k) / r).astype(v.dtype)
     return w @ v
 
 
 def complex_fft_lanes(regs, nc, sign=-1):
     """regs: (L, 16) complex, regs[lane, m] = z[lane + L*m].  Returns the same layout holding
-    Z[lane + L*m] (sign=-1 forward, +1 unnormalised inverse)."""
+    Z[lane + L*m] (sign=-1 forward, +1 unnormalised inverse).  Every intermediate is held in regs' dtype (complex64: a
+    float32 run with twiddles rounded to float32)."""
     L = nc // P
     radices = radices_for(nc)
     ns = 1
@@ -75,13 +76,13 @@ def complex_fft_lanes(regs, nc, sign=-1):
     for pi, R in enumerate(radices):
         q_per = P // R                   # butterflies per lane
         new = np.empty_like(regs)
-        lds = np.zeros(nc, dtype=complex)
+        lds = np.zeros(nc, dtype=regs.dtype)
         for q in range(q_per):
             t = lanes + L * q            # butterfly ("thread") index, < nc/R
             # inputs in[t + (nc/R)*r] = slot m = q + (16/R)*r
             v = np.stack([regs[:, q + q_per * r] for r in range(R)])        # (R, L)
             kk = t % ns
-            tw = np.exp(sign * 2j * np.pi * np.outer(np.arange(R), kk) / (ns * R))
+            tw = np.exp(sign * 2j * np.pi * np.outer(np.arange(R), kk) / (ns * R)).astype(regs.dtype)
             v = _dft_small(v * tw, sign)
             base = (t // ns) * ns * R + kk
             last = (ns * R == nc)
@@ -205,7 +206,7 @@ def complex_fft_lanes_wide(regs, sign=-1):
         v = np.stack([regs[:, r] for r in range(R)]) if R == 16 else None
         if R == 16:
             kk = t % ns
-            tw = np.exp(sign * 2j * np.pi * np.outer(np.arange(R), kk) / (ns * R))
+            tw = np.exp(sign * 2j * np.pi * np.outer(np.arange(R), kk) / (ns * R)).astype(regs.dtype)
             v = _dft_small(v * tw, sign)
             for r in range(R):
                 lds[wide_write_addr(pi + 1, lanes, r)] = v[r]
