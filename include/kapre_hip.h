@@ -160,6 +160,9 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *                  longer items and smaller batches in two) | 1 = streamed for
  *                  every shape | 2 = resident wherever it applies (A/B runs, tests; results within the error bound of each other,
  *                  not bit-identical)
+ *   "yin_variant"  0 = automatic (default: kpr_yin_f32 shares the block sums of overlapping frames where hop divides win_length,
+ *                  kpr_yin_plan) | 1 = the direct form, every frame summed on its own, for every shape (A/B runs, tests; results
+ *                  within the error bound of each other, not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -826,6 +829,42 @@ int kpr_add_noise_f32(const float* x, int64_t batch, int channels, int64_t time,
 int kpr_add_noise_bwd_f32(const float* gy, const float* x, int64_t batch, int channels, int64_t time, int layout, const float* noise,
                           int n_noise, int64_t stride, const int32_t* lengths, const int32_t* table, const double* stats, float* gx,
                           double* stats_out, void* workspace, size_t workspace_bytes, kpr_stream_t stream);
+
+/* ---- YIN: fundamental-frequency (F0) tracking of a waveform, kapre_amd.signal.YIN ----------------------------------------
+ * de Cheveigne & Kawahara (2002) steps 1-5 as librosa.yin arranges them, on this library's frames (not centred).  Per series
+ * (batch item, channel) of `time` float32 samples:
+ *   framing     the frames of kpr_frame_count(time, frame_length, hop, pad_end); frame t = x[t hop ... t hop + frame_length), with
+ *               pad_end the samples past the end read as 0
+ *   lags        W = win_length; the caller hands tau_min = max(floor(sr / fmax), 1) and tau_hi = min(ceil(sr / fmin),
+ *               frame_length - W - 1)
+ *   difference  d(tau) = sum_{j < W} (x[j] - x[j + tau])^2 for tau = 0 ... tau_hi, float32, in this difference form: a sum of
+ *               non-negative terms in a fixed order, never energy minus twice the autocorrelation
+ *   CMND        c(tau) = sum_{k = 1 .. tau} d(k);  y(0) = 1;  y(tau) = d(tau) tau / c(tau), and 1 where c(tau) == 0 (a constant frame)
+ *   decision    on i in [tau_min, tau_hi]: i is a trough when i == tau_min and y[i] < y[i+1], or tau_min < i < tau_hi and
+ *               y[i] < y[i-1] and y[i] <= y[i+1]; tau_hi is never one.  tau* = the smallest trough with y < trough_threshold,
+ *               else the smallest index of the minimum of y over the range
+ *   refinement  a = (y+ - y0) + (y- - y0), b = (y+ - y-) 0.5 around tau*, every operation rounded to float32;
+ *               shift = -b / a if |b| < |a|, else 0; shift = 0 at tau* == tau_min and at tau* == tau_hi
+ *   outputs     f0 = (float)sample_rate / (float(tau*) + shift);  cmnd = y[tau*] (the caller's voicing test: cmnd < threshold)
+ *   non-finite  a frame one of whose d(tau), tau <= tau_hi, is NaN or infinite (a NaN / Inf sample among the W + tau_hi samples the
+ *               frame reads, or an overflow) gives NaN in both outputs (and in its curve); every other frame is bit for bit what
+ *               it is without that sample
+ * x: (batch, time, channels) [LAST] or (batch, channels, time) [FIRST]; f0, cmnd: float32 (batch, frames, channels) [LAST] or
+ * (batch, channels, frames) [FIRST]; want_curve (may be NULL; tests): y as (batch, channels, frames, tau_hi + 1) float32.
+ * One launch (k_yin), no atomics, no host reads, nothing allocated: the same inputs give the same bits; capturable.  Two forms
+ * (option "yin_variant"): shared -- where hop divides win_length into 2 ... 16 blocks the sums over blocks of hop samples are
+ * computed once per run of frames and d is the sum of a frame's blocks in ascending order -- and direct; they sum in different
+ * orders and agree within the error bound (2 W + tau_hi + 8) 2^-24 |y| of either, not bit for bit.
+ * Limits: frame_length <= 4096, 2 <= win_length <= frame_length - 3, hop >= 1, tau_min >= 1, tau_hi <= frame_length - win_length - 1,
+ * tau_hi - tau_min >= 2, trough_threshold > 0, sample_rate > 0; these, pointers that are NULL, not 4-byte aligned or overlapping:
+ * KPR_E_BADARG.  time >= 2^31: KPR_E_UNSUPPORTED.  batch, channels or frames == 0: returns 0, launches nothing.
+ * kpr_yin_plan (host only): the frames of one series that a workgroup takes as a run, and the form (KPR_YIN_DIRECT / KPR_YIN_SHARED)
+ * the dispatch uses for this geometry under the current "yin_variant"; seams for tests. */
+enum { KPR_YIN_DIRECT = 1, KPR_YIN_SHARED = 2 };
+int kpr_yin_plan(int frame_length, int win_length, int hop, int tau_min, int tau_hi, int* frames_per_run, int* form);
+int kpr_yin_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, double sample_rate, int frame_length,
+                int win_length, int hop, int tau_min, int tau_hi, double trough_threshold, int pad_end, float* f0, float* cmnd,
+                float* want_curve, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

@@ -29,7 +29,7 @@ from .time_frequency import (
 )
 
 from . import signal
-from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve, PitchShift
+from .signal import Frame, Energy, MuLawEncoding, MuLawDecoding, LogmelToMFCC, Resample, LFilter, Preemphasis, Deemphasis, Convolve, PitchShift, YIN
 
 from . import augmentation
 from .augmentation import SpecAugment, ChannelSwap, Reverb, AddNoise
@@ -105,6 +105,7 @@ __all__ = [
     'LogmelToMFCC',
     'Resample',
     'PitchShift',
+    'YIN',
     'LFilter',
     'Preemphasis',
     'Deemphasis',

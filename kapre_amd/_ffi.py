@@ -245,6 +245,12 @@ EXPORTS = {
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_size_t, ctypes.c_void_p]),
+    # YIN (kapre_amd/signal.py)
+    "kpr_yin_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "kpr_yin_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1186,3 +1192,35 @@ def add_noise_bwd(gy, x, fmt, bank, lengths, table, stats):
     _call("kpr_add_noise_bwd_f32", x.device, ptr(gy), ptr(x), b, c, t, layout(fmt), ptr(bank), int(bank.shape[0]),
           int(bank.shape[1]), ptr(lengths), ptr(table), ptr(stats), ptr(gx), ptr(stats_out), ptr(ws), ws_bytes)
     return gx, stats_out
+
+
+# YIN (kapre_amd/signal.py)
+YIN_DIRECT, YIN_SHARED = 1, 2
+
+
+def yin_plan(frame_length: int, win_length: int, hop: int, tau_min: int, tau_hi: int):
+    """(frames_per_run, form): the consecutive frames of a series that one workgroup of kpr_yin_f32 takes, and the form
+    (YIN_DIRECT or YIN_SHARED) its dispatch uses for this geometry under the current ``yin_variant`` (host only).
+    ``ValueError`` for a geometry outside the limits."""
+    f, form = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().kpr_yin_plan(int(frame_length), int(win_length), int(hop), int(tau_min), int(tau_hi), ctypes.byref(f),
+                            ctypes.byref(form))
+    if rc == E_BADARG:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_yin_plan")
+    return f.value, form.value
+
+
+def yin(x, fmt, sr, frame_length, win_length, hop, tau_min, tau_hi, threshold, pad_end, want_curve=False):
+    """(f0, cmnd) of the float32 waveform ``x``, or (f0, cmnd, curve) with ``want_curve``: the YIN pitch track of every series,
+    float32 (b, frames, ch) / (b, ch, frames) as ``fmt`` says; curve: the normalised difference function (b, ch, frames,
+    tau_hi + 1), for tests.  One launch."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    n = _frame_count(int(t), int(frame_length), int(hop), pad_end)
+    f0 = torch.empty(shape_of(fmt, b, c, n), dtype=torch.float32, device=x.device)
+    cmnd = torch.empty_like(f0)
+    curve = torch.empty((b, c, n, int(tau_hi) + 1), dtype=torch.float32, device=x.device) if want_curve else None
+    _call("kpr_yin_f32", x.device, ptr(x), b, c, t, layout(fmt), float(sr), int(frame_length), int(win_length), int(hop),
+          int(tau_min), int(tau_hi), float(threshold), int(bool(pad_end)), ptr(f0), ptr(cmnd), ptr(curve))
+    return (f0, cmnd, curve) if want_curve else (f0, cmnd)

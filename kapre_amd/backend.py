@@ -14,6 +14,8 @@ from __future__ import annotations
 
 from typing import Callable, Optional, Union
 
+import math
+
 import numpy as np
 
 from . import _ffi
@@ -1264,3 +1266,71 @@ def hpss(x, kernel_size=31, power=2.0, margin=1.0, mask=False, data_format='defa
     sizes, power, margins = hpss_parameters(kernel_size, power, margin)
     fmt = resolve_data_format(data_format)
     return time_frequency._hpss_run(x, sizes, power, margins, bool(mask), fmt, 'pair')
+
+
+# --------------------------------------------------------------------------------------
+# YIN pitch tracking
+# --------------------------------------------------------------------------------------
+YIN_MAX_FRAME = 4096
+
+
+def _yin_int(value, what, least):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
+        raise ValueError('YIN: %s must be an integer >= %d, got %r' % (what, least, value))
+    return int(value)
+
+
+def yin_parameters(fmin, fmax, sample_rate, frame_length=2048, win_length=None, hop_length=None, trough_threshold=0.1):
+    """Validated (sample_rate, frame_length, win_length, hop_length, tau_min, tau_hi, trough_threshold) of a YIN pitch tracker:
+    win_length defaults to frame_length // 2, hop_length to frame_length // 4; tau_min = max(floor(sr / fmax), 1) and
+    tau_hi = min(ceil(sr / fmin), frame_length - win_length - 1), the lags the kernel is handed.  ``ValueError`` for
+    fmin >= fmax, a lag range of fewer than three lags, frame_length > 4096, win_length outside 2 ... frame_length - 3,
+    hop_length < 1, a sample rate or threshold that is not positive."""
+    for v, what in ((fmin, 'fmin'), (fmax, 'fmax'), (sample_rate, 'sample_rate'), (trough_threshold, 'trough_threshold')):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (math.isfinite(v) and v > 0):
+            raise ValueError('YIN: %s must be a positive number, got %r' % (what, v))
+    if fmin >= fmax:
+        raise ValueError('YIN: fmin < fmax is required, got fmin = %r, fmax = %r' % (fmin, fmax))
+    frame_length = _yin_int(frame_length, 'frame_length', 1)
+    if frame_length > YIN_MAX_FRAME:
+        raise ValueError('YIN: frame_length is at most %d, got %d' % (YIN_MAX_FRAME, frame_length))
+    win_length = frame_length // 2 if win_length is None else _yin_int(win_length, 'win_length', 2)
+    hop_length = frame_length // 4 if hop_length is None else hop_length
+    hop_length = _yin_int(hop_length, 'hop_length', 1)
+    if not 2 <= win_length <= frame_length - 3:
+        raise ValueError('YIN: win_length must lie in 2 ... frame_length - 3 = %d, got %d' % (frame_length - 3, win_length))
+    sr = float(sample_rate)
+    tau_min = max(int(math.floor(sr / float(fmax))), 1)
+    tau_hi = min(int(math.ceil(sr / float(fmin))), frame_length - win_length - 1)
+    if tau_hi - tau_min < 2:
+        raise ValueError('YIN: fmin = %r, fmax = %r at sample rate %r and frame_length %d, win_length %d leave the lags '
+                         '%d ... %d: at least three are required' % (fmin, fmax, sample_rate, frame_length, win_length, tau_min, tau_hi))
+    return sr, frame_length, win_length, hop_length, tau_min, tau_hi, float(trough_threshold)
+
+
+def _yin_run(x, params, pad_end, fmt, return_cmnd):
+    """``x`` (rank 3) through kpr_yin_f32 with ``params`` = ``yin_parameters(...)``; ``fmt`` is resolved."""
+    import torch
+    from . import autograd
+    autograd.refuse(x, 3, 'YIN expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'YIN has a float32 kernel only; got a float64 input (cast it to float32)')
+    x = _ffi.as_device(x.detach() if isinstance(x, torch.Tensor) else x, torch.float32)
+    sr, frame_length, win_length, hop_length, tau_min, tau_hi, threshold = params
+    f0, cmnd = _ffi.yin(x, fmt, sr, frame_length, win_length, hop_length, tau_min, tau_hi, threshold, pad_end)
+    if not return_cmnd:
+        return f0
+    return torch.stack((f0, cmnd), dim=-1 if _ffi.is_channels_last(fmt) else 1)
+
+
+def yin(x, fmin, fmax, sample_rate, frame_length=2048, win_length=None, hop_length=None, trough_threshold=0.1, pad_end=False,
+        data_format='default', return_cmnd=False):
+    """Fundamental frequency of every frame of a waveform batch on the GPU (``kapre_amd.YIN`` as a function): the YIN algorithm
+    (de Cheveigne & Kawahara 2002, steps 1-5) as ``librosa.yin`` arranges it, on this library's frames -- not centred, frame t
+    starts at sample t * hop_length, ``pad_end`` reads zeros past the end.  (b, time, ch) -> (b, frames, ch) for
+    ``channels_last``, (b, ch, time) -> (b, ch, frames) for ``channels_first``, float32 Hz.  ``return_cmnd`` stacks the
+    normalised difference at the chosen lag as a second feature: (b, frames, ch, 2), or (b, 2, ch, frames) for
+    ``channels_first``; a frame is voiced where cmnd < trough_threshold.  A frame that reads a NaN / Inf sample is NaN.  One
+    launch (kpr_yin_f32), no gradient.  ``ValueError`` for the limits of ``yin_parameters``, ``TypeError`` for float64."""
+    validate_data_format_str(data_format)
+    params = yin_parameters(fmin, fmax, sample_rate, frame_length, win_length, hop_length, trough_threshold)
+    return _yin_run(x, params, bool(pad_end), resolve_data_format(data_format), bool(return_cmnd))

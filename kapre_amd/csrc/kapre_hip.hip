@@ -53,9 +53,12 @@
 //                             (augmentation.AddNoise) and its input gradient: float64 energy / dot-product sums along time without
 //                             atomics, then out = a + s b; streamed (two launches, a workspace of chunk sums) or resident in the
 //                             registers of one workgroup per item (one launch)
+//   kpr_yin_kernels.h         YIN pitch tracking of a waveform (signal.YIN): the difference function of a run of frames from one
+//                             staged span -- lanes own blocks of lags, a sliding register window, block sums shared between
+//                             overlapping frames --, then the normalised curve, the trough search and the refinement, one launch
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -108,6 +111,7 @@
 #include "kpr_lfilter_kernels.h"
 #include "kpr_spec_fir_kernels.h"
 #include "kpr_mix_kernels.h"
+#include "kpr_yin_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -119,6 +123,7 @@
 #include "kpr_host_lfilter.h"
 #include "kpr_host_convolve.h"
 #include "kpr_host_mix.h"
+#include "kpr_host_yin.h"
 
 // ==========================================================================================
 // C ABI
@@ -177,7 +182,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -651,6 +656,23 @@ int kpr_add_noise_bwd_f32(const float* gy, const float* x, int64_t batch, int ch
     if (int e = api_enter()) return e;
     return run_add_noise(true, gy, x, batch, channels, time, layout, noise, n_noise, stride, lengths, table, stats, gx, stats_out,
                          workspace, workspace_bytes, stream);
+}
+
+/* ---- YIN (kpr_yin_kernels.h) -------------------------------------------------------------------- */
+int kpr_yin_plan(int frame_length, int win_length, int hop, int tau_min, int tau_hi, int* frames_per_run, int* form) {
+    if (!frames_per_run || !form) return fail(KPR_E_BADARG, "frames_per_run / form must not be NULL");
+    YinPlan p;
+    if (int e = yin_plan(frame_length, win_length, hop, tau_min, tau_hi, &p)) return e;
+    *frames_per_run = p.F;
+    *form = p.form;
+    return 0;
+}
+int kpr_yin_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, double sample_rate, int frame_length,
+                int win_length, int hop, int tau_min, int tau_hi, double trough_threshold, int pad_end, float* f0, float* cmnd,
+                float* want_curve, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_yin(x, batch, channels, time, layout, sample_rate, frame_length, win_length, hop, tau_min, tau_hi, trough_threshold,
+                   pad_end, f0, cmnd, want_curve, stream);
 }
 
 }  // extern "C"

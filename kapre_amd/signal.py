@@ -6,7 +6,8 @@ MuLawEncoding / MuLawDecoding (signal.py:236-361) are thin layers over backend.m
 (kpr_mu_law_encode_f32 / kpr_mu_law_decode_i32 / kpr_mu_law_decode_f32).  Resample has no counterpart in the reference: it is
 the step in front of every front end (kpr_resample_f32).  Neither have LFilter, Preemphasis and Deemphasis: biquad filtering of
 the waveform itself (kpr_lfilter_f32), Convolve: convolution with a fixed impulse response (kpr_stft_f32, kpr_spec_fir_c64,
-kpr_istft_f32), and PitchShift: a time stretch and the table-free resampler (kpr_resample_direct_f32)."""
+kpr_istft_f32), PitchShift: a time stretch and the table-free resampler (kpr_resample_direct_f32), and YIN: the pitch track of
+the waveform (kpr_yin_f32)."""
 import math
 
 import numpy as np
@@ -16,7 +17,7 @@ from .backend import _CH_FIRST_STR, _CH_LAST_STR
 from .keras_shim import Layer, register_keras_serializable
 
 __all__ = ['Frame', 'Energy', 'MuLawEncoding', 'MuLawDecoding', 'LogmelToMFCC', 'Resample', 'LFilter', 'Preemphasis',
-           'Deemphasis', 'Convolve', 'PitchShift']
+           'Deemphasis', 'Convolve', 'PitchShift', 'YIN']
 
 
 def _as_waveform(x):
@@ -451,4 +452,54 @@ class Convolve(Layer):
         config = super(Convolve, self).get_config()
         config.update({'ir': self.ir, 'mode': self.mode, 'block_size': self.block_size,
                        'input_data_format': self.input_data_format_str})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class YIN(Layer):
+    """Fundamental-frequency (F0) track of the waveform: the YIN algorithm (de Cheveigne & Kawahara 2002, steps 1-5) as
+    ``librosa.yin`` arranges it, on this library's frames (``backend.yin``).  Frame t starts at sample t * hop_length (not
+    centred; ``pad_end`` reads zeros past the end); per frame the difference function over ``win_length`` samples
+    (default ``frame_length // 2``) for the lags max(floor(sr / fmax), 1) ... min(ceil(sr / fmin), frame_length - win_length - 1),
+    its cumulative-mean normalisation, the first trough below ``trough_threshold`` (else the global minimum) and a parabolic
+    refinement.  ``hop_length`` defaults to ``frame_length // 4``.
+
+    (batch, time, ch) -> (batch, frames, ch) for ``channels_last``, (batch, ch, time) -> (batch, ch, frames) for
+    ``channels_first``: float32 Hz.  ``return_cmnd=True`` stacks the normalised difference at the chosen lag as a second
+    feature on a new trailing axis, (batch, frames, ch, 2), for ``channels_last`` and on a new axis 1, (batch, 2, ch, frames),
+    for ``channels_first``: index 0 is f0, index 1 cmnd; a frame is voiced where cmnd < trough_threshold.  numpy or torch,
+    float32 (a float64 input raises ``TypeError``).  A frame that reads a NaN / Inf sample is NaN, no other frame changes.
+    One launch (kpr_yin_f32); no gradient, the output is detached, like ``TimeStretch``'s.  ``ValueError`` for fmin >= fmax,
+    fewer than three lags, frame_length > 4096 and the other limits of ``backend.yin_parameters``."""
+
+    def __init__(self, fmin, fmax, sample_rate, frame_length=2048, win_length=None, hop_length=None, trough_threshold=0.1,
+                 pad_end=False, data_format='default', return_cmnd=False, **kwargs):
+        super(YIN, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        self._params = backend.yin_parameters(fmin, fmax, sample_rate, frame_length, win_length, hop_length, trough_threshold)
+        self.fmin, self.fmax, self.sample_rate, self.trough_threshold = fmin, fmax, sample_rate, trough_threshold
+        self.frame_length, self.win_length, self.hop_length = self._params[1:4]
+        self.pad_end = bool(pad_end)
+        self.return_cmnd = bool(return_cmnd)
+        self.data_format_str = data_format
+        self.data_format = backend.resolve_data_format(data_format)
+        self.time_axis = 2 if self.data_format == _CH_FIRST_STR else 1
+
+    def compute_output_shape(self, input_shape):
+        """(b, t, ch) -> (b, frames, ch) [+ (2,)]; (b, ch, t) -> (b, ch, frames), or (b, 2, ch, frames) with return_cmnd"""
+        b, c, t = _ffi.dims_of(input_shape, self.data_format)
+        n = None if t is None else _ffi._frame_count(int(t), self.frame_length, self.hop_length, self.pad_end)
+        shape = _ffi.shape_of(self.data_format, b, c, n)
+        if not self.return_cmnd:
+            return shape
+        return shape + (2,) if self.data_format == _CH_LAST_STR else (shape[0], 2) + shape[1:]
+
+    def call(self, x):
+        return backend._yin_run(x, self._params, self.pad_end, self.data_format, self.return_cmnd)
+
+    def get_config(self):
+        config = super(YIN, self).get_config()
+        config.update({'fmin': self.fmin, 'fmax': self.fmax, 'sample_rate': self.sample_rate, 'frame_length': self.frame_length,
+                       'win_length': self.win_length, 'hop_length': self.hop_length, 'trough_threshold': self.trough_threshold,
+                       'pad_end': self.pad_end, 'data_format': self.data_format_str, 'return_cmnd': self.return_cmnd})
         return config
