@@ -163,6 +163,8 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *   "yin_variant"  0 = automatic (default: kpr_yin_f32 shares the block sums of overlapping frames where hop divides win_length,
  *                  kpr_yin_plan) | 1 = the direct form, every frame summed on its own, for every shape (A/B runs, tests; results
  *                  within the error bound of each other, not bit-identical)
+ *   "cqt_chunk"    0 = automatic (default) | n = kpr_cqt_f32 stages at most n taps (rounded up to 16) of a frame at once (tests: the
+ *                  multi-chunk path at small shapes; results within the error bound of each other, not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -865,6 +867,36 @@ int kpr_yin_plan(int frame_length, int win_length, int hop, int tau_min, int tau
 int kpr_yin_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, double sample_rate, int frame_length,
                 int win_length, int hop, int tau_min, int tau_hi, double trough_threshold, int pad_end, float* f0, float* cmnd,
                 float* want_curve, kpr_stream_t stream);
+
+/* ---- CQT: constant-Q transform of a waveform, kapre_amd.CQT ------------------------------------------------------------------
+ * Definition (float64 on the host; the device sees only the float32 table).  Q = filter_scale / (2^(1/B) - 1), f_k = fmin 2^(k/B),
+ * N_k = ceil(Q sr / f_k), L = N_0, off_k = (L - N_k) / 2 (integer division);
+ *   w_k[n] = window(N_k)[n] exp(2 pi i f_k (n - N_k / 2) / sr), divided by sum |w_k| (norm 1) or ||w_k||_2 (norm 2), multiplied by
+ *   sqrt(N_k) when scaled, rounded to float32;
+ *   C[t, k] = sum_{n < N_k} x[o + t hop + off_k + n] conj(w_k[n]).
+ * Frames: center == 0: o = 0 and kpr_frame_count(time, L, hop, pad_end) frames; center != 0: o = -(L / 2) and 1 + time / hop frames.
+ * Samples outside [0, time) read as exact zeros inside the kernel; nothing is padded in memory.
+ * lengths (HOST, n_bins int32): N_k, non-increasing, 2 <= N_k, N_0 <= 65536.
+ * table (DEVICE, 16-byte aligned): the kernels in the packed tile form.  Tile j = bins 8 j ... 8 j + 7 = 16 columns, column 2 b = Re w,
+ *   column 2 b + 1 = -Im w of bin 8 j + b (zero columns past the last bin).  Its tap range is that of bin 8 j rounded to steps of 16
+ *   taps inside [0, L): lo_j = off_{8j} & ~15, hi_j = min(L, lo_j + 16 ceil((off_{8j} + N_{8j} - lo_j) / 16)), S_j = ceil((hi_j - lo_j) / 16)
+ *   steps.  Tiles follow each other, steps ascend, a step is 64 x 4 floats: float 4 l + e of step s is B[tap lo_j + 16 s + 4 (l >> 4) + e]
+ *   [column l & 15], l = 0 ... 63, e = 0 ... 3 (the MFMA fragment order of lane l), zero outside bin's [off_k, off_k + N_k) and at taps
+ *   >= hi_j.  table_floats = 256 sum_j S_j, checked.
+ * x: (batch, time, channels) [LAST] or (batch, channels, time) [FIRST], float32.  out: complex64 (batch, frames, n_bins, channels)
+ * [out_layout LAST] or (batch, channels, frames, n_bins) [FIRST] -- the shapes kpr_stft_f32 writes --, or with magnitude != 0 float32
+ * |C| in the same shape, computed in the same launch.  One launch (k_cqt), no atomics, nothing allocated: the same inputs give the
+ * same bits; capturable.  A NaN / Inf sample reaches only the frames whose L taps cover it.
+ * Error: |dRe|, |dIm| <= (N_k + 4) 2^-24 sum_n |x| |w_k[n]|.
+ * Bad lengths, hop < 1, a table_floats that does not match, pointers that are NULL, misaligned (x 4, table 16, out 8 / 4 bytes) or
+ * overlapping: KPR_E_BADARG.  time >= 2^31, more than 64 (tile, chunk) phases: KPR_E_UNSUPPORTED.  batch, channels or frames == 0:
+ * returns 0, launches nothing.
+ * kpr_cqt_plan (host only): the frames of one series a workgroup takes as a run (64 or 32), the taps of a frame staged in LDS at once
+ * at most (option "cqt_chunk" caps it) and the number of work items (slices of a tile's reduction, one per wave and phase). */
+int kpr_cqt_plan(const int32_t* lengths, int n_bins, int hop, int* frames_per_run, int* chunk, int* work_items);
+int kpr_cqt_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
+                const float* table, int64_t table_floats, int hop, int center, int pad_end, int out_layout, int magnitude, void* out,
+                kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

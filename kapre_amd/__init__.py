@@ -26,6 +26,7 @@ from .time_frequency import (
     GriffinLim,
     TimeStretch,
     HPSS,
+    CQT,
 )
 
 from . import signal
@@ -42,6 +43,7 @@ from .composed import (
     get_stft_mag_phase,
     get_time_stretch_layer,
     get_hpss_layer,
+    get_cqt_layer,
 )
 
 
@@ -98,6 +100,7 @@ __all__ = [
     'GriffinLim',
     'TimeStretch',
     'HPSS',
+    'CQT',
     'Frame',
     'Energy',
     'MuLawEncoding',
@@ -121,6 +124,7 @@ __all__ = [
     'get_stft_mag_phase',
     'get_time_stretch_layer',
     'get_hpss_layer',
+    'get_cqt_layer',
     'Layer',
     'Sequential',
     'Model',

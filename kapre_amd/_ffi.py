@@ -251,6 +251,12 @@ EXPORTS = {
     "kpr_yin_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # CQT (kapre_amd/time_frequency.py)
+    "kpr_cqt_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "kpr_cqt_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1224,3 +1230,68 @@ def yin(x, fmt, sr, frame_length, win_length, hop, tau_min, tau_hi, threshold, p
     _call("kpr_yin_f32", x.device, ptr(x), b, c, t, layout(fmt), float(sr), int(frame_length), int(win_length), int(hop),
           int(tau_min), int(tau_hi), float(threshold), int(bool(pad_end)), ptr(f0), ptr(cmnd), ptr(curve))
     return (f0, cmnd, curve) if want_curve else (f0, cmnd)
+
+
+# CQT (kapre_amd/time_frequency.py)
+CQT_STEP, CQT_TILE_BINS = 16, 8
+
+
+def cqt_tiles(lengths):
+    """[(lo, hi)] per tile of 8 bins: the tap range of the tile's lowest bin, rounded to steps of 16 taps inside [0, L)
+    (include/kapre_hip.h, kpr_cqt_f32)."""
+    L = int(lengths[0])
+    out = []
+    for k in range(0, len(lengths), CQT_TILE_BINS):
+        off = (L - int(lengths[k])) // 2
+        lo = off & ~15
+        out.append((lo, min(L, lo + -(-(off + int(lengths[k]) - lo) // 16) * 16)))
+    return out
+
+
+def cqt_pack(lengths, kernels) -> np.ndarray:
+    """The packed tile form of kpr_cqt_f32 from the ragged complex kernels ``kernels[k]`` (N_k taps each): per tile and step of
+    16 taps 64 x 4 floats, float 4 l + e = B[tap lo + 16 s + 4 (l >> 4) + e][column l & 15], column 2 b = Re, 2 b + 1 = -Im of
+    bin 8 j + b; zeros outside a bin's taps, past the last bin and past the tile's range."""
+    L, K = int(lengths[0]), len(lengths)
+    parts = []
+    for j, (lo, hi) in enumerate(cqt_tiles(lengths)):
+        steps = -(-(hi - lo) // CQT_STEP)
+        dense = np.zeros((steps * CQT_STEP, 16), np.float32)
+        for b in range(min(CQT_TILE_BINS, K - CQT_TILE_BINS * j)):
+            k = CQT_TILE_BINS * j + b
+            off = (L - int(lengths[k])) // 2 - lo
+            dense[off:off + int(lengths[k]), 2 * b] = np.real(kernels[k])
+            dense[off:off + int(lengths[k]), 2 * b + 1] = -np.imag(kernels[k])
+        parts.append(dense.reshape(steps, 4, 4, 16).transpose(0, 1, 3, 2).reshape(-1))      # [s][kq][e][m] -> [s][kq][m][e]
+    return np.concatenate(parts)
+
+
+def cqt_plan(lengths, hop: int):
+    """(frames_per_run, chunk, work_items) of kpr_cqt_f32 for these kernel lengths and hop under the current ``cqt_chunk``
+    (host only).  ``ValueError`` for lengths or a hop outside the limits."""
+    n = np.ascontiguousarray(lengths, np.int32)
+    f, chunk, items = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().kpr_cqt_plan(n.ctypes.data_as(ctypes.c_void_p), len(n), int(hop), ctypes.byref(f), ctypes.byref(chunk),
+                            ctypes.byref(items))
+    if rc == E_BADARG:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_cqt_plan")
+    return f.value, chunk.value, items.value
+
+
+def cqt_frames(t: int, L: int, hop: int, center: bool, pad_end: bool) -> int:
+    return 1 + int(t) // int(hop) if center else _frame_count(int(t), int(L), int(hop), pad_end)
+
+
+def cqt(x, fmt, out_fmt, lengths, table, hop, center, pad_end, magnitude):
+    """The constant-Q transform of the float32 waveform ``x`` with the packed ``table`` (device) of the kernels of ``lengths``
+    (host int32): complex64, or float32 magnitudes, (b, frames, K, ch) / (b, ch, frames, K) as ``out_fmt`` says.  One launch."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    n = np.ascontiguousarray(lengths, np.int32)
+    frames = cqt_frames(t, n[0], hop, center, pad_end)
+    out = torch.empty(shape_of(out_fmt, b, c, frames, len(n)), dtype=torch.float32 if magnitude else torch.complex64,
+                      device=x.device)
+    _call("kpr_cqt_f32", x.device, ptr(x), b, c, t, layout(fmt), n.ctypes.data_as(ctypes.c_void_p), len(n), ptr(table),
+          int(table.numel()), int(hop), int(bool(center)), int(bool(pad_end)), layout(out_fmt), int(bool(magnitude)), ptr(out))
+    return out

@@ -1334,3 +1334,92 @@ def yin(x, fmin, fmax, sample_rate, frame_length=2048, win_length=None, hop_leng
     validate_data_format_str(data_format)
     params = yin_parameters(fmin, fmax, sample_rate, frame_length, win_length, hop_length, trough_threshold)
     return _yin_run(x, params, bool(pad_end), resolve_data_format(data_format), bool(return_cmnd))
+
+
+# --------------------------------------------------------------------------------------
+# constant-Q transform
+# --------------------------------------------------------------------------------------
+CQT_MAX_TAPS = 65536
+CQT_OUTPUTS = ('complex', 'magnitude')
+
+
+def cqt_frequencies(fmin=32.70319566, n_bins=84, bins_per_octave=12):
+    """f_k = fmin 2^(k / bins_per_octave), float64"""
+    return float(fmin) * 2.0 ** (np.arange(int(n_bins), dtype=np.float64) / float(bins_per_octave))
+
+
+def cqt_kernels(sample_rate, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1, window_name=None, norm=1,
+                scale=True):
+    """(lengths, offsets, kernels) of a constant-Q bank: N_k = ceil(Q sr / f_k) with Q = filter_scale / (2^(1/B) - 1),
+    off_k = (N_0 - N_k) // 2, and the complex64 kernels w_k[n] = window(N_k)[n] exp(2 pi i f_k (n - N_k // 2) / sr), divided by
+    sum |w_k| (``norm`` 1) or ||w_k||_2 (``norm`` 2), times sqrt(N_k) with ``scale``; computed in float64 and rounded once.
+    The window is the periodic form ``STFT`` uses.  ``ValueError`` where the highest bin's band passes the Nyquist frequency,
+    N_0 > 65536 or N_{K-1} < 2."""
+    for v, what in ((sample_rate, 'sample_rate'), (fmin, 'fmin'), (filter_scale, 'filter_scale')):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (math.isfinite(v) and v > 0):
+            raise ValueError('CQT: %s must be a positive number, got %r' % (what, v))
+    for v, what in ((n_bins, 'n_bins'), (bins_per_octave, 'bins_per_octave')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('CQT: %s must be an integer >= 1, got %r' % (what, v))
+    if norm not in (1, 2):
+        raise ValueError('CQT: norm must be 1 or 2, got %r' % (norm,))
+    window_fn = get_window_fn(window_name)
+    sr = float(sample_rate)
+    q = float(filter_scale) / (2.0 ** (1.0 / bins_per_octave) - 1.0)
+    freqs = cqt_frequencies(fmin, n_bins, bins_per_octave)
+    if freqs[-1] * (1.0 + 0.5 / q) > sr / 2.0:
+        raise ValueError('CQT: the band of bin %d (%.1f Hz) passes the Nyquist frequency %.1f Hz' % (n_bins - 1, freqs[-1], sr / 2))
+    lengths = np.ceil(q * sr / freqs).astype(np.int64)
+    if lengths[0] > CQT_MAX_TAPS or lengths[-1] < 2:
+        raise ValueError('CQT: kernel lengths %d ... %d: at most %d and at least 2 taps are supported'
+                         % (lengths[0], lengths[-1], CQT_MAX_TAPS))
+    kernels = []
+    for f, n in zip(freqs, lengths):
+        n = int(n)
+        w = window_values(window_fn, n, np.float64) * np.exp(2j * np.pi * f * (np.arange(n) - n // 2) / sr)
+        w = w / (np.abs(w).sum() if norm == 1 else np.sqrt((np.abs(w) ** 2).sum()))
+        kernels.append((w * (np.sqrt(n) if scale else 1.0)).astype(np.complex64))
+    return lengths.astype(np.int32), ((lengths[0] - lengths) // 2).astype(np.int32), kernels
+
+
+_CQT_CONSTS = _ffi.DeviceConstants(max_entries=16)      # the packed tables of backend.cqt (the layer keeps its own)
+
+
+def _cqt_run(x, consts, bank, lengths, hop_length, center, pad_end, fmt, out_fmt, output):
+    """``x`` (rank 3) through kpr_cqt_f32; ``bank``: the hashable arguments of ``cqt_kernels``, the key of the packed table."""
+    import torch
+    from . import autograd
+    autograd.refuse(x, 3, 'CQT expects a rank-3 waveform batch, got shape %s', TypeError,
+                    'CQT has a float32 kernel only; got a float64 input (cast it to float32)')
+    x = _ffi.as_device(x.detach() if isinstance(x, torch.Tensor) else x, torch.float32)
+    table = consts.get(('cqt',) + bank, x.device, lambda: _ffi.cqt_pack(lengths, cqt_kernels(*bank)[2]))
+    return _ffi.cqt(x, fmt, out_fmt, lengths, table, hop_length, center, pad_end, output == 'magnitude')
+
+
+def cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, window_name, norm, scale, output):
+    """(bank, lengths): the validated, hashable arguments of ``cqt_kernels`` and the kernel lengths"""
+    if isinstance(hop_length, bool) or not isinstance(hop_length, (int, np.integer)) or hop_length < 1:
+        raise ValueError('CQT: hop_length must be an integer >= 1, got %r' % (hop_length,))
+    if output not in CQT_OUTPUTS:
+        raise ValueError('CQT: output must be one of %s, got %r' % (CQT_OUTPUTS, output))
+    bank = (sample_rate, fmin, int(n_bins) if not isinstance(n_bins, bool) else n_bins, bins_per_octave, filter_scale,
+            window_name, norm, bool(scale))
+    return bank, cqt_kernels(*bank)[0]
+
+
+def cqt(x, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1, window_name=None,
+        norm=1, scale=True, center=False, pad_end=False, output='complex', input_data_format='default',
+        output_data_format='default'):
+    """Constant-Q transform of a waveform batch on the GPU (``kapre_amd.CQT`` as a function): bin k has its own window of
+    N_k = ceil(Q sr / f_k) samples, centred in the frame of N_0 samples, C[t, k] = sum_n x[o + t hop + off_k + n] conj(w_k[n]).
+    Frame t starts at sample t hop (``center=False``, this library's convention; ``pad_end`` as in ``STFT``) or at
+    t hop - N_0 // 2 (``center=True``, 1 + time // hop frames); samples outside the signal are zeros.  (b, time, ch) /
+    (b, ch, time) float32 -> complex64 (b, frames, n_bins, ch) / (b, ch, frames, n_bins), or float32 ``|C|`` with
+    ``output='magnitude'``.  One launch (kpr_cqt_f32), no gradient.  ``ValueError`` for the limits of ``cqt_kernels``,
+    ``TypeError`` for float64."""
+    for fmt in (input_data_format, output_data_format):
+        validate_data_format_str(fmt)
+    bank, lengths = cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, window_name, norm, scale,
+                                   output)
+    return _cqt_run(x, _CQT_CONSTS, bank, lengths, int(hop_length), bool(center), bool(pad_end),
+                    resolve_data_format(input_data_format), resolve_data_format(output_data_format), output)

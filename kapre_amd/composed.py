@@ -21,6 +21,7 @@ from .time_frequency import (
     ApplyFilterbank,
     TimeStretch,
     HPSS,
+    CQT,
 )
 from . import backend
 from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
@@ -233,6 +234,40 @@ def get_hpss_layer(
     chain.add(HPSS(kernel_size=kernel_size, power=power, margin=margin, output=output, data_format=input_data_format))
     chain.add(InverseSTFT(forward_window_name='hann_window', input_data_format=input_data_format,
                           output_data_format=input_data_format, **shared))
+    return chain
+
+
+def get_cqt_layer(
+    sample_rate,
+    hop_length=512,
+    fmin=32.70319566,
+    n_bins=84,
+    bins_per_octave=12,
+    filter_scale=1,
+    window_name=None,
+    center=False,
+    pad_end=False,
+    return_decibel=False,
+    db_amin=1e-5,
+    db_ref_value=1.0,
+    db_dynamic_range=80.0,
+    input_shape=None,
+    input_data_format='default',
+    output_data_format='default',
+    name='cqt',
+):
+    """``Sequential([CQT(output='magnitude'), (MagnitudeToDecibel)])``: a waveform batch in, the constant-Q magnitude
+    spectrogram out, (batch, frames, n_bins, ch) or (batch, ch, frames, n_bins) (this package's own; ``abs(librosa.cqt)``
+    on frames that are not centred unless ``center``)."""
+    args = dict(sample_rate=sample_rate, hop_length=hop_length, fmin=fmin, n_bins=n_bins, bins_per_octave=bins_per_octave,
+                filter_scale=filter_scale, window_name=window_name, center=center, pad_end=pad_end, output='magnitude',
+                input_data_format=input_data_format, output_data_format=output_data_format)
+    if input_shape is not None:
+        args['input_shape'] = input_shape
+    chain = Sequential(name=name)
+    chain.add(CQT(**args))
+    if return_decibel:
+        chain.add(MagnitudeToDecibel(ref_value=db_ref_value, amin=db_amin, dynamic_range=db_dynamic_range))
     return chain
 
 

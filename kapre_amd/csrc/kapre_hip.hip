@@ -56,9 +56,12 @@
 //   kpr_yin_kernels.h         YIN pitch tracking of a waveform (signal.YIN): the difference function of a run of frames from one
 //                             staged span -- lanes own blocks of lags, a sliding register window, block sums shared between
 //                             overlapping frames --, then the normalised curve, the trough search and the refinement, one launch
+//   kpr_cqt_kernels.h         constant-Q transform of a waveform (time_frequency.CQT): an implicit GEMM on the matrix units -- rows
+//                             are the frames of a run staged once in LDS, columns the (Re, -Im) of eight bins with their own tap
+//                             range, the reduction split over the waves and added in a fixed order, complex or magnitude epilogue
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -112,6 +115,7 @@
 #include "kpr_spec_fir_kernels.h"
 #include "kpr_mix_kernels.h"
 #include "kpr_yin_kernels.h"
+#include "kpr_cqt_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -124,6 +128,7 @@
 #include "kpr_host_convolve.h"
 #include "kpr_host_mix.h"
 #include "kpr_host_yin.h"
+#include "kpr_host_cqt.h"
 
 // ==========================================================================================
 // C ABI
@@ -182,7 +187,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -673,6 +678,24 @@ int kpr_yin_f32(const float* x, int64_t batch, int channels, int64_t time, int l
     if (int e = api_enter()) return e;
     return run_yin(x, batch, channels, time, layout, sample_rate, frame_length, win_length, hop, tau_min, tau_hi, trough_threshold,
                    pad_end, f0, cmnd, want_curve, stream);
+}
+
+/* ---- CQT (kpr_cqt_kernels.h) -------------------------------------------------------------------- */
+int kpr_cqt_plan(const int32_t* lengths, int n_bins, int hop, int* frames_per_run, int* chunk, int* work_items) {
+    if (!frames_per_run || !chunk || !work_items) return fail(KPR_E_BADARG, "frames_per_run / chunk / work_items must not be NULL");
+    CqtPlan p;
+    if (int e = cqt_plan(lengths, n_bins, hop, &p)) return e;
+    *frames_per_run = 16 * p.RT;
+    *chunk = p.chunk;
+    *work_items = p.items;
+    return 0;
+}
+int kpr_cqt_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
+                const float* table, int64_t table_floats, int hop, int center, int pad_end, int out_layout, int magnitude, void* out,
+                kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_cqt(x, batch, channels, time, layout, lengths, n_bins, table, table_floats, hop, center, pad_end, out_layout, magnitude,
+                   out, stream);
 }
 
 }  // extern "C"

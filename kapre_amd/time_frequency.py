@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim``, ``TimeStretch`` and ``HPSS`` are this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim``, ``TimeStretch``, ``HPSS`` and ``CQT`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -39,6 +39,7 @@ __all__ = [
     'GriffinLim',
     'TimeStretch',
     'HPSS',
+    'CQT',
 ]
 
 
@@ -1096,6 +1097,69 @@ class HPSS(Layer):
         config = super(HPSS, self).get_config()
         config.update({'kernel_size': list(self.kernel_size), 'power': self.power, 'margin': list(self.margin),
                        'output': self.output, 'mask': self.mask, 'data_format': self.data_format_original})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class CQT(Layer):
+    """Constant-Q transform of the waveform (``librosa.cqt``, nnAudio's ``CQT1992v2``; ``backend.cqt``).  Bin k at
+    f_k = fmin 2^(k / bins_per_octave) has its own window of N_k = ceil(Q sr / f_k) samples, Q = filter_scale / (2^(1/B) - 1),
+    centred in the frame of L = N_0 samples; its kernel is w_k[n] = window(N_k)[n] exp(2 pi i f_k (n - N_k // 2) / sr), divided by
+    sum |w_k| (``norm=1``) or ||w_k||_2 (``norm=2``), times sqrt(N_k) with ``scale``, and
+
+        C[t, k] = sum_{n < N_k} x[o + t hop + off_k + n] conj(w_k[n]),    off_k = (L - N_k) // 2.
+
+    ``center=False`` (this library's convention): frame t starts at sample t hop and the frames are ``STFT``'s of ``n_fft`` = L
+    (``pad_end`` as there); ``center=True``: it starts at t hop - L // 2 and there are 1 + time // hop frames.  Samples outside
+    the signal read as zeros (no reflect padding).  ``window_name``: the names ``STFT`` accepts, in the periodic form.
+
+    (batch, time, ch) / (batch, ch, time) float32 -> complex64 (batch, frames, n_bins, ch) for ``output_data_format``
+    'channels_last', (batch, ch, frames, n_bins) for 'channels_first': the layouts ``STFT`` writes, so ``Magnitude``, ``Phase``,
+    ``MagnitudeToDecibel``, ``HPSS``, ``SpecAugment`` chain behind it.  ``output='magnitude'`` gives float32 ``|C|`` from the
+    same launch.  One launch of ``k_cqt`` (kpr_cqt_f32): an implicit GEMM on the matrix units; the same inputs give the same
+    bits.  float32 only (a float64 input raises ``TypeError``).  The output carries no gradient -- the adjoint is a scatter
+    that is not built yet -- and an input that requires grad is detached.  ``ValueError`` where the highest bin's band
+    f_{K-1} (1 + 1 / (2 Q)) passes sr / 2, where L > 65536 or N_{K-1} < 2."""
+
+    def __init__(self, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1,
+                 window_name=None, norm=1, scale=True, center=False, pad_end=False, output='complex',
+                 input_data_format='default', output_data_format='default', **kwargs):
+        super(CQT, self).__init__(**kwargs)
+        for data_format in (input_data_format, output_data_format):
+            backend.validate_data_format_str(data_format)
+        self._bank, self._lengths = backend.cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale,
+                                                           window_name, norm, scale, output)
+        self.sample_rate, self.hop_length, self.fmin, self.n_bins = sample_rate, int(hop_length), fmin, int(n_bins)
+        self.bins_per_octave, self.filter_scale, self.window_name, self.norm = bins_per_octave, filter_scale, window_name, norm
+        self.scale, self.center, self.pad_end, self.output = bool(scale), bool(center), bool(pad_end), output
+        self.input_data_format_original = input_data_format
+        self.output_data_format_original = output_data_format
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self._consts = _ffi.DeviceConstants()
+
+    @property
+    def frame_length(self):
+        """L = N_0, the samples a frame spans"""
+        return int(self._lengths[0])
+
+    def compute_output_shape(self, input_shape):
+        """(b, t, ch) / (b, ch, t) -> (b, frames, n_bins, ch) / (b, ch, frames, n_bins)"""
+        b, c, t = _ffi.dims_of(input_shape, self.input_data_format)
+        frames = None if t is None else _ffi.cqt_frames(t, self.frame_length, self.hop_length, self.center, self.pad_end)
+        return _ffi.shape_of(self.output_data_format, b, c, frames, self.n_bins)
+
+    def call(self, x):
+        return backend._cqt_run(x, self._consts, self._bank, self._lengths, self.hop_length, self.center, self.pad_end,
+                                self.input_data_format, self.output_data_format, self.output)
+
+    def get_config(self):
+        config = super(CQT, self).get_config()
+        config.update({'sample_rate': self.sample_rate, 'hop_length': self.hop_length, 'fmin': self.fmin, 'n_bins': self.n_bins,
+                       'bins_per_octave': self.bins_per_octave, 'filter_scale': self.filter_scale,
+                       'window_name': self.window_name, 'norm': self.norm, 'scale': self.scale, 'center': self.center,
+                       'pad_end': self.pad_end, 'output': self.output, 'input_data_format': self.input_data_format_original,
+                       'output_data_format': self.output_data_format_original})
         return config
 
 
