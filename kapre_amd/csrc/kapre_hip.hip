@@ -7,6 +7,8 @@
 //   kpr_common.h              errors, frame geometry, sample fetch, and the wave-protocol pieces every kernel family shares:
 //                             ticket draw, bounded waits, window pairs into LDS
 //   kpr_cols.h                the column groups of the time-tiled kernels (k_pcen, k_cmvn, k_time_stretch): ColGroup, ColVec
+//   kpr_series.h              the series of the waveform kernels (k_yin, k_cqt, k_resample, k_resample_direct, k_lfilter): the three
+//                             strides of a (batch, channels, time) batch in either layout, the series and work unit of a workgroup
 //   kpr_mel_kernels.h        k_mel_ws: waveform -> [frame + window + rFFT -> |X| -> (K x M)
 //                             filterbank on fp32 MFMA -> optional 10 log10], the whole Sequential of
 //                             composed.py:138-261 in one launch; FROM_MAG: stand-alone ApplyFilterbank
@@ -60,7 +62,7 @@
 //                             are the frames of a run staged once in LDS, columns the (Re, -Im) of eight bins with their own tap
 //                             range, the reduction split over the waves and added in a fixed order, complex or magnitude epilogue
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
-// (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_griffin_lim.h,
+// (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_resample.h, kpr_host_griffin_lim.h,
 // kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
@@ -90,6 +92,7 @@
 
 #include "kpr_common.h"
 #include "kpr_cols.h"
+#include "kpr_series.h"
 #include "kpr_mel_kernels.h"
 #include "kpr_mel_ts_kernels.h"
 #include "kpr_mel_pw_kernels.h"
@@ -123,6 +126,7 @@
 #include "kpr_host_istft.h"
 #include "kpr_host_mel.h"
 #include "kpr_host_ops.h"
+#include "kpr_host_resample.h"
 #include "kpr_host_griffin_lim.h"
 #include "kpr_host_lfilter.h"
 #include "kpr_host_convolve.h"

@@ -53,9 +53,9 @@ struct CqtArgs {
     const float* x;
     const f4* table;
     float* out;                         // complex64 as float pairs, or float32 magnitudes
-    long long item, series;             // elements per batch item; from one channel's series to the next
-    long long out_item, out_series;     // the same for out, in output elements
-    int estride, out_t, out_k;          // elements from one sample / frame / bin to the next
+    long long item, chan;               // the series of x (kpr_series.h)
+    long long out_item, out_chan;       // the same for out, in output elements
+    int stride, out_t, out_k;           // elements from one sample / frame / bin to the next
     int C, time, frames, runs, K;
     int hop, origin;                    // frame t starts at sample origin + t hop
     int hopL, pad;                      // LDS: row m starts at m hopL; a word i lies at i + pad * (i / hop)
@@ -103,12 +103,10 @@ __attribute__((target("no-packed-fp32-ops"))) __global__ __launch_bounds__(kCqtT
     float* xs = cqt_lds;
     float* red = cqt_lds + a.red;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
-    const int s = blockIdx.x / a.runs, run = blockIdx.x - s * a.runs;
-    const int item_b = s / a.C, ch = s - item_b * a.C;
-    const int t0 = run * F;
-    const int fv = min(F, a.frames - t0);
-    const float* in = a.x + item_b * a.item + ch * a.series;
-    float* out = a.out + (item_b * a.out_item + ch * a.out_series + (long long)t0 * a.out_t) * (MAG ? 1 : 2);
+    const SeriesUnit u = series_unit(a.runs, a.C);                       // unit: the run
+    const float* in = u.at(a.x, a.item, a.chan);
+    const auto [t0, fv] = frame_run(u.unit, F, a.frames);
+    float* out = a.out + (u.off(a.out_item, a.out_chan) + (long long)t0 * a.out_t) * (MAG ? 1 : 2);
     const long long g_run = (long long)a.origin + (long long)t0 * a.hop;
 
     int row[RT];
@@ -130,7 +128,7 @@ __attribute__((target("no-packed-fp32-ops"))) __global__ __launch_bounds__(kCqtT
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const long long g = g0 + i0 + j * kCqtThreads;
-                        v[j] = (i0 + j * kCqtThreads < plen && g >= 0 && g < a.time) ? in[g * a.estride] : 0.0f;
+                        v[j] = (i0 + j * kCqtThreads < plen && g >= 0 && g < a.time) ? in[g * a.stride] : 0.0f;
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {

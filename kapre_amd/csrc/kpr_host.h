@@ -1,5 +1,6 @@
 // kpr_host.h -- host side shared by every kernel family: options, once-per-device state, launch log, device status word, LDS opt-in,
-// CU count, with_vec, geometry checks (ranges_overlap, col_launch for the time-tiled kernels), the GEMM launcher, the device-table cache,
+// CU count, with_vec, geometry checks (ranges_overlap, col_launch for the time-tiled kernels; series_of, check_series, check_reach, check_ptrs, grid_of
+// for the waveform kernels), the GEMM launcher, the device-table cache,
 // the launcher of the framewise FFT kernels.
 // Part of the single translation unit kapre_hip.hip (after the kernel headers, before kpr_host_fft.h / _stft.h / _istft.h / _mel.h / _ops.h).
 #pragma once
@@ -187,6 +188,64 @@ static int col_launch(int64_t outer, int64_t inner, int V, int waves, bool align
     if (blocks > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "too many columns: outer * inner = %lld", (long long)(outer * inner));
     l->grid = dim3((unsigned)blocks);
     l->block = dim3(64 * waves);
+    return 0;
+}
+
+// ---- the waveform families (device side: kpr_series.h): a (batch, channels, len) batch walked one series at a time ----
+// The strides of a series of `len` samples.  collapse_single_channel: one channel in channels_last is addressed as channels_first,
+// the same memory image; the families that pair channels or order their output by the layout pass false.
+static Series series_of(int layout, int channels, int64_t len, bool collapse_single_channel) {
+    const bool cl = layout == KPR_CHANNELS_LAST && (channels > 1 || !collapse_single_channel);
+    // (called before check_reach has seen len: the product may wrap, which unsigned arithmetic lets it do)
+    return Series{(long long)((unsigned long long)channels * (unsigned long long)len), cl ? 1 : (long long)len, cl ? channels : 1};
+}
+
+// signs and the layout enum (two layouts: pass layout | out_layout; two lengths: the smaller); `what` is the refusal's text.
+// zero_channels_ok: channels == 0 is an empty call, which the caller returns from once its other arguments are checked
+static int check_series(const char* what, int64_t batch, int channels, int64_t len, int layout, bool zero_channels_ok) {
+    if (batch < 0 || channels < (zero_channels_ok ? 0 : 1) || len < 0 || (unsigned)layout > 1u) return fail(KPR_E_BADARG, "%s", what);
+    return 0;
+}
+
+// the kernels address one series with 32-bit offsets: len * stride < 2^bits -- 2^30 elements, or 2^31 samples with stride 1 --
+// compared without a product that could overflow
+static int check_reach(const char* op, int64_t len, int stride, int bits) {
+    if (len > ((1LL << bits) - 1) / stride)
+        return fail(KPR_E_UNSUPPORTED, "%s: %lld samples at a stride of %d: 2^%d elements or more per signal are not supported", op,
+                    (long long)len, stride, bits);
+    return 0;
+}
+
+// One pointer of a call and the bytes it spans.  check_ptrs: no NULL but where may_be_null, every pointer aligned, and no two
+// ranges overlap of which the call writes at least one (`out`).  op starts the texts ("yin: "), note ends an overlap's.
+struct PtrArg {
+    const char* name;
+    const void* p;
+    uintptr_t bytes;
+    unsigned align;
+    bool may_be_null, out;
+};
+static int check_ptrs(const char* op, std::initializer_list<PtrArg> args, const char* note = "") {
+    for (const PtrArg& a : args)
+        if (!a.p && !a.may_be_null) {
+            std::string names;
+            for (const PtrArg& b : args)
+                if (!b.may_be_null) names += (names.empty() ? "" : " / ") + std::string(b.name);
+            return fail(KPR_E_BADARG, "%s%s must not be NULL", op, names.c_str());
+        }
+    for (const PtrArg& a : args)
+        if ((uintptr_t)a.p & (a.align - 1)) return fail(KPR_E_BADARG, "%sthe pointers must be %u-byte aligned", op, a.align);
+    for (const PtrArg* a = args.begin(); a != args.end(); ++a)
+        for (const PtrArg* b = a + 1; b != args.end(); ++b)
+            if ((a->out || b->out) && ranges_overlap(a->p, a->bytes, b->p, b->bytes))
+                return fail(KPR_E_BADARG, "%s%s and %s overlap%s", op, a->name, b->name, note);
+    return 0;
+}
+
+// the grid of a series-major launch (kpr_series.h): `units` workgroups per series x batch x channels (or channel groups), in 31 bits
+static int grid_of(long long units, int64_t batch, int n, const char* what, long long* grid) {
+    *grid = units * batch * n;
+    if (units > 0x7fffffffLL || *grid > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "%s: too many workgroups (%lld)", what, *grid);
     return 0;
 }
 

@@ -138,31 +138,32 @@ static int launch_cqt(const CqtArgs& a, long long grid, size_t lds, hipStream_t 
 static int run_cqt(const float* x, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
                    const float* table, int64_t table_floats, int hop, int center, int pad_end, int out_layout, int magnitude,
                    void* out, kpr_stream_t stream) {
-    if (batch < 0 || channels < 0 || time < 0 || (unsigned)layout > 1u || (unsigned)out_layout > 1u)
-        return fail(KPR_E_BADARG, "cqt: bad batch/channels/time/layout");
+    if (int e = check_series("cqt: bad batch/channels/time/layout", batch, channels, time, layout | out_layout, true)) return e;
     CqtPlan p;
     if (int e = cqt_plan(lengths, n_bins, hop, &p)) return e;
     if (table_floats != p.table_floats)
         return fail(KPR_E_BADARG, "cqt: the packed table of these lengths has %lld floats, got %lld", p.table_floats, (long long)table_floats);
-    if (time >= (1LL << 31)) return fail(KPR_E_UNSUPPORTED, "cqt: %lld samples per series: 2^31 or more are not supported", (long long)time);
+    if (int e = check_reach("cqt", time, 1, 31)) return e;
     const int L = lengths[0];
     const int64_t frames = center ? 1 + time / hop : frame_count(time, L, hop, pad_end);
     if (batch == 0 || channels == 0 || frames <= 0) return 0;
-    if (!x || !table || !out) return fail(KPR_E_BADARG, "cqt: x / table / out must not be NULL");
-    if ((((uintptr_t)x) & 3) || (((uintptr_t)table) & 15) || (((uintptr_t)out) & (magnitude ? 3 : 7)))
-        return fail(KPR_E_BADARG, "cqt: x must be 4-byte, the table 16-byte and out %d-byte aligned", magnitude ? 4 : 8);
-    const uintptr_t nx = (uintptr_t)batch * channels * time * 4, nt = (uintptr_t)table_floats * 4,
-                    no = (uintptr_t)batch * channels * frames * n_bins * (magnitude ? 4 : 8);
-    if (ranges_overlap(x, nx, out, no) || ranges_overlap(table, nt, out, no)) return fail(KPR_E_BADARG, "cqt: out must not overlap x or the table");
+    // x: the series; out: one (frames, n_bins) plane per series, a bin `so.stride` elements from the next
+    const Series sx = series_of(layout, channels, time, true), so = series_of(out_layout, channels, frames * n_bins, true);
+    const unsigned esz = magnitude ? 4 : 8;
+    if (int e = check_ptrs("cqt: ", {{"x", x, (uintptr_t)batch * sx.item * 4, 4, false, false},
+                                     {"table", table, (uintptr_t)table_floats * 4, 16, false, false},
+                                     {"out", out, (uintptr_t)batch * so.item * esz, esz, false, true}}))
+        return e;
     const int F = 16 * p.RT;
-    const long long runs = (frames + F - 1) / F, grid = runs * batch * channels;
-    if (grid > 0x7fffffffLL || frames * hop + L >= (1LL << 40)) return fail(KPR_E_UNSUPPORTED, "cqt: too many frame runs (%lld)", grid);
-    const bool cl = layout == KPR_CHANNELS_LAST && channels > 1, ocl = out_layout == KPR_CHANNELS_LAST && channels > 1;
+    const long long runs = (frames + F - 1) / F;
+    long long grid;
+    if (int e = grid_of(runs, batch, channels, "cqt", &grid)) return e;
+    if (frames * hop + L >= (1LL << 40)) return fail(KPR_E_UNSUPPORTED, "cqt: %lld frames at a hop of %d reach past 2^40 samples", (long long)frames, hop);
     CqtArgs a;
     a.x = x; a.table = reinterpret_cast<const f4*>(table); a.out = static_cast<float*>(out);
-    a.item = (long long)channels * time; a.series = cl ? 1 : time; a.estride = cl ? channels : 1;
-    a.out_item = (long long)channels * frames * n_bins; a.out_series = ocl ? 1 : frames * n_bins;
-    a.out_t = ocl ? n_bins * channels : n_bins; a.out_k = ocl ? channels : 1;
+    a.item = sx.item; a.chan = sx.chan; a.stride = sx.stride;
+    a.out_item = so.item; a.out_chan = so.chan;
+    a.out_t = n_bins * so.stride; a.out_k = so.stride;
     a.C = channels; a.time = (int)time; a.frames = (int)frames; a.runs = (int)runs; a.K = n_bins;
     a.hop = hop; a.origin = center ? -(L / 2) : 0;
     a.hopL = p.hopL; a.pad = p.pad; a.magic = p.magic; a.pieces = p.pieces; a.red = p.red;

@@ -84,14 +84,10 @@ static int lfilter_table(const double* coef, LfTab* tab) {
 }
 
 static int lfilter_dims(int64_t batch, int channels, int64_t len, int layout) {
-    if (batch < 0 || channels <= 0 || len < 0 || (unsigned)layout > 1u) return fail(KPR_E_BADARG, "bad batch/channels/len/layout");
-    const long long reach = layout == KPR_CHANNELS_LAST ? channels : 1;
-    if (len * reach >= (1LL << 30))
-        return fail(KPR_E_UNSUPPORTED, "lfilter: %lld samples x %d channels: 2^30 elements or more per signal are not supported",
-                    (long long)len, channels);
-    if (batch * (long long)channels * ((len + kLfSeg - 1) / kLfSeg + 1) > 0x7fffffffLL)
-        return fail(KPR_E_UNSUPPORTED, "lfilter: too many segments (%lld series of %lld samples)", (long long)(batch * channels), (long long)len);
-    return 0;
+    if (int e = check_series("lfilter: bad batch/channels/len/layout", batch, channels, len, layout, false)) return e;
+    if (int e = check_reach("lfilter", len, series_of(layout, channels, len, false).stride, 30)) return e;
+    long long most;                                              // segments and one more per series: the largest grid of the forms
+    return grid_of((len + kLfSeg - 1) / kLfSeg + 1, batch, channels, "lfilter", &most);
 }
 
 static long long lfilter_segments(int64_t len) { return std::max<long long>(1, (len + kLfSeg - 1) / kLfSeg); }
@@ -128,12 +124,10 @@ static int run_lfilter(const float* x, int64_t batch, int channels, int64_t len,
     if (int e = lfilter_coef(coef)) return e;
     if (reverse != 0 && reverse != 1) return fail(KPR_E_BADARG, "reverse must be 0 or 1, got %d", reverse);
     if (batch == 0 || len == 0) return 0;
-    if (!x || !out) return fail(KPR_E_BADARG, "x / out must not be NULL");
-    if ((((uintptr_t)x) | ((uintptr_t)out)) & 3) return fail(KPR_E_BADARG, "x / out must be 4-byte aligned");
-    const size_t n_bytes = (size_t)batch * channels * (size_t)len * 4;
-    // (the FIR form reads its neighbour's samples from x after that neighbour may have stored: there is no in-place form)
-    if (ranges_overlap(x, n_bytes, out, n_bytes)) return fail(KPR_E_BADARG, "x and out overlap (there is no in-place form)");
-    const bool cl = layout == KPR_CHANNELS_LAST && channels > 1;
+    const Series s = series_of(layout, channels, len, true);
+    const PtrArg px = {"x", x, (uintptr_t)batch * s.item * 4, 4, false, false}, pout = {"out", out, px.bytes, 4, false, true};
+    // (the FIR form reads its neighbour's samples from x after that neighbour may have stored)
+    if (int e = check_ptrs("lfilter: ", {px, pout}, " (there is no in-place form)")) return e;
     const bool fir = coef[3] == 0.0 && coef[4] == 0.0;
     const long long series = batch * (long long)channels, n_seg = lfilter_segments(len);
     const int form = fir ? 2 : lfilter_form(batch, channels, len);
@@ -144,13 +138,13 @@ static int run_lfilter(const float* x, int64_t batch, int channels, int64_t len,
     a.b0 = coef[0]; a.b1 = coef[1]; a.b2 = coef[2]; a.na1 = -coef[3]; a.na2 = -coef[4];
     a.sigma = (double)lfilter_sigma(coef[3]);
     a.len = (int)len;
-    a.stride = cl ? channels : 1;
+    a.stride = s.stride;
     a.channels = channels;
-    a.item = (long long)channels * len;
-    a.chan = cl ? 1 : len;
+    a.item = s.item;
+    a.chan = s.chan;
     a.n_seg = form == 2 ? (int)n_seg : 1;
     a.seg_steps = form == 2 ? kLfSegSteps : (int)((len + kLfStep - 1) / kLfStep);
-    const bool vec = !cl && len % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
+    const bool vec = s.stride == 1 && len % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0;
     if (opt(OPT_VERBOSE))
         fprintf(stderr, "[kapre_hip] k_lfilter: %lld series of %lld samples, stride %d, %s, %s, %d workgroup(s) per series, %s\n", series,
                 (long long)len, a.stride, fir ? "fir" : form == 2 ? "segmented" : "whole-signal", reverse ? "reverse" : "forward", a.n_seg,
@@ -166,8 +160,8 @@ static int run_lfilter(const float* x, int64_t batch, int channels, int64_t len,
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
         return fail(KPR_E_WORKSPACE, "lfilter workspace: %zu bytes needed (kpr_lfilter_workspace_bytes, 8-byte aligned), got %zu", need,
                     workspace ? workspace_bytes : (size_t)0);
-    if (ranges_overlap(workspace, need, x, n_bytes) || ranges_overlap(workspace, need, out, n_bytes))
-        return fail(KPR_E_BADARG, "the workspace overlaps x or out");
+    if (int e = check_ptrs("lfilter: ", {{"the workspace", workspace, need, 8, false, true}, px, pout}, " (the workspace overlaps x or out)"))
+        return e;
     a.ends = (double*)workspace;
     double* carry = a.ends + 2 * series * n_seg;
     if (int e = lfilter_launch<LF_ENDS>(a, vec, reverse, series * n_seg, st)) return e;

@@ -48,31 +48,28 @@ static int yin_plan(int frame_length, int W, int hop, int tau_min, int tau_hi, Y
 static int run_yin(const float* x, int64_t batch, int channels, int64_t time, int layout, double sample_rate, int frame_length,
                    int win_length, int hop, int tau_min, int tau_hi, double trough_threshold, int pad_end, float* f0, float* cmnd,
                    float* curve, kpr_stream_t stream) {
-    if (batch < 0 || channels < 0 || time < 0 || (unsigned)layout > 1u) return fail(KPR_E_BADARG, "yin: bad batch/channels/time/layout");
+    if (int e = check_series("yin: bad batch/channels/time/layout", batch, channels, time, layout, true)) return e;
     const float sr = (float)sample_rate, thr = (float)trough_threshold;
     if (!(sr > 0.0f) || !std::isfinite(sr)) return fail(KPR_E_BADARG, "yin: the sample rate must be positive and finite, got %g", sample_rate);
     if (!(thr > 0.0f)) return fail(KPR_E_BADARG, "yin: trough_threshold must be positive, got %g", trough_threshold);
     YinPlan p;
     if (int e = yin_plan(frame_length, win_length, hop, tau_min, tau_hi, &p)) return e;
-    if (time >= (1LL << 31)) return fail(KPR_E_UNSUPPORTED, "yin: %lld samples per series: 2^31 or more are not supported", (long long)time);
+    if (int e = check_reach("yin", time, 1, 31)) return e;
     const int64_t frames = frame_count(time, frame_length, hop, pad_end);
     if (batch == 0 || channels == 0 || frames <= 0) return 0;
-    if (!x || !f0 || !cmnd) return fail(KPR_E_BADARG, "yin: x / f0 / cmnd must not be NULL");
-    if ((((uintptr_t)x) | ((uintptr_t)f0) | ((uintptr_t)cmnd) | ((uintptr_t)curve)) & 3)
-        return fail(KPR_E_BADARG, "yin: the pointers must be 4-byte aligned");
     const int nl = tau_hi + 1;
-    const uintptr_t nx = (uintptr_t)batch * channels * time * 4, no = (uintptr_t)batch * channels * frames * 4, nc = no * nl;
-    if (ranges_overlap(x, nx, f0, no) || ranges_overlap(x, nx, cmnd, no) || ranges_overlap(x, nx, curve, nc) ||
-        ranges_overlap(f0, no, cmnd, no) || ranges_overlap(f0, no, curve, nc) || ranges_overlap(cmnd, no, curve, nc))
-        return fail(KPR_E_BADARG, "yin: x, f0, cmnd and curve must not overlap");
-    const bool cl = layout == KPR_CHANNELS_LAST && channels > 1;
-    const long long runs = (frames + p.F - 1) / p.F, grid = runs * batch * channels;
-    if (grid > 0x7fffffffLL) return fail(KPR_E_UNSUPPORTED, "yin: too many frame runs (%lld)", grid);
+    const Series sx = series_of(layout, channels, time, true), so = series_of(layout, channels, frames, true);
+    const uintptr_t nx = (uintptr_t)batch * sx.item * 4, no = (uintptr_t)batch * so.item * 4;
+    if (int e = check_ptrs("yin: ", {{"x", x, nx, 4, false, false}, {"f0", f0, no, 4, false, true}, {"cmnd", cmnd, no, 4, false, true},
+                                     {"curve", curve, no * nl, 4, true, true}}))
+        return e;
+    const long long runs = (frames + p.F - 1) / p.F;
+    long long grid;
+    if (int e = grid_of(runs, batch, channels, "yin", &grid)) return e;
     YinArgs a;
     a.x = x; a.f0 = f0; a.cmnd = cmnd; a.curve = curve;
-    a.item = (long long)channels * time; a.series = cl ? 1 : time;
-    a.out_item = (long long)channels * frames; a.out_series = cl ? 1 : frames;
-    a.estride = cl ? channels : 1; a.out_stride = a.estride;
+    a.item = sx.item; a.chan = sx.chan; a.stride = sx.stride;
+    a.out_item = so.item; a.out_chan = so.chan; a.out_stride = so.stride;
     a.C = channels; a.time = (int)time; a.frames = (int)frames; a.runs = (int)runs; a.F = p.F;
     a.W = win_length; a.hop = hop; a.tau_min = tau_min; a.tau_hi = tau_hi;
     a.nb = p.nb; a.Q = p.Q; a.LP = p.LP; a.span = p.span;

@@ -61,9 +61,9 @@ struct LfArgs {
     double b0, b1, b2, na1, na2; // na = -a
     double sigma;                // +-1: carries are (z1 + sigma z2, -sigma z2)
     int len;                     // samples of a series
-    int stride;                  // elements between consecutive samples
+    int stride;                  // the series of x and out (kpr_series.h)
     int channels;
-    long long item, chan;        // elements between batch items / between the channels of one
+    long long item, chan;
     int n_seg, seg_steps;        // workgroups per series and the steps each walks
     LfTab tab;
 };
@@ -86,6 +86,7 @@ __global__ __launch_bounds__(64 * kLfWaves) void k_lfilter(const LfArgs a) {
     constexpr int L = kLfLane, W = kLfWaves;
     __shared__ double slab[2][W][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // (series_unit's decoding, written out: with the division after the early return the compiler keeps this prologue as tuned)
     const int series = blockIdx.x / a.n_seg, seg = blockIdx.x - series * a.n_seg;
     if (MODE == LF_ENDS && seg == (REV ? 0 : a.n_seg - 1)) return;               // nothing follows it
     const long long base = (long long)(series / a.channels) * a.item + (long long)(series % a.channels) * a.chan;

@@ -39,10 +39,10 @@ struct ResampleDirectArgs {
     int P, Q;                           // reduced rates of this direction
     int n_taps, H;                      // n_taps = 2 H
     int in_len, out_len;
-    int estride;                        // elements from one sample of a channel to the next (channels_last: C)
-    int groups;                         // signals per batch item: C, or C / 2 with NCH = 2
-    long long in_item, out_item;        // elements per batch item
-    long long in_group, out_group;      // elements from one signal of an item to the next
+    int stride;                         // the series of x and out (kpr_series.h): one stride for both
+    int groups;                         // series per batch item: C, or C / 2 pairs of interleaved channels with NCH = 2
+    long long in_item, out_item;
+    long long in_chan, out_chan;        // from one series (or pair) of an item to the next
     int per_lane;                       // outputs per lane
     int tile;                           // outputs per workgroup = threads * per_lane
     int tiles_per_signal;
@@ -69,12 +69,11 @@ template <int NCH>
 __global__ __launch_bounds__(kRdMaxThreads) void k_resample_direct(ResampleDirectArgs a) {
     extern __shared__ float rd_lds[];
     const int tid = threadIdx.x, n_threads = blockDim.x;
-    const int s = blockIdx.x / a.tiles_per_signal, tl = blockIdx.x - s * a.tiles_per_signal;
-    const int item_b = s / a.groups, g = s - item_b * a.groups;
-    const float* in = a.x + item_b * a.in_item + g * a.in_group;
-    float* out = a.out + item_b * a.out_item + g * a.out_group;
+    const SeriesUnit u = series_unit(a.tiles_per_signal, a.groups);
+    const float* in = u.at(a.x, a.in_item, a.in_chan);
+    float* out = u.at(a.out, a.out_item, a.out_chan);
 
-    const int i0 = tl * a.tile;                                          // (out_len < 2^30: no overflow)
+    const int i0 = u.unit * a.tile;                                      // (out_len < 2^30: no overflow)
     const long long a0 = ((long long)i0 * a.Q) / a.P;                    // uniform: the tile's first position
     const long long lo = a0 - a.H + 1;                                   // first staged sample (may be < 0, may lie past in_len)
 
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(kRdMaxThreads) void k_resample_direct(ResampleDirec
         const int i = w / NCH, ch = w - i * NCH;
         const long long gi = lo + i;
         float v = 0.0f;
-        if (gi >= 0 && gi < a.in_len) v = in[(int)gi * a.estride + ch];
+        if (gi >= 0 && gi < a.in_len) v = in[(int)gi * a.stride + ch];
         rd_lds[ch * a.lds_stride + i] = v;
     }
     __syncthreads();
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(kRdMaxThreads) void k_resample_direct(ResampleDirec
         }
         if (i < a.out_len) {
 #pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) out[i * a.estride + ch] = acc[ch];
+            for (int ch = 0; ch < NCH; ++ch) out[i * a.stride + ch] = acc[ch];
         }
         i += n_threads;
         rel += a.step_a;

@@ -4,7 +4,7 @@
 //   out[i] = sum_{k < n_taps} tab[i mod P][k] * in[(i div P) * Q + first[i mod P] + k],   in[.] = 0 outside 0 .. in_len - 1
 //
 // P = n_phases, Q = step.  Forward: (P, Q) = (new, orig); adjoint: (orig, new) with the adjoint's table (kpr_resample_table in
-// kapre_hip.hip, resample_support in kpr_host_ops.h).  Output i = b P + p is "block b, phase p"; all outputs of one phase share a row of the table.
+// kapre_hip.hip, resample_support in kpr_host_resample.h).  Output i = b P + p is "block b, phase p"; all outputs of one phase share a row of the table.
 //
 // A workgroup of 128 .. 512 lanes (the plan picks the count that leaves the fewest lanes without a work item) owns, for one
 // signal (or NCH = 2 interleaved channels of one), `nb` consecutive blocks x `pt` consecutive phases.  It stages the one contiguous input span those outputs read into LDS -- coalesced loads, interleaved
@@ -40,10 +40,10 @@ struct ResampleArgs {
     const int* first;                   // (P)
     int P, Q, n_taps;
     int in_len, out_len;
-    int estride;                        // elements from one sample of a channel to the next (channels_last: C)
-    int groups;                         // signals per batch item: C, or C / 2 with NCH = 2
-    long long in_item, out_item;        // elements per batch item
-    long long in_group, out_group;      // elements from one signal of an item to the next
+    int stride;                         // the series of x and out (kpr_series.h): one stride for both
+    int groups;                         // series per batch item: C, or C / 2 pairs of interleaved channels with NCH = 2
+    long long in_item, out_item;
+    long long in_chan, out_chan;        // from one series (or pair) of an item to the next
     int pt, n_pt;                       // phases per workgroup, phase tiles
     int ng, nb;                         // block groups and blocks per workgroup (nb <= 8 ng)
     int n_blocks;                       // ceil(out_len / P)
@@ -55,11 +55,10 @@ template <int NCH>
 __global__ __launch_bounds__(kRsMaxThreads) void k_resample(ResampleArgs a) {
     extern __shared__ float rs_lds[];
     const int tid = threadIdx.x, n_threads = blockDim.x;
-    const int s = blockIdx.x / a.tiles_per_signal, t = blockIdx.x - s * a.tiles_per_signal;
-    const int bt = t / a.n_pt, ptile = t - bt * a.n_pt;
-    const int item_b = s / a.groups, g = s - item_b * a.groups;
-    const float* in = a.x + item_b * a.in_item + g * a.in_group;
-    float* out = a.out + item_b * a.out_item + g * a.out_group;
+    const SeriesUnit u = series_unit(a.tiles_per_signal, a.groups);
+    const int bt = u.unit / a.n_pt, ptile = u.unit - bt * a.n_pt;
+    const float* in = u.at(a.x, a.in_item, a.in_chan);
+    float* out = u.at(a.out, a.out_item, a.out_chan);
 
     const int p0 = ptile * a.pt, p1 = min(p0 + a.pt, a.P) - 1;
     const int b0 = bt * a.nb, nb = min(a.nb, a.n_blocks - b0);
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(kRsMaxThreads) void k_resample(ResampleArgs a) {
         const int i = w / NCH, ch = w - i * NCH;
         const int gi = lo + i;
         float v = 0.0f;
-        if (gi >= 0 && gi < a.in_len) v = in[gi * a.estride + ch];
+        if (gi >= 0 && gi < a.in_len) v = in[gi * a.stride + ch];
         rs_lds[ch * a.lds_stride + i] = v;
     }
     __syncthreads();
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(kRsMaxThreads) void k_resample(ResampleArgs a) {
                 const int m = (b0 + bj) * a.P + p;                      // (b0 + bj < n_blocks: at most out_len + P - 1)
                 if (m < a.out_len) {
 #pragma unroll
-                    for (int ch = 0; ch < NCH; ++ch) out[m * a.estride + ch] = acc[ch][j];
+                    for (int ch = 0; ch < NCH; ++ch) out[m * a.stride + ch] = acc[ch][j];
                 }
             }
         }

@@ -42,9 +42,9 @@ struct YinArgs {
     float* f0;
     float* cmnd;
     float* curve;                       // (series, frames, tau_hi + 1) or NULL
-    long long item, series;             // elements per batch item; from one channel's series to the next
-    long long out_item, out_series;     // the same for f0 / cmnd
-    int estride, out_stride;            // elements from one sample / frame of a series to the next
+    long long item, chan;               // the series of x (kpr_series.h)
+    long long out_item, out_chan;       // the same for f0 / cmnd, whose series are the frames
+    int stride, out_stride;
     int C, time, frames, runs, F;       // runs per series = ceil(frames / F)
     int W, hop, tau_min, tau_hi;
     int nb;                             // shared: W / hop
@@ -78,16 +78,14 @@ __attribute__((target("no-packed-fp32-ops"))) __global__ __launch_bounds__(kYinT
     float* xs = yin_lds;                                                 // the span
     float* sums = xs + a.span;                                           // rows of LP floats: s(m, .) or d_m(.)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int s = blockIdx.x / a.runs, run = blockIdx.x - s * a.runs;
-    const int item_b = s / a.C, ch = s - item_b * a.C;
-    const int t0 = run * a.F;
-    const int fv = min(a.F, a.frames - t0);                              // frames of this run
-    const float* in = a.x + item_b * a.item + ch * a.series;
+    const SeriesUnit u = series_unit(a.runs, a.C);                       // unit: the run
+    const float* in = u.at(a.x, a.item, a.chan);
+    const auto [t0, fv] = frame_run(u.unit, a.F, a.frames);
     const long long g0 = (long long)t0 * a.hop;
 
     for (int i = tid; i < a.span; i += kYinThreads) {
         const long long gi = g0 + i;
-        xs[i] = gi < a.time ? in[gi * a.estride] : 0.0f;
+        xs[i] = gi < a.time ? in[gi * a.stride] : 0.0f;
     }
     __syncthreads();
 
@@ -193,12 +191,12 @@ __attribute__((target("no-packed-fp32-ops"))) __global__ __launch_bounds__(kYinT
             }
             const float f0 = __fdiv_rn(a.sr, __fadd_rn((float)best, shift));
             if (lane == 0) {
-                const long long o = item_b * a.out_item + ch * a.out_series + (long long)(t0 + t) * a.out_stride;
+                const long long o = u.off(a.out_item, a.out_chan) + (long long)(t0 + t) * a.out_stride;
                 a.f0[o] = frame_bad ? nan : f0;
                 a.cmnd[o] = frame_bad ? nan : y0;
             }
             if (a.curve) {
-                float* cv = a.curve + ((long long)s * a.frames + t0 + t) * nl;
+                float* cv = a.curve + ((long long)u.s * a.frames + t0 + t) * nl;
                 for (int tau = lane; tau < nl; tau += 64) cv[tau] = frame_bad ? nan : yrow[tau];
             }
         }
