@@ -165,6 +165,8 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *                  within the error bound of each other, not bit-identical)
  *   "cqt_chunk"    0 = automatic (default) | n = kpr_cqt_f32 stages at most n taps (rounded up to 16) of a frame at once (tests: the
  *                  multi-chunk path at small shapes; results within the error bound of each other, not bit-identical)
+ *   "cqt_adjoint_rows" 0 = automatic (default) | n = kpr_cqt_adjoint_f32 stages at most n rows of the cotangent at once (at least a
+ *                  run: kpr_cqt_adjoint_plan; tests: the chunked reduction at small shapes; within the error bound, not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -897,6 +899,32 @@ int kpr_cqt_plan(const int32_t* lengths, int n_bins, int hop, int* frames_per_ru
 int kpr_cqt_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
                 const float* table, int64_t table_floats, int hop, int center, int pad_end, int out_layout, int magnitude, void* out,
                 kpr_stream_t stream);
+
+/* ---- The adjoint of CQT (its backward pass): the cotangent of the complex spectrogram back to the waveform -------------------------
+ * With B[tau][2 k] = Re w_k[tau - off_k], B[tau][2 k + 1] = -Im w_k[tau - off_k] (zero outside bin k's taps [off_k, off_k + N_k)) and
+ * G2[t][2 k] = dl/dRe C[t, k], G2[t][2 k + 1] = dl/dIm C[t, k] (g: complex64 read as float pairs, torch's convention):
+ *   gx[s] = sum_t sum_c G2[t][c] B[s - o - t hop][c],    0 <= s < time,    o and the frames as kpr_cqt_f32 defines them.
+ * Along the hop, s = o + q hop + r (0 <= r < hop), D = ceil(L / hop):  gx[o + q hop + r] = sum_{d < D} sum_c G2[q - d][c] B[d hop + r][c]
+ * -- a matrix product of hop blocks q by offsets r on the matrix units (k_cqt_adj), one launch, no atomics, nothing allocated: the same
+ * inputs give the same bits; capturable.  Every gx[s] is stored exactly once; a sample that no kernel covers is +0.0.
+ * table (DEVICE, 16-byte aligned): depends on the hop.  Rt = ceil(min(hop, L) / 16) r-tiles of 16 offsets, T tiles of 8 bins (the
+ *   forward's [lo_j, hi_j)).  For (rt, j) the fragments are the d with [d hop + 16 rt, + w) meeting [lo_j, hi_j), w = min(16, hop - 16 rt):
+ *   d_lo = max(0, ceil((lo_j - 16 rt - w + 1) / hop)) <= d < floor((hi_j - 1 - 16 rt) / hop) + 1.  A header of Rt x T entries of four
+ *   int32 {first fragment, d_lo, number of d, 0} at entry rt T + j; then the fragments, rt ascending, j ascending, d ascending, 64 x 4
+ *   floats each: float 4 l + e is B[d hop + 16 rt + (l & 15)][16 j + 4 (l >> 4) + e], zero where 16 rt + (l & 15) >= hop.
+ *   table_floats = 4 Rt T + 256 (number of fragments), checked; the header's numbers are clamped to the table by the kernel.
+ * g: complex64 (batch, frames, n_bins, channels) [g_layout LAST] or (batch, channels, frames, n_bins) [FIRST]; gx: float32 in `layout`.
+ * A NaN / Inf in g[t, k] reaches only the samples o + t hop - 15 <= s < o + t hop + L + 15.
+ * Error: |gx[s] - exact| <= (M_s + 4) 2^-24 sum |G2[t][c]| |B[s - o - t hop][c]|, M_s the number of (t, c) whose kernel covers s.
+ * Refusals as kpr_cqt_f32 (g 8, table 16, gx 4 bytes aligned); 2^31 or more hop blocks: KPR_E_UNSUPPORTED.  batch, channels or
+ * time == 0: returns 0, launches nothing; no frames: gx is zeros.
+ * kpr_cqt_adjoint_plan (host only): the hop blocks of one series a workgroup takes as a run (64, 32 or 16), the cotangent rows staged
+ * in LDS at once (option "cqt_adjoint_rows" caps them; fewer than run + D - 1: the reduction runs in chunks of d) and the number of
+ * work items (an r-tile times a group of row tiles, dealt to the eight waves). */
+int kpr_cqt_adjoint_plan(const int32_t* lengths, int n_bins, int hop, int* blocks_per_run, int* rows, int* work_items);
+int kpr_cqt_adjoint_f32(const void* g, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
+                        const float* table, int64_t table_floats, int hop, int center, int pad_end, int g_layout, float* gx,
+                        kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

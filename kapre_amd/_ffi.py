@@ -257,6 +257,11 @@ EXPORTS = {
     "kpr_cqt_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_cqt_adjoint_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "kpr_cqt_adjoint_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1295,3 +1300,71 @@ def cqt(x, fmt, out_fmt, lengths, table, hop, center, pad_end, magnitude):
     _call("kpr_cqt_f32", x.device, ptr(x), b, c, t, layout(fmt), n.ctypes.data_as(ctypes.c_void_p), len(n), ptr(table),
           int(table.numel()), int(hop), int(bool(center)), int(bool(pad_end)), layout(out_fmt), int(bool(magnitude)), ptr(out))
     return out
+
+
+def cqt_adjoint_ranges(lengths, hop: int):
+    """[[(d_lo, n_d)] per tile] per r-tile of kpr_cqt_adjoint_f32's table: the d whose 16 taps d hop + 16 rt ... meet the tile's
+    tap range (include/kapre_hip.h)."""
+    hop, L = int(hop), int(lengths[0])
+    out = []
+    for rt in range(-(-min(hop, L) // 16)):
+        w, row = min(16, hop - 16 * rt), []
+        for lo, hi in cqt_tiles(lengths):
+            d_lo = max(0, -(-(lo - 16 * rt - w + 1) // hop))
+            row.append((d_lo, max(0, (hi - 1 - 16 * rt) // hop + 1 - d_lo) if hi - 1 - 16 * rt >= 0 else 0))
+        out.append(row)
+    return out
+
+
+def cqt_pack_adjoint(lengths, kernels, hop: int) -> np.ndarray:
+    """The table of kpr_cqt_adjoint_f32 for this hop from the ragged complex kernels: the header, per (r-tile, tile) four int32
+    {first fragment, d_lo, n_d, 0} stored in the float array bit for bit, then per fragment 64 x 4 floats, float 4 l + e =
+    B[d hop + 16 rt + (l & 15)][16 j + 4 (l >> 4) + e]; zeros outside a bin's taps, past the last bin and at offsets >= hop."""
+    hop, L, K = int(hop), int(lengths[0]), len(lengths)
+    ntiles = -(-K // CQT_TILE_BINS)
+    dense = np.zeros((L, 16 * ntiles), np.float32)                       # B[tap][column]
+    for k in range(K):
+        off = (L - int(lengths[k])) // 2
+        dense[off:off + int(lengths[k]), 2 * k] = np.real(kernels[k])
+        dense[off:off + int(lengths[k]), 2 * k + 1] = -np.imag(kernels[k])
+    header, frags = [], []
+    for rt, row in enumerate(cqt_adjoint_ranges(lengths, hop)):
+        w = min(16, hop - 16 * rt)
+        for j, (d_lo, n_d) in enumerate(row):
+            header.append((len(frags), d_lo, n_d, 0))
+            for d in range(d_lo, d_lo + n_d):
+                taps = np.zeros((16, 16), np.float32)                    # [n][column of the tile]
+                t0 = d * hop + 16 * rt
+                n1 = max(0, min(w, L - t0))
+                taps[:n1] = dense[t0:t0 + n1, 16 * j:16 * j + 16]
+                frags.append(taps.reshape(16, 4, 4).transpose(1, 0, 2).reshape(-1))          # [n][kq][e] -> [kq][n][e]
+    head = np.asarray(header, np.int32).reshape(-1).view(np.float32)
+    return np.concatenate([head] + frags) if frags else head
+
+
+def cqt_adjoint_plan(lengths, hop: int):
+    """(blocks_per_run, rows, work_items) of kpr_cqt_adjoint_f32 for these kernel lengths and hop under the current
+    ``cqt_adjoint_rows`` (host only).  ``ValueError`` for lengths or a hop outside the limits, and for a plan that is refused."""
+    n = np.ascontiguousarray(lengths, np.int32)
+    f, rows, items = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().kpr_cqt_adjoint_plan(n.ctypes.data_as(ctypes.c_void_p), len(n), int(hop), ctypes.byref(f), ctypes.byref(rows),
+                                    ctypes.byref(items))
+    if rc in (E_BADARG, E_UNSUPPORTED):
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_cqt_adjoint_plan")
+    return f.value, rows.value, items.value
+
+
+def cqt_adjoint(g, g_fmt, x_fmt, time, lengths, table, hop, center, pad_end):
+    """The adjoint of ``cqt``: the complex64 cotangent ``g`` of the spectrogram (layout ``g_fmt``) with the packed adjoint
+    ``table`` (device, ``cqt_pack_adjoint`` of this hop) -> the float32 cotangent of the waveform of ``time`` samples in the
+    layout ``x_fmt``.  One launch; every sample is written."""
+    import torch
+    b, c, frames, k = dims_of(g.shape, g_fmt)
+    n = np.ascontiguousarray(lengths, np.int32)
+    if k != len(n) or frames != max(0, cqt_frames(time, n[0], hop, center, pad_end)):
+        raise ValueError('cqt_adjoint: a cotangent of %d frames x %d bins does not belong to %d samples' % (frames, k, time))
+    gx = torch.empty(shape_of(x_fmt, b, c, int(time)), dtype=torch.float32, device=g.device)
+    _call("kpr_cqt_adjoint_f32", g.device, ptr(g), b, c, int(time), layout(x_fmt), n.ctypes.data_as(ctypes.c_void_p), len(n),
+          ptr(table), int(table.numel()), int(hop), int(bool(center)), int(bool(pad_end)), layout(g_fmt), ptr(gx))
+    return gx

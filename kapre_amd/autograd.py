@@ -495,7 +495,22 @@ def _functions():
             gx, _ = _ffi.add_noise_bwd(g, x, ctx.data_format, ctx.bank, ctx.lengths, table, stats)
             return gx, None, None, None, None
 
-    _FN = dict(add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
+    class CqtFn(torch.autograd.Function):
+        """C = CQT(x), a linear map of the waveform onto (Re C, Im C): backward = its adjoint on the cotangent's float pairs
+        (one launch of k_cqt_adj).  ``tables``: the forward's packed table and the adjoint's of this hop."""
+
+        @staticmethod
+        def forward(ctx, x, data_format, out_format, lengths, tables, hop, center, pad_end):
+            ctx.args = (out_format, data_format, _ffi.dims_of(x.shape, data_format)[2], lengths, tables[1], hop, center, pad_end)
+            return _ffi.cqt(x.detach(), data_format, out_format, lengths, tables[0], hop, center, pad_end, False)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            g = g.contiguous().to(torch.complex64)
+            return (_ffi.cqt_adjoint(g, *ctx.args),) + (None,) * 7
+
+    _FN = dict(cqt=CqtFn, add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
                mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn,
                resample_direct=ResampleDirectFn)
@@ -583,6 +598,10 @@ def lfilter(x, data_format, plan):
 
 def convolve(x, data_format, plan, idx, first, n_out):
     return _functions()['convolve'].apply(x, data_format, plan, idx, first, n_out)
+
+
+def cqt(x, data_format, out_format, lengths, tables, hop, center, pad_end):
+    return _functions()['cqt'].apply(x, data_format, out_format, lengths, tables, hop, center, pad_end)
 
 
 def add_noise(x, data_format, bank, lengths, table):

@@ -1385,15 +1385,53 @@ def cqt_kernels(sample_rate, fmin=32.70319566, n_bins=84, bins_per_octave=12, fi
 _CQT_CONSTS = _ffi.DeviceConstants(max_entries=16)      # the packed tables of backend.cqt (the layer keeps its own)
 
 
-def _cqt_run(x, consts, bank, lengths, hop_length, center, pad_end, fmt, out_fmt, output):
-    """``x`` (rank 3) through kpr_cqt_f32; ``bank``: the hashable arguments of ``cqt_kernels``, the key of the packed table."""
+def _cqt_run(x, consts, bank, lengths, hop_length, center, pad_end, fmt, out_fmt, output, differentiable=False):
+    """``x`` (rank 3) through kpr_cqt_f32; ``bank``: the hashable arguments of ``cqt_kernels``, the key of the packed table.
+    ``differentiable`` and an input that needs a gradient: the complex transform on the tape (``autograd.cqt``, backward
+    kpr_cqt_adjoint_f32), then ``Magnitude`` and its own backward pass where ``output`` asks for magnitudes."""
     import torch
     from . import autograd
     autograd.refuse(x, 3, 'CQT expects a rank-3 waveform batch, got shape %s', TypeError,
                     'CQT has a float32 kernel only; got a float64 input (cast it to float32)')
+    pack = lambda: _ffi.cqt_pack(lengths, cqt_kernels(*bank)[2])
+    if differentiable and autograd.needs_grad(x):
+        x = autograd.prep(x, 'float32')
+        tables = (consts.get(('cqt',) + bank, x.device, pack), _cqt_adjoint_table(consts, bank, lengths, hop_length, x.device))
+        y = autograd.cqt(x, fmt, out_fmt, lengths, tables, hop_length, center, pad_end)
+        if output == 'magnitude':
+            from .time_frequency import Magnitude
+            y = Magnitude(name='cqt_magnitude')(y)
+        return y
     x = _ffi.as_device(x.detach() if isinstance(x, torch.Tensor) else x, torch.float32)
-    table = consts.get(('cqt',) + bank, x.device, lambda: _ffi.cqt_pack(lengths, cqt_kernels(*bank)[2]))
+    table = consts.get(('cqt',) + bank, x.device, pack)
     return _ffi.cqt(x, fmt, out_fmt, lengths, table, hop_length, center, pad_end, output == 'magnitude')
+
+
+def _cqt_adjoint_table(consts, bank, lengths, hop_length, device):
+    """the packed adjoint table of (bank, hop) on ``device``, cached in ``consts``"""
+    return consts.get(('cqt_adjoint', int(hop_length)) + bank, device,
+                      lambda: _ffi.cqt_pack_adjoint(lengths, cqt_kernels(*bank)[2], hop_length))
+
+
+def cqt_adjoint(g, time, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1,
+                window_name=None, norm=1, scale=True, center=False, pad_end=False, input_data_format='default',
+                output_data_format='default'):
+    """The adjoint of ``cqt`` with the same arguments (its backward pass as a function): the complex64 cotangent ``g`` of the
+    spectrogram, (b, frames, n_bins, ch) / (b, ch, frames, n_bins) as ``output_data_format`` says, -> the float32 cotangent
+    of the waveform of ``time`` samples, (b, time, ch) / (b, ch, time) as ``input_data_format`` says:
+    gx[s] = sum_{t, k} Re g[t, k] Re w_k[n] + Im g[t, k] (-Im w_k[n]), n = s - o - t hop - off_k inside [0, N_k).
+    One launch (kpr_cqt_adjoint_f32); the same inputs give the same bits."""
+    import torch
+    for fmt in (input_data_format, output_data_format):
+        validate_data_format_str(fmt)
+    bank, lengths = cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, window_name, norm, scale,
+                                   'complex')
+    if len(g.shape) != 4:
+        raise ValueError('cqt_adjoint expects a rank-4 cotangent, got shape %s' % (tuple(g.shape),))
+    g = _ffi.as_device(g.detach() if isinstance(g, torch.Tensor) else g, torch.complex64)
+    table = _cqt_adjoint_table(_CQT_CONSTS, bank, lengths, int(hop_length), g.device)
+    return _ffi.cqt_adjoint(g, resolve_data_format(output_data_format), resolve_data_format(input_data_format), int(time), lengths,
+                            table, int(hop_length), bool(center), bool(pad_end))
 
 
 def cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, window_name, norm, scale, output):
@@ -1409,17 +1447,18 @@ def cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filte
 
 def cqt(x, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1, window_name=None,
         norm=1, scale=True, center=False, pad_end=False, output='complex', input_data_format='default',
-        output_data_format='default'):
+        output_data_format='default', differentiable=False):
     """Constant-Q transform of a waveform batch on the GPU (``kapre_amd.CQT`` as a function): bin k has its own window of
     N_k = ceil(Q sr / f_k) samples, centred in the frame of N_0 samples, C[t, k] = sum_n x[o + t hop + off_k + n] conj(w_k[n]).
     Frame t starts at sample t hop (``center=False``, this library's convention; ``pad_end`` as in ``STFT``) or at
     t hop - N_0 // 2 (``center=True``, 1 + time // hop frames); samples outside the signal are zeros.  (b, time, ch) /
     (b, ch, time) float32 -> complex64 (b, frames, n_bins, ch) / (b, ch, frames, n_bins), or float32 ``|C|`` with
-    ``output='magnitude'``.  One launch (kpr_cqt_f32), no gradient.  ``ValueError`` for the limits of ``cqt_kernels``,
-    ``TypeError`` for float64."""
+    ``output='magnitude'``.  One launch (kpr_cqt_f32).  ``differentiable=True``: an input that requires grad gets its gradient
+    through the adjoint kernel (kpr_cqt_adjoint_f32; magnitudes: the complex transform, then ``Magnitude``, two launches);
+    the default detaches it.  ``ValueError`` for the limits of ``cqt_kernels``, ``TypeError`` for float64."""
     for fmt in (input_data_format, output_data_format):
         validate_data_format_str(fmt)
     bank, lengths = cqt_parameters(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, window_name, norm, scale,
                                    output)
     return _cqt_run(x, _CQT_CONSTS, bank, lengths, int(hop_length), bool(center), bool(pad_end),
-                    resolve_data_format(input_data_format), resolve_data_format(output_data_format), output)
+                    resolve_data_format(input_data_format), resolve_data_format(output_data_format), output, bool(differentiable))

@@ -255,13 +255,14 @@ def get_cqt_layer(
     input_data_format='default',
     output_data_format='default',
     name='cqt',
+    differentiable=False,
 ):
     """``Sequential([CQT(output='magnitude'), (MagnitudeToDecibel)])``: a waveform batch in, the constant-Q magnitude
     spectrogram out, (batch, frames, n_bins, ch) or (batch, ch, frames, n_bins) (this package's own; ``abs(librosa.cqt)``
-    on frames that are not centred unless ``center``)."""
+    on frames that are not centred unless ``center``).  ``differentiable``: ``CQT``'s argument of that name."""
     args = dict(sample_rate=sample_rate, hop_length=hop_length, fmin=fmin, n_bins=n_bins, bins_per_octave=bins_per_octave,
                 filter_scale=filter_scale, window_name=window_name, center=center, pad_end=pad_end, output='magnitude',
-                input_data_format=input_data_format, output_data_format=output_data_format)
+                input_data_format=input_data_format, output_data_format=output_data_format, differentiable=differentiable)
     if input_shape is not None:
         args['input_shape'] = input_shape
     chain = Sequential(name=name)

@@ -61,9 +61,11 @@
 //   kpr_cqt_kernels.h         constant-Q transform of a waveform (time_frequency.CQT): an implicit GEMM on the matrix units -- rows
 //                             are the frames of a run staged once in LDS, columns the (Re, -Im) of eight bins with their own tap
 //                             range, the reduction split over the waves and added in a fixed order, complex or magnitude epilogue
+//   kpr_cqt_adj_kernels.h     its adjoint (the backward pass of CQT): the same product along the hop -- rows are hop blocks, columns the
+//                             offsets inside a hop, a table of fragments per hop --, the accumulators of an item owned by one wave
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_resample.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h, kpr_host_cqt_adj.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -119,6 +121,7 @@
 #include "kpr_mix_kernels.h"
 #include "kpr_yin_kernels.h"
 #include "kpr_cqt_kernels.h"
+#include "kpr_cqt_adj_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -133,6 +136,7 @@
 #include "kpr_host_mix.h"
 #include "kpr_host_yin.h"
 #include "kpr_host_cqt.h"
+#include "kpr_host_cqt_adj.h"
 
 // ==========================================================================================
 // C ABI
@@ -191,7 +195,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536, 65536};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -700,6 +704,22 @@ int kpr_cqt_f32(const float* x, int64_t batch, int channels, int64_t time, int l
     if (int e = api_enter()) return e;
     return run_cqt(x, batch, channels, time, layout, lengths, n_bins, table, table_floats, hop, center, pad_end, out_layout, magnitude,
                    out, stream);
+}
+int kpr_cqt_adjoint_plan(const int32_t* lengths, int n_bins, int hop, int* blocks_per_run, int* rows, int* work_items) {
+    if (!blocks_per_run || !rows || !work_items) return fail(KPR_E_BADARG, "blocks_per_run / rows / work_items must not be NULL");
+    CqtAdjPlan p;
+    if (int e = cqt_adj_plan(lengths, n_bins, hop, &p)) return e;
+    *blocks_per_run = p.F;
+    *rows = p.rows;
+    *work_items = p.items;
+    return 0;
+}
+int kpr_cqt_adjoint_f32(const void* g, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
+                        const float* table, int64_t table_floats, int hop, int center, int pad_end, int g_layout, float* gx,
+                        kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_cqt_adjoint(g, batch, channels, time, layout, lengths, n_bins, table, table_floats, hop, center, pad_end, g_layout, gx,
+                           stream);
 }
 
 }  // extern "C"

@@ -1117,13 +1117,22 @@ class CQT(Layer):
     'channels_last', (batch, ch, frames, n_bins) for 'channels_first': the layouts ``STFT`` writes, so ``Magnitude``, ``Phase``,
     ``MagnitudeToDecibel``, ``HPSS``, ``SpecAugment`` chain behind it.  ``output='magnitude'`` gives float32 ``|C|`` from the
     same launch.  One launch of ``k_cqt`` (kpr_cqt_f32): an implicit GEMM on the matrix units; the same inputs give the same
-    bits.  float32 only (a float64 input raises ``TypeError``).  The output carries no gradient -- the adjoint is a scatter
-    that is not built yet -- and an input that requires grad is detached.  ``ValueError`` where the highest bin's band
-    f_{K-1} (1 + 1 / (2 Q)) passes sr / 2, where L > 65536 or N_{K-1} < 2."""
+    bits.  float32 only (a float64 input raises ``TypeError``).
+
+    ``differentiable=False`` (the default): the output carries no gradient and an input that requires grad is detached.
+    ``differentiable=True``: an input that requires grad gets its gradient through one launch of ``k_cqt_adj``
+    (kpr_cqt_adjoint_f32), the adjoint as a matrix product of hop blocks by offsets inside a hop on the same matrix
+    instruction, once differentiable, the same bits every time; |gx - exact| <= (M_s + 4) 2^-24 sum |g| |w| per sample
+    (DESIGN 4.22).  ``output='magnitude'`` is then this layer's complex output followed by ``Magnitude`` and its backward
+    pass, two launches (the fused magnitude keeps no phase).  Without a gradient to carry (numpy input, ``no_grad``) the
+    layer launches what the default launches.
+
+    ``ValueError`` where the highest bin's band f_{K-1} (1 + 1 / (2 Q)) passes sr / 2, where L > 65536 or N_{K-1} < 2, and
+    with ``differentiable=True`` where the adjoint's launch plan is refused."""
 
     def __init__(self, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_octave=12, filter_scale=1,
                  window_name=None, norm=1, scale=True, center=False, pad_end=False, output='complex',
-                 input_data_format='default', output_data_format='default', **kwargs):
+                 input_data_format='default', output_data_format='default', differentiable=False, **kwargs):
         super(CQT, self).__init__(**kwargs)
         for data_format in (input_data_format, output_data_format):
             backend.validate_data_format_str(data_format)
@@ -1132,6 +1141,9 @@ class CQT(Layer):
         self.sample_rate, self.hop_length, self.fmin, self.n_bins = sample_rate, int(hop_length), fmin, int(n_bins)
         self.bins_per_octave, self.filter_scale, self.window_name, self.norm = bins_per_octave, filter_scale, window_name, norm
         self.scale, self.center, self.pad_end, self.output = bool(scale), bool(center), bool(pad_end), output
+        self.differentiable = bool(differentiable)
+        if self.differentiable:
+            _ffi.cqt_adjoint_plan(self._lengths, self.hop_length)        # ValueError for a plan the kernel refuses
         self.input_data_format_original = input_data_format
         self.output_data_format_original = output_data_format
         self.input_data_format = backend.resolve_data_format(input_data_format)
@@ -1151,7 +1163,7 @@ class CQT(Layer):
 
     def call(self, x):
         return backend._cqt_run(x, self._consts, self._bank, self._lengths, self.hop_length, self.center, self.pad_end,
-                                self.input_data_format, self.output_data_format, self.output)
+                                self.input_data_format, self.output_data_format, self.output, self.differentiable)
 
     def get_config(self):
         config = super(CQT, self).get_config()
@@ -1159,7 +1171,7 @@ class CQT(Layer):
                        'bins_per_octave': self.bins_per_octave, 'filter_scale': self.filter_scale,
                        'window_name': self.window_name, 'norm': self.norm, 'scale': self.scale, 'center': self.center,
                        'pad_end': self.pad_end, 'output': self.output, 'input_data_format': self.input_data_format_original,
-                       'output_data_format': self.output_data_format_original})
+                       'output_data_format': self.output_data_format_original, 'differentiable': self.differentiable})
         return config
 
 
