@@ -167,6 +167,9 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *                  multi-chunk path at small shapes; results within the error bound of each other, not bit-identical)
  *   "cqt_adjoint_rows" 0 = automatic (default) | n = kpr_cqt_adjoint_f32 stages at most n rows of the cotangent at once (at least a
  *                  run: kpr_cqt_adjoint_plan; tests: the chunked reduction at small shapes; within the error bound, not bit-identical)
+ *   "fb_wgrad_rows" 0 = automatic (default) | n = kpr_filterbank_wgrad_f32 cuts the rows into slabs of at most n rows, rounded up to the
+ *                  chunk (kpr_filterbank_wgrad_plan; tests: the slab seam and the reduce launch at small shapes; within the error
+ *                  bound of each other, not bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -925,6 +928,29 @@ int kpr_cqt_adjoint_plan(const int32_t* lengths, int n_bins, int hop, int* block
 int kpr_cqt_adjoint_f32(const void* g, int64_t batch, int channels, int64_t time, int layout, const int32_t* lengths, int n_bins,
                         const float* table, int64_t table_floats, int hop, int center, int pad_end, int g_layout, float* gx,
                         kpr_stream_t stream);
+
+/* ---- The weight gradient of a filterbank applied along the frequency axis (TrainableFilterbank's backward pass) ---------------------
+ * With y = x . W (kpr_apply_filterbank_f32, W (n_freq, n_filt)) and g the cotangent of y, both float32 in `layout`:
+ *   gW[f][m] = sum_{b, c, t} x[b, c, t, f] g[b, c, t, m]        (the channels are summed into the one matrix)
+ * on v_mfma_f32_16x16x4_f32 (k_fb_wgrad): tiles of 64 bins x up to 128 filters (more filters: further column passes) times slabs of
+ * S rows; a tile's accumulators belong to one wave from the slab's first row to the store; no atomics.  One slab: gW is written
+ * directly.  Several: each slab writes its own matrix into `workspace` and k_fb_wgrad_reduce adds them in ascending slab order.
+ * The slab count depends on the shape and option "fb_wgrad_rows" only: the same inputs give the same bits.  Capturable.
+ * Rows past the end, bins past n_freq and filters past n_filt enter the product as +0.0 (set bit-wise, never by a multiplication):
+ * a NaN in x[., f0] reaches row f0 of gW, an Inf in g[., m0] column m0, nothing else.
+ * Error: |gW[f][m] - exact| <= gamma_K sum |x||g|, gamma_K = K u / (1 - K u), u = 2^-24, K = S c' + n_slabs + 1 with c' = channels
+ * for CHANNELS_LAST (a row holds its channels: c' steps of the chain), 1 for CHANNELS_FIRST.
+ * kpr_filterbank_wgrad_plan (host only): `rows` = batch x channels x frames for CHANNELS_FIRST, batch x frames for CHANNELS_LAST;
+ *   out[0 ... 3] = bins per tile, S, n_slabs (0 without rows), column passes.  S n_slabs >= rows.
+ * kpr_filterbank_wgrad_workspace_bytes: 4 n_slabs n_freq n_filt where n_slabs > 1, else 0; negative for arguments the plan refuses.
+ * Refusals: sizes < 1 (batch, frames < 0), a bad layout, NULL or misaligned pointers (x, g, gw 4, workspace 16 bytes), overlap with
+ * gw or the workspace: KPR_E_BADARG; a short workspace: KPR_E_WORKSPACE; more interleaved channels than four rows of a tile leave
+ * room for in the staging registers (channels x min(n_filt, 128) > 1024, or channels > 16), 2^31 workgroups: KPR_E_UNSUPPORTED.
+ * batch or frames == 0: gW is zeros (one launch of k_fb_wgrad_reduce). */
+int kpr_filterbank_wgrad_plan(int64_t rows, int n_freq, int n_filt, int channels, int layout, int* out);
+int64_t kpr_filterbank_wgrad_workspace_bytes(int64_t rows, int n_freq, int n_filt, int channels, int layout);
+int kpr_filterbank_wgrad_f32(const float* x, const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int n_filt,
+                             int layout, void* workspace, int64_t workspace_bytes, float* gw, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

@@ -19,6 +19,7 @@ from .time_frequency import (
     Phase,
     MagnitudeToDecibel,
     ApplyFilterbank,
+    TrainableFilterbank,
     Delta,
     ConcatenateFrequencyMap,
     PCEN,
@@ -93,6 +94,7 @@ __all__ = [
     'Phase',
     'MagnitudeToDecibel',
     'ApplyFilterbank',
+    'TrainableFilterbank',
     'Delta',
     'ConcatenateFrequencyMap',
     'PCEN',

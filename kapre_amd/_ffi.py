@@ -262,6 +262,13 @@ EXPORTS = {
     "kpr_cqt_adjoint_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_filterbank_wgrad_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_int)]),
+    "kpr_filterbank_wgrad_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                              ctypes.c_int]),
+    "kpr_filterbank_wgrad_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1368,3 +1375,43 @@ def cqt_adjoint(g, g_fmt, x_fmt, time, lengths, table, hop, center, pad_end):
     _call("kpr_cqt_adjoint_f32", g.device, ptr(g), b, c, int(time), layout(x_fmt), n.ctypes.data_as(ctypes.c_void_p), len(n),
           ptr(table), int(table.numel()), int(hop), int(bool(center)), int(bool(pad_end)), layout(g_fmt), ptr(gx))
     return gx
+
+
+def _wgrad_rows(b, c, frames, fmt):
+    """the rows of kpr_filterbank_wgrad_f32's reduction: channels_last folds the channels into a row"""
+    return int(b) * int(frames) * (1 if is_channels_last(fmt) else int(c))
+
+
+def filterbank_wgrad_plan(rows: int, n_freq: int, n_filt: int, channels: int, fmt):
+    """(bins per tile, S, n_slabs, column passes) of kpr_filterbank_wgrad_f32 for ``rows`` rows (batch x channels x frames for
+    channels_first, batch x frames for channels_last) under the current ``fb_wgrad_rows`` (host only).  ``ValueError`` for
+    sizes below 1 and for a plan that is refused."""
+    out = (ctypes.c_int * 4)()
+    rc = lib().kpr_filterbank_wgrad_plan(int(rows), int(n_freq), int(n_filt), int(channels), layout(fmt), out)
+    if rc in (E_BADARG, E_UNSUPPORTED):
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_filterbank_wgrad_plan")
+    return tuple(out)
+
+
+def filterbank_wgrad(x, g, fmt):
+    """gW[f][m] = sum over batch, channels and frames of x[..., f] g[..., m]: the float32 rank-4 input ``x`` of a filterbank
+    applied along the frequency axis and the cotangent ``g`` of its output (both contiguous, on the device, layout ``fmt``)
+    -> the (n_freq, n_filt) cotangent of the matrix.  One launch of k_fb_wgrad, and k_fb_wgrad_reduce where the rows are cut
+    into several slabs; the same inputs give the same bits."""
+    import torch
+    if len(x.shape) != 4 or len(g.shape) != 4:
+        raise ValueError('filterbank_wgrad expects rank-4 tensors, got shapes %s and %s' % (tuple(x.shape), tuple(g.shape)))
+    b, c, f, n_freq = dims_of(x.shape, fmt)
+    n_filt = dims_of(g.shape, fmt)[3]
+    if tuple(dims_of(g.shape, fmt)[:3]) != (b, c, f) or n_freq < 1 or n_filt < 1 or c < 1:
+        raise ValueError('filterbank_wgrad: an input of shape %s and a cotangent of shape %s do not belong together'
+                         % (tuple(x.shape), tuple(g.shape)))
+    args = (_wgrad_rows(b, c, f, fmt), n_freq, n_filt, c, layout(fmt))
+    ws_bytes = int(lib().kpr_filterbank_wgrad_workspace_bytes(*args))
+    if ws_bytes < 0:
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    ws = workspace(ws_bytes, x.device)
+    gw = torch.empty((n_freq, n_filt), dtype=torch.float32, device=x.device)
+    _call("kpr_filterbank_wgrad_f32", x.device, ptr(x), ptr(g), b, c, f, n_freq, n_filt, layout(fmt), ptr(ws), ws_bytes, ptr(gw))
+    return gw

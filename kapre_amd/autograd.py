@@ -18,6 +18,8 @@ inside ``model.fit`` / ``tf.GradientTape`` is differentiable (reference: time_fr
   table of the time-reversed impulse responses (which are constants: no gradient reaches them); ``AddNoise`` is not linear
   (its gain follows the item's energy): backward is its two kernels in their other modes, a dot product with the wrapped
   noise and ``gy + coef x``, from the saved input, draw table and stats rows;
+* ``TrainableFilterbank`` learns its matrix: the input gradient is the GEMM with the transposed matrix, the weight gradient
+  ``x^T g`` a kernel of its own on the matrix units (``csrc/kpr_fb_wgrad_kernels.h``);
 * ``Magnitude`` / ``Phase`` / ``MagnitudeToDecibel`` have elementwise backward kernels
   (``csrc/kpr_grad_kernels.h``) that follow TensorFlow's registered gradients, including the part of
   the decibel gradient that reaches an item's maximum through the dynamic-range floor;
@@ -510,7 +512,28 @@ def _functions():
             g = g.contiguous().to(torch.complex64)
             return (_ffi.cqt_adjoint(g, *ctx.args),) + (None,) * 7
 
-    _FN = dict(cqt=CqtFn, add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
+    class FilterbankFn(torch.autograd.Function):
+        """y = x . W over the frequency axis with a learned W (TrainableFilterbank): forward the plain GEMM on W's own device
+        memory; backward gx = g . W^T (the same GEMM; the transposed copy is made here, a copy and no arithmetic) and
+        gW = x^T g (k_fb_wgrad), each only where it is asked for."""
+
+        @staticmethod
+        def forward(ctx, x, w, data_format):
+            ctx.data_format = data_format
+            x, w = x.detach(), w.detach()
+            ctx.save_for_backward(x, w)
+            return _ffi.freq_matmul(x, data_format, w)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            x, w = ctx.saved_tensors
+            g = g.contiguous().to(torch.float32)
+            gx = _ffi.freq_matmul(g, ctx.data_format, w.t().contiguous()) if ctx.needs_input_grad[0] else None
+            gw = _ffi.filterbank_wgrad(x, g, ctx.data_format) if ctx.needs_input_grad[1] else None
+            return gx, gw, None
+
+    _FN = dict(filterbank=FilterbankFn, cqt=CqtFn, add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
                mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn,
                resample_direct=ResampleDirectFn)
@@ -598,6 +621,11 @@ def lfilter(x, data_format, plan):
 
 def convolve(x, data_format, plan, idx, first, n_out):
     return _functions()['convolve'].apply(x, data_format, plan, idx, first, n_out)
+
+
+def filterbank(x, w, data_format):
+    """x . w with the learned matrix ``w`` on the tape (gradients for both)"""
+    return _functions()['filterbank'].apply(x, w, data_format)
 
 
 def cqt(x, data_format, out_format, lengths, tables, hop, center, pad_end):

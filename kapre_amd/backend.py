@@ -1462,3 +1462,18 @@ def cqt(x, sample_rate, hop_length=512, fmin=32.70319566, n_bins=84, bins_per_oc
                                    output)
     return _cqt_run(x, _CQT_CONSTS, bank, lengths, int(hop_length), bool(center), bool(pad_end),
                     resolve_data_format(input_data_format), resolve_data_format(output_data_format), output, bool(differentiable))
+
+
+def filterbank_grad(x, g, data_format='default'):
+    """The gradient of a filterbank matrix (``TrainableFilterbank``'s backward pass as a function): with y = x . W along the
+    frequency axis and ``g`` the cotangent of y, gW[f][m] = sum over batch, channels and frames of x[..., f] g[..., m].
+    ``x`` (b, t, n_freq, ch) and ``g`` (b, t, n_filt, ch) for 'channels_last', (b, ch, t, n_freq) and (b, ch, t, n_filt) for
+    'channels_first' -> float32 (n_freq, n_filt) on the device.  float32 only (``TypeError`` for float64); one launch of
+    k_fb_wgrad on the matrix units, two where the rows are cut into slabs (kpr_filterbank_wgrad_f32); the same inputs give the
+    same bits; |gW - exact| <= gamma_K sum |x||g|."""
+    import torch
+    validate_data_format_str(data_format)
+    if _ffi.is_f64(x) or _ffi.is_f64(g):
+        raise TypeError('filterbank_grad has a float32 kernel only; got a float64 input (cast it to float32)')
+    as_dev = lambda v: _ffi.as_device(v.detach() if isinstance(v, torch.Tensor) else v, torch.float32)
+    return _ffi.filterbank_wgrad(as_dev(x), as_dev(g), resolve_data_format(data_format))

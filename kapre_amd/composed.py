@@ -19,6 +19,7 @@ from .time_frequency import (
     Phase,
     MagnitudeToDecibel,
     ApplyFilterbank,
+    TrainableFilterbank,
     TimeStretch,
     HPSS,
     CQT,
@@ -29,13 +30,14 @@ from .backend import _CH_FIRST_STR, _CH_LAST_STR, _CH_DEFAULT_STR
 
 
 
-def _spectrogram_chain(name, input_shape, stft_args, filterbank=None, decibel=None):
+def _spectrogram_chain(name, input_shape, stft_args, filterbank=None, decibel=None, trainable_fb=False):
     """Build ``Sequential([STFT, Magnitude, (ApplyFilterbank), (MagnitudeToDecibel)])``.
 
     ``stft_args``: keyword arguments of ``STFT`` (both data formats are validated here first, as every
     reference helper does before constructing anything).  ``filterbank``: ``None`` or ``(type,
     filterbank_kwargs)`` -- the layer takes the STFT's *output* data format (composed.py:250-252,
-    :374-376).  ``decibel``: ``None`` or ``(ref_value, amin, dynamic_range)``."""
+    :374-376); ``trainable_fb``: a ``TrainableFilterbank`` in its place.  ``decibel``: ``None`` or ``(ref_value, amin,
+    dynamic_range)``."""
     for key in ('input_data_format', 'output_data_format'):
         backend.validate_data_format_str(stft_args[key])
     if input_shape is not None:
@@ -45,8 +47,8 @@ def _spectrogram_chain(name, input_shape, stft_args, filterbank=None, decibel=No
     chain.add(Magnitude())
     if filterbank is not None:
         fb_type, fb_kwargs = filterbank
-        chain.add(ApplyFilterbank(type=fb_type, filterbank_kwargs=fb_kwargs,
-                                  data_format=stft_args['output_data_format']))
+        chain.add((TrainableFilterbank if trainable_fb else ApplyFilterbank)(
+            type=fb_type, filterbank_kwargs=fb_kwargs, data_format=stft_args['output_data_format']))
     if decibel is not None:
         ref_value, amin, dynamic_range = decibel
         chain.add(MagnitudeToDecibel(ref_value=ref_value, amin=amin, dynamic_range=dynamic_range))
@@ -105,10 +107,13 @@ def get_melspectrogram_layer(
     input_data_format='default',
     output_data_format='default',
     name='melspectrogram',
+    trainable_fb=False,
 ):
     """``Sequential([STFT, Magnitude, ApplyFilterbank('mel'), (MagnitudeToDecibel)])``
     (reference: composed.py:138-261).  The filterbank is applied to the magnitude (power 1) and
-    its layer uses ``output_data_format`` (composed.py:250-252)."""
+    its layer uses ``output_data_format`` (composed.py:250-252).  ``trainable_fb=True`` (this package's own): a
+    ``TrainableFilterbank`` initialised with the mel bank in place of ``ApplyFilterbank`` -- the matrix is a parameter of the
+    returned model (``parameters()``), and the chain runs unfused behind the magnitude."""
     mel = dict(sample_rate=sample_rate, n_freq=n_fft // 2 + 1, n_mels=n_mels, f_min=mel_f_min,
                f_max=mel_f_max, htk=mel_htk, norm=mel_norm)
     return _spectrogram_chain(
@@ -116,7 +121,7 @@ def get_melspectrogram_layer(
         _stft_args(n_fft, win_length, hop_length, window_name, pad_begin, pad_end,
                    input_data_format, output_data_format),
         filterbank=('mel', mel),
-        decibel=(db_ref_value, db_amin, db_dynamic_range) if return_decibel else None)
+        decibel=(db_ref_value, db_amin, db_dynamic_range) if return_decibel else None, trainable_fb=trainable_fb)
 
 
 def get_log_frequency_spectrogram_layer(
@@ -139,9 +144,11 @@ def get_log_frequency_spectrogram_layer(
     input_data_format='default',
     output_data_format='default',
     name='log_frequency_spectrogram',
+    trainable_fb=False,
 ):
     """``Sequential([STFT, Magnitude, ApplyFilterbank('log'), (MagnitudeToDecibel)])``
-    (reference: composed.py:264-385)."""
+    (reference: composed.py:264-385).  ``trainable_fb=True``: a ``TrainableFilterbank`` in place of ``ApplyFilterbank``, as in
+    ``get_melspectrogram_layer``."""
     log = dict(sample_rate=sample_rate, n_freq=n_fft // 2 + 1, n_bins=log_n_bins,
                bins_per_octave=log_bins_per_octave, f_min=log_f_min, spread=log_spread)
     return _spectrogram_chain(
@@ -149,7 +156,7 @@ def get_log_frequency_spectrogram_layer(
         _stft_args(n_fft, win_length, hop_length, window_name, pad_begin, pad_end,
                    input_data_format, output_data_format),
         filterbank=('log', log),
-        decibel=(db_ref_value, db_amin, db_dynamic_range) if return_decibel else None)
+        decibel=(db_ref_value, db_amin, db_dynamic_range) if return_decibel else None, trainable_fb=trainable_fb)
 
 
 def get_perfectly_reconstructing_stft_istft(

@@ -63,9 +63,11 @@
 //                             range, the reduction split over the waves and added in a fixed order, complex or magnitude epilogue
 //   kpr_cqt_adj_kernels.h     its adjoint (the backward pass of CQT): the same product along the hop -- rows are hop blocks, columns the
 //                             offsets inside a hop, a table of fragments per hop --, the accumulators of an item owned by one wave
+//   kpr_fb_wgrad_kernels.h    the weight gradient of a filterbank (TrainableFilterbank): gW = x^T g over the rows on the matrix units --
+//                             f-tiles x row slabs, chunks of rows double-buffered in LDS, the slabs added in order by a second launch
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_resample.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h, kpr_host_cqt_adj.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h, kpr_host_cqt_adj.h, kpr_host_fb_wgrad.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -122,6 +124,7 @@
 #include "kpr_yin_kernels.h"
 #include "kpr_cqt_kernels.h"
 #include "kpr_cqt_adj_kernels.h"
+#include "kpr_fb_wgrad_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -137,6 +140,7 @@
 #include "kpr_host_yin.h"
 #include "kpr_host_cqt.h"
 #include "kpr_host_cqt_adj.h"
+#include "kpr_host_fb_wgrad.h"
 
 // ==========================================================================================
 // C ABI
@@ -195,7 +199,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536, 65536};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536, 65536, 1 << 30};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -720,6 +724,24 @@ int kpr_cqt_adjoint_f32(const void* g, int64_t batch, int channels, int64_t time
     if (int e = api_enter()) return e;
     return run_cqt_adjoint(g, batch, channels, time, layout, lengths, n_bins, table, table_floats, hop, center, pad_end, g_layout, gx,
                            stream);
+}
+int kpr_filterbank_wgrad_plan(int64_t rows, int n_freq, int n_filt, int channels, int layout, int* out) {
+    if (!out) return fail(KPR_E_BADARG, "out must not be NULL");
+    FbWgradPlan p;
+    if (int e = fb_wgrad_plan(rows, n_freq, n_filt, channels, layout, &p)) return e;
+    out[0] = kWgTF;
+    out[1] = (int)p.S;
+    out[2] = (int)p.n_slabs;
+    out[3] = p.passes;
+    return 0;
+}
+int64_t kpr_filterbank_wgrad_workspace_bytes(int64_t rows, int n_freq, int n_filt, int channels, int layout) {
+    return fb_wgrad_workspace_bytes(rows, n_freq, n_filt, channels, layout);
+}
+int kpr_filterbank_wgrad_f32(const float* x, const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int n_filt,
+                             int layout, void* workspace, int64_t workspace_bytes, float* gw, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_fb_wgrad(x, g, batch, channels, frames, n_freq, n_filt, layout, workspace, workspace_bytes, gw, stream);
 }
 
 }  // extern "C"

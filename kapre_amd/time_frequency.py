@@ -32,6 +32,7 @@ __all__ = [
     'Phase',
     'MagnitudeToDecibel',
     'ApplyFilterbank',
+    'TrainableFilterbank',
     'Delta',
     'ConcatenateFrequencyMap',
     'PCEN',
@@ -533,6 +534,120 @@ class ApplyFilterbank(Layer):
                 'data_format': self.data_format_original,
             }
         )
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class TrainableFilterbank(Layer):
+    """A learned (n_freq, n_filterbanks) filterbank along the frequency axis: ``ApplyFilterbank`` whose matrix is a parameter
+    (Kapre's original ``Melspectrogram(trainable_fb=True)``; the learnable front ends that start from a mel bank).
+
+    ``type`` ('mel' / 'log') and ``filterbank_kwargs`` initialise the matrix from ``backend.filterbank_mel`` /
+    ``backend.filterbank_log`` as ``ApplyFilterbank`` does; ``filterbank``, an explicit (n_freq, n_filterbanks) array, takes
+    precedence (``type`` may then be ``None``).  (b, t, n_freq, ch) -> (b, t, n_filterbanks, ch) for ``channels_last``,
+    (b, ch, t, n_freq) -> (b, ch, t, n_filterbanks) for ``channels_first``; float32 (a float64 layer raises
+    ``NotImplementedError``).
+
+    ``build(input_shape)``, ``parameters()`` or the first call creates one float32 ``torch.nn.Parameter`` (n_freq, n_filterbanks),
+    moved to the input's device by the first call there; ``parameters()`` hands it to a torch optimiser (``weights``,
+    ``count_params()`` too).  Forward: the plain GEMM (kpr_apply_filterbank_f32) on the parameter's own device memory -- no
+    packed copy, no row ranges, nothing cached, so an optimiser step is seen by the next call; this class is not an
+    ``ApplyFilterbank`` and ``Sequential`` never takes it into the fused mel launch.  Backward: gx = g . W^T, the same GEMM
+    with a transposed copy made on the spot, and gW = x^T g, one launch of ``k_fb_wgrad`` on the matrix units
+    (kpr_filterbank_wgrad_f32, ``backend.filterbank_grad``), each only where it is needed; the output has a
+    ``grad_fn`` also for an input that carries none.  With the Keras keyword ``trainable=False`` the parameter exists but does
+    not require grad.  ``constrain_()`` clamps the matrix to >= 0 after an optimiser step.  ``get_config()`` carries the current
+    (learned) matrix, so a saved model reloads with it."""
+
+    def __init__(self, type=None, filterbank_kwargs=None, data_format='default', filterbank=None, **kwargs):
+        super(TrainableFilterbank, self).__init__(**kwargs)
+        backend.validate_data_format_str(data_format)
+        if isinstance(data_format, dict):
+            data_format = data_format['config']
+        self.type = type
+        self.filterbank_kwargs = filterbank_kwargs
+        if filterbank is not None:
+            init = np.array(filterbank, dtype=np.float32)
+        elif type == 'log':
+            init = np.array(backend.filterbank_log(**filterbank_kwargs), dtype=np.float32)
+        elif type == 'mel':
+            init = np.array(backend.filterbank_mel(**filterbank_kwargs), dtype=np.float32)
+        else:
+            raise ValueError("TrainableFilterbank: type must be 'mel' or 'log' where no filterbank is given, got %r" % (type,))
+        if init.ndim != 2 or 0 in init.shape:
+            raise ValueError('TrainableFilterbank: the filterbank must be a non-empty (n_freq, n_filterbanks) matrix, got shape %s'
+                             % (init.shape,))
+        self._init = init
+        self._weight = None                                   # the torch.nn.Parameter, made by build() / the first call
+        self.data_format_original = data_format
+        self.data_format = backend.resolve_data_format(data_format)
+        self.freq_axis = 3 if self.data_format == _CH_FIRST_STR else 2
+
+    @property
+    def filterbank(self):
+        """the current (learned) matrix as a float32 numpy array (a copy)"""
+        if self._weight is None:
+            return self._init.copy()
+        return self._weight.detach().cpu().numpy().copy()
+
+    def build(self, input_shape=None, device=None):
+        """Create the parameter on ``device`` (default: the CPU; the first call moves it to its input's device)."""
+        if self._weight is None:
+            import torch
+
+            self._weight = torch.nn.Parameter(torch.from_numpy(self._init.copy()).to(device or 'cpu'),
+                                              requires_grad=bool(self.trainable))
+
+    def parameters(self):
+        self.build()
+        return [self._weight]
+
+    @property
+    def weights(self):
+        return [self._weight] if self._weight is not None else []
+
+    def count_params(self) -> int:
+        return int(self._init.size)
+
+    def constrain_(self):
+        """Clamp the learned matrix in place to >= 0 (a filterbank of magnitudes).  For use after an optimiser step."""
+        import torch
+
+        self.build()
+        with torch.no_grad():
+            self._weight.clamp_(min=0.0)
+        return self
+
+    def compute_output_shape(self, input_shape):
+        """the frequency axis (3 for channels_first, 2 for channels_last) becomes the number of filters"""
+        shape = list(input_shape)
+        shape[self.freq_axis] = int(self._init.shape[1])
+        return tuple(shape)
+
+    def call(self, x):
+        if self._f64:
+            raise NotImplementedError('TrainableFilterbank has float32 kernels only; build the layer with dtype float32')
+        import torch
+
+        if len(x.shape) != 4:
+            raise ValueError('TrainableFilterbank expects a rank-4 input, got shape %s' % (tuple(x.shape),))
+        k = _ffi.dims_of(x.shape, self.data_format)[3]
+        if k != self._init.shape[0]:
+            raise ValueError('frequency axis has %d bins but the filterbank expects %d' % (k, self._init.shape[0]))
+        x, recorded = autograd.to_device(x, 'float32')
+        self.build(device=x.device)
+        w = self._weight
+        if w.device != x.device:
+            w.data = w.data.to(x.device)                      # (the Parameter an optimiser holds stays the same object)
+        w.requires_grad_(bool(self.trainable))
+        if recorded or (w.requires_grad and torch.is_grad_enabled()):
+            return autograd.filterbank(x, w, self.data_format)
+        return _ffi.freq_matmul(x, self.data_format, w.detach())
+
+    def get_config(self):
+        config = super(TrainableFilterbank, self).get_config()
+        config.update({'type': self.type, 'filterbank_kwargs': self.filterbank_kwargs, 'data_format': self.data_format_original,
+                       'filterbank': self.filterbank.tolist()})
         return config
 
 
