@@ -170,6 +170,8 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *   "fb_wgrad_rows" 0 = automatic (default) | n = kpr_filterbank_wgrad_f32 cuts the rows into slabs of at most n rows, rounded up to the
  *                  chunk (kpr_filterbank_wgrad_plan; tests: the slab seam and the reduce launch at small shapes; within the error
  *                  bound of each other, not bit-identical)
+ *   "mdct_run"     0 = automatic (default) | n = a wave of kpr_mdct_f32 / kpr_imdct_f32 owns at most n consecutive frames / output
+ *                  blocks of a series (kpr_mdct_plan; tests: run seams at small shapes; the results are bit-identical)
  *   "verbose"      1 = print launch plans to stderr
  * Unknown name or out-of-range value: KPR_E_BADARG. */
 int kpr_set_option(const char* name, int value);
@@ -951,6 +953,35 @@ int kpr_filterbank_wgrad_plan(int64_t rows, int n_freq, int n_filt, int channels
 int64_t kpr_filterbank_wgrad_workspace_bytes(int64_t rows, int n_freq, int n_filt, int channels, int layout);
 int kpr_filterbank_wgrad_f32(const float* x, const float* g, int64_t batch, int channels, int64_t frames, int n_freq, int n_filt,
                              int layout, void* workspace, int64_t workspace_bytes, float* gw, kpr_stream_t stream);
+
+/* ---- MDCT / inverse MDCT: the lapped cosine transform of a waveform, kapre_amd.MDCT / InverseMDCT (tf.signal.mdct / inverse_mdct) ----
+ * Frame length N (512, 1024, 2048 or 4096; anything else: KPR_E_UNSUPPORTED), M = N / 2, hop M, window w[0 .. N-1] (device, float32).
+ * Frame t starts at sample t M - (M if pad_begin else 0); samples outside the signal are zeros.  Per series (batch item, channel):
+ *   kpr_mdct_f32   X[t, k] = s  sum_{n < N} w[n] x[start_t + n] cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)),          k = 0 .. M-1
+ *   kpr_imdct_f32  y_t[n]  = s' w[n] sum_{k < M} X[t, k] cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)), overlap-added at hop M
+ * norm 0: s = 2, s' = 1 / M (tf.signal: the fold, then scipy's unnormalised DCT-IV); norm 1 ('ortho'): s = s' = sqrt(2 / M).
+ * adjoint 1 swaps s and s': kpr_imdct_f32(adjoint = 1) is the transpose of kpr_mdct_f32(adjoint = 0) and the other way round (the
+ * backward passes).  With a Princen-Bradley window (w^2[n] + w^2[n + M] = 1) the inverse of the forward returns x on every sample
+ * that two frames cover.
+ * Frames of kpr_mdct_f32: kpr_frame_count(time + (M if pad_begin else 0), N, M, pad_end).  kpr_imdct_f32 writes out_len samples per
+ * series: sample i is position i + (M if pad_begin else 0) of the overlap-added signal of (n_frames + 1) M samples; what no frame
+ * covers is +0.0 (n_frames == 0: all of it; X may then be NULL).
+ * x / out of kpr_imdct_f32: (batch, time, channels) [LAST] or (batch, channels, time) [FIRST]; the coefficients: (batch, frames, M,
+ * channels) [LAST] or (batch, channels, frames, M) [FIRST].  float32, 4-byte aligned; NULL, misaligned or overlapping pointers, bad
+ * sizes, layouts or flags: KPR_E_BADARG; 2^31 samples or coefficients per series: KPR_E_UNSUPPORTED.  batch or channels == 0, no
+ * frame (forward) or out_len == 0 (inverse): returns 0, launches nothing.
+ * One launch each (k_mdct / k_imdct: fold, pre-twiddle, one N/4-point complex FFT, post-twiddle; the twiddle tables are computed on
+ * the host in float64 and cached per (N, scale)); no atomics, nothing allocated after the first call of a size: the same inputs give
+ * the same bits, and a frame's bits do not depend on its place in the launch.  Capturable after a first call.
+ * Error: |X - exact| <= K 2^-24 s sum_n |w[n] x[n]| per frame, and K 2^-24 s' |w[n]| sum_k |X[t, k]| summed over the two frames of an
+ * output sample, K = 28.5, 29.5, 37, 38 for N = 512 ... 4096.
+ * kpr_mdct_plan (host only): out[0] = the frames (inverse: output blocks of M samples) a wave owns as a run under the current
+ * "mdct_run", out[1] = the lanes that own one frame. */
+int kpr_mdct_plan(int frame_length, int* out);
+int kpr_mdct_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, int frame_length, const float* window, int norm,
+                 int adjoint, int pad_begin, int pad_end, int out_layout, float* out, kpr_stream_t stream);
+int kpr_imdct_f32(const float* X, int64_t batch, int channels, int64_t n_frames, int layout, int frame_length, const float* window,
+                  int norm, int adjoint, int pad_begin, int64_t out_len, int out_layout, float* out, kpr_stream_t stream);
 
 /* LogmelToMFCC.call (tf.signal.mfccs_from_log_mel_spectrograms, signal.py:418-436) has no entry
  * point of its own: it is kpr_apply_filterbank_f32 with the (n_mels, n_mfccs) DCT-II matrix

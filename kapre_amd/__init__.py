@@ -28,6 +28,8 @@ from .time_frequency import (
     TimeStretch,
     HPSS,
     CQT,
+    MDCT,
+    InverseMDCT,
 )
 
 from . import signal
@@ -103,6 +105,8 @@ __all__ = [
     'TimeStretch',
     'HPSS',
     'CQT',
+    'MDCT',
+    'InverseMDCT',
     'Frame',
     'Energy',
     'MuLawEncoding',

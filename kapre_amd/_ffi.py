@@ -269,6 +269,14 @@ EXPORTS = {
     "kpr_filterbank_wgrad_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    # MDCT / InverseMDCT (kapre_amd/time_frequency.py)
+    "kpr_mdct_plan": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "kpr_mdct_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "kpr_imdct_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 PAD_MODES = {"constant": 0, "symmetric": 1, "reflect": 2}
@@ -1415,3 +1423,48 @@ def filterbank_wgrad(x, g, fmt):
     gw = torch.empty((n_freq, n_filt), dtype=torch.float32, device=x.device)
     _call("kpr_filterbank_wgrad_f32", x.device, ptr(x), ptr(g), b, c, f, n_freq, n_filt, layout(fmt), ptr(ws), ws_bytes, ptr(gw))
     return gw
+
+
+# MDCT / InverseMDCT (kapre_amd/time_frequency.py)
+def mdct_plan(frame_length: int):
+    """(run, lanes): the consecutive frames (inverse: output blocks) of a series that one wave of kpr_mdct_f32 / kpr_imdct_f32
+    owns under the current ``mdct_run``, and the lanes that own one frame (host only).  ``ValueError`` for a frame length
+    other than 512, 1024, 2048 or 4096."""
+    out = (ctypes.c_int * 2)()
+    rc = lib().kpr_mdct_plan(int(frame_length), out)
+    if rc in (E_BADARG, E_UNSUPPORTED):
+        raise ValueError('kapre_amd: ' + lib().kpr_last_error().decode("utf-8", "replace"))
+    check(rc, "kpr_mdct_plan")
+    return tuple(out)
+
+
+def mdct_frames(t: int, frame_length: int, pad_begin: bool, pad_end: bool) -> int:
+    m = int(frame_length) // 2
+    return _frame_count(int(t) + (m if pad_begin else 0), int(frame_length), m, pad_end)
+
+
+def mdct(x, fmt, out_fmt, frame_length, window, ortho, pad_begin, pad_end, adjoint=False):
+    """The MDCT of the float32 waveform ``x`` under the device ``window`` of ``frame_length`` floats: float32
+    (b, frames, M, ch) / (b, ch, frames, M) as ``out_fmt`` says.  ``adjoint``: with the inverse's scale (the transpose of
+    ``imdct``).  One launch."""
+    import torch
+    b, c, t = dims_of(x.shape, fmt)
+    frames = mdct_frames(t, frame_length, pad_begin, pad_end)
+    out = torch.empty(shape_of(out_fmt, b, c, frames, int(frame_length) // 2), dtype=torch.float32, device=x.device)
+    _call("kpr_mdct_f32", x.device, ptr(x), b, c, t, layout(fmt), int(frame_length), ptr(window), int(bool(ortho)),
+          int(bool(adjoint)), int(bool(pad_begin)), int(bool(pad_end)), layout(out_fmt), ptr(out))
+    return out
+
+
+def imdct(X, fmt, out_fmt, window, ortho, pad_begin, length=None, adjoint=False):
+    """The inverse MDCT of the float32 coefficients ``X`` (layout ``fmt``, frame length twice the coefficient count): the
+    overlap-added waveform of ``length`` samples (default (frames + 1) M, less M with ``pad_begin``) in the layout
+    ``out_fmt``.  ``adjoint``: with the forward's scale (the transpose of ``mdct``).  One launch; every sample is written."""
+    import torch
+    b, c, frames, m = dims_of(X.shape, fmt)
+    if length is None:
+        length = (frames + 1) * m - (m if pad_begin else 0)
+    out = torch.empty(shape_of(out_fmt, b, c, int(length)), dtype=torch.float32, device=X.device)
+    _call("kpr_imdct_f32", X.device, ptr(X), b, c, frames, layout(fmt), 2 * int(m), ptr(window), int(bool(ortho)),
+          int(bool(adjoint)), int(bool(pad_begin)), int(length), layout(out_fmt), ptr(out))
+    return out

@@ -533,7 +533,40 @@ def _functions():
             gw = _ffi.filterbank_wgrad(x, g, ctx.data_format) if ctx.needs_input_grad[1] else None
             return gx, gw, None
 
-    _FN = dict(filterbank=FilterbankFn, cqt=CqtFn, add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
+    class MdctFn(torch.autograd.Function):
+        """X = MDCT(x) or y = InverseMDCT(X): linear maps, each the other's transpose up to the scale -- backward is the
+        other launcher with ``adjoint`` (one launch, no third kernel)."""
+
+        @staticmethod
+        def forward(ctx, x, inverse, fmt, out_fmt, frame_length, window, ortho, pad_begin, pad_end, length):
+            ctx.args = (inverse, fmt, out_fmt, frame_length, window, ortho, pad_begin)
+            ctx.in_shape = tuple(x.shape)
+            if inverse:
+                return _ffi.imdct(x.detach(), fmt, out_fmt, window, ortho, pad_begin, length)
+            return _ffi.mdct(x.detach(), fmt, out_fmt, frame_length, window, ortho, pad_begin, pad_end)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            inverse, fmt, out_fmt, frame_length, window, ortho, pad_begin = ctx.args
+            g = g.contiguous().to(torch.float32)
+            if not inverse:
+                gx = _ffi.imdct(g, out_fmt, fmt, window, ortho, pad_begin, _ffi.dims_of(ctx.in_shape, fmt)[2], adjoint=True)
+            else:
+                # the frames of the cotangent read as a waveform of the default length (frames + 1) M [- M]: what lies past it
+                # reached no frame, what is missing of it was zeros
+                frames, m = _ffi.dims_of(ctx.in_shape, fmt)[2:]
+                full, t_axis = (frames + 1) * m - (m if pad_begin else 0), 1 if _ffi.is_channels_last(out_fmt) else 2
+                have = g.shape[t_axis]
+                if have > full:
+                    g = g.narrow(t_axis, 0, full).contiguous()
+                elif have < full:
+                    pad = [0, 0] * (g.dim() - 1 - t_axis) + [0, full - have]
+                    g = torch.nn.functional.pad(g, pad).contiguous()
+                gx = _ffi.mdct(g, out_fmt, fmt, 2 * m, window, ortho, pad_begin, False, adjoint=True)
+            return (gx,) + (None,) * 9
+
+    _FN = dict(mdct=MdctFn, filterbank=FilterbankFn, cqt=CqtFn, add_noise=AddNoiseFn, convolve=ConvolveFn, stft=STFTFn, istft=ISTFTFn, c2r=CplxToRealFn, matrix=MatrixFn, db=DbFn, chain=ChainFn,
                frame=FrameFn, delta=DeltaFn, spec_augment=SpecAugmentFn, channel_gather=ChannelGatherFn,
                mu_law_decode=MuLawDecodeFn, freq_map=FreqMapFn, pcen=PcenFn, cmvn=CmvnFn, resample=ResampleFn, lfilter=LFilterFn,
                resample_direct=ResampleDirectFn)
@@ -635,3 +668,11 @@ def cqt(x, data_format, out_format, lengths, tables, hop, center, pad_end):
 def add_noise(x, data_format, bank, lengths, table):
     """(y, stats) of _ffi.add_noise with y on the tape"""
     return _functions()['add_noise'].apply(x, data_format, bank, lengths, table)
+
+
+def mdct(x, data_format, out_format, frame_length, window, ortho, pad_begin, pad_end):
+    return _functions()['mdct'].apply(x, False, data_format, out_format, frame_length, window, ortho, pad_begin, pad_end, None)
+
+
+def imdct(x, data_format, out_format, window, ortho, pad_begin, length):
+    return _functions()['mdct'].apply(x, True, data_format, out_format, None, window, ortho, pad_begin, False, length)

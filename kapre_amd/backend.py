@@ -100,6 +100,12 @@ def vorbis_window(window_length: int, dtype=np.float32) -> np.ndarray:
     return np.sin(np.pi / 2.0 * np.sin(np.pi / window_length * arg) ** 2).astype(dtype)
 
 
+def sine_window(window_length: int, dtype=np.float32) -> np.ndarray:
+    """sin(pi (n + 1/2) / N): the MDCT window of MP3 / AAC; w^2[n] + w^2[n + N/2] = 1 (Princen-Bradley)."""
+    window_length = int(window_length)
+    return np.sin(np.pi / window_length * (np.arange(window_length, dtype=np.float64) + 0.5)).astype(dtype)
+
+
 _AVAILABLE_WINDOWS = {
     'hamming_window': hamming_window,
     'hann_window': hann_window,
@@ -1477,3 +1483,98 @@ def filterbank_grad(x, g, data_format='default'):
         raise TypeError('filterbank_grad has a float32 kernel only; got a float64 input (cast it to float32)')
     as_dev = lambda v: _ffi.as_device(v.detach() if isinstance(v, torch.Tensor) else v, torch.float32)
     return _ffi.filterbank_wgrad(as_dev(x), as_dev(g), resolve_data_format(data_format))
+
+
+# --------------------------------------------------------------------------------------
+# MDCT / inverse MDCT
+# --------------------------------------------------------------------------------------
+MDCT_FRAME_LENGTHS = (512, 1024, 2048, 4096)
+_MDCT_CONSTS = _ffi.DeviceConstants(max_entries=32)
+
+
+def mdct_parameters(frame_length, window, norm):
+    """(frame_length, window key, ortho) of an MDCT, validated.  ``window``: None (the Vorbis window, ``tf.signal``'s default),
+    'sine_window' or a name ``get_window_fn`` knows, a callable length -> values, or the ``frame_length`` values themselves
+    (the key then holds them as a tuple).  ``norm``: None (forward scale 2, inverse 1 / M) or 'ortho' (both sqrt(2 / M)).
+    ``ValueError`` for another frame length than 512, 1024, 2048, 4096, another norm, or values of the wrong length."""
+    if isinstance(frame_length, bool) or not isinstance(frame_length, (int, np.integer)) or int(frame_length) not in MDCT_FRAME_LENGTHS:
+        raise ValueError('MDCT: frame_length must be one of %s, got %r' % (MDCT_FRAME_LENGTHS, frame_length))
+    if norm not in (None, 'ortho'):
+        raise ValueError("MDCT: norm must be None or 'ortho', got %r" % (norm,))
+    if window is None or isinstance(window, str) or callable(window):
+        mdct_window_fn(window)
+        key = window
+    else:
+        key = tuple(float(v) for v in np.asarray(window, np.float64).reshape(-1))
+        if len(key) != int(frame_length):
+            raise ValueError('MDCT: a window of %d values does not fit frame_length = %d' % (len(key), frame_length))
+    return int(frame_length), key, norm == 'ortho'
+
+
+def mdct_window_fn(window):
+    if window is None:
+        return vorbis_window
+    if callable(window):
+        return window
+    return sine_window if window == 'sine_window' else get_window_fn(window)
+
+
+def _mdct_window(consts, key, frame_length, device):
+    make = (lambda: np.asarray(key, np.float32)) if isinstance(key, tuple) else \
+        (lambda: window_values(mdct_window_fn(key), frame_length, np.float32))
+    return consts.get(('mdct_window', key if not callable(key) else id(key), frame_length), device, make)
+
+
+def _mdct_run(x, consts, params, pad_begin, pad_end, fmt, out_fmt):
+    """``x`` (rank 3) through kpr_mdct_f32; on the tape where it requires grad (backward: kpr_imdct_f32, adjoint)"""
+    from . import autograd
+    frame_length, key, ortho = params
+    x, recorded = autograd.intake(x, 3, 'float32', 'MDCT expects a rank-3 waveform batch, got shape %s', TypeError,
+                                  'MDCT has a float32 kernel only; got a float64 input (cast it to float32)')
+    w = _mdct_window(consts, key, frame_length, x.device)
+    if recorded:
+        return autograd.mdct(x, fmt, out_fmt, frame_length, w, ortho, pad_begin, pad_end)
+    return _ffi.mdct(x, fmt, out_fmt, frame_length, w, ortho, pad_begin, pad_end)
+
+
+def _imdct_run(X, consts, window, norm, pad_begin, length, fmt, out_fmt):
+    """``X`` (rank 4) through kpr_imdct_f32; on the tape where it requires grad (backward: kpr_mdct_f32, adjoint)"""
+    from . import autograd
+    X, recorded = autograd.intake(X, 4, 'float32', 'InverseMDCT expects rank-4 MDCT coefficients, got shape %s', TypeError,
+                                  'InverseMDCT has a float32 kernel only; got a float64 input (cast it to float32)')
+    frame_length, key, ortho = mdct_parameters(2 * int(_ffi.dims_of(X.shape, fmt)[3]), window, norm)
+    if length is not None and (isinstance(length, bool) or int(length) < 0):
+        raise ValueError('InverseMDCT: length must be a non-negative integer or None, got %r' % (length,))
+    w = _mdct_window(consts, key, frame_length, X.device)
+    if recorded:
+        return autograd.imdct(X, fmt, out_fmt, w, ortho, pad_begin, length)
+    return _ffi.imdct(X, fmt, out_fmt, w, ortho, pad_begin, length)
+
+
+def mdct(x, frame_length, window=None, norm=None, pad_begin=False, pad_end=False, data_format='default',
+         output_data_format=None):
+    """The modified discrete cosine transform of a waveform batch on the GPU (``tf.signal.mdct``; ``kapre_amd.MDCT`` as a
+    function).  Frames of ``frame_length`` = N samples at hop M = N / 2, frame t starting at sample t M (t M - M with
+    ``pad_begin``), zeros outside the signal:  X[t, k] = s sum_n w[n] x[start_t + n] cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)),
+    s = 2 (``norm=None``) or sqrt(2 / M) ('ortho').  (b, time, ch) / (b, ch, time) float32 -> float32 (b, frames, M, ch) /
+    (b, ch, frames, M); frames as ``STFT``'s with n_fft = N and hop M.  One launch (kpr_mdct_f32: fold, one N/4-point complex FFT
+    between two twiddles); differentiable (backward: one launch of kpr_imdct_f32).  ``window``: see ``mdct_parameters``."""
+    validate_data_format_str(data_format)
+    out_fmt = data_format if output_data_format is None else output_data_format
+    validate_data_format_str(out_fmt)
+    return _mdct_run(x, _MDCT_CONSTS, mdct_parameters(frame_length, window, norm), bool(pad_begin), bool(pad_end),
+                     resolve_data_format(data_format), resolve_data_format(out_fmt))
+
+
+def inverse_mdct(X, window=None, norm=None, pad_begin=False, length=None, data_format='default', output_data_format=None):
+    """The inverse of ``mdct`` (``tf.signal.inverse_mdct``; ``kapre_amd.InverseMDCT`` as a function): frame t becomes
+    y_t[n] = s' w[n] sum_k X[t, k] cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)), s' = 1 / M (``norm=None``) or sqrt(2 / M)
+    ('ortho'), and the frames are overlap-added at hop M.  With a window whose squares at n and n + M add up to 1 (Vorbis, sine,
+    Kaiser-Bessel-derived) this returns the waveform on every sample that two frames cover.  (b, frames, M, ch) /
+    (b, ch, frames, M) float32 -> (b, length, ch) / (b, ch, length); ``length`` defaults to (frames + 1) M, less the first M
+    with ``pad_begin``; a longer one is filled with zeros.  One launch (kpr_imdct_f32), differentiable."""
+    validate_data_format_str(data_format)
+    out_fmt = data_format if output_data_format is None else output_data_format
+    validate_data_format_str(out_fmt)
+    return _imdct_run(X, _MDCT_CONSTS, window, norm, bool(pad_begin), length, resolve_data_format(data_format),
+                      resolve_data_format(out_fmt))

@@ -65,9 +65,12 @@
 //                             offsets inside a hop, a table of fragments per hop --, the accumulators of an item owned by one wave
 //   kpr_fb_wgrad_kernels.h    the weight gradient of a filterbank (TrainableFilterbank): gW = x^T g over the rows on the matrix units --
 //                             f-tiles x row slabs, chunks of rows double-buffered in LDS, the slabs added in order by a second launch
+//   kpr_mdct_kernels.h        the MDCT of a waveform and its inverse (time_frequency.MDCT / InverseMDCT): fold, twiddle, one N/4-point complex
+//                             FFT of kpr_fft.h, twiddle; a wave owns a run of frames (or output blocks) of one series, the shared halves
+//                             of neighbouring frames and the overlap-add pass through wave-private LDS rows; each is the other's adjoint
 // The host code (table caches, launch plans, routes, argument validation, the bodies of the entry points) follows the kernels: kpr_host.h
 // (shared by every family), then kpr_host_fft.h, kpr_host_stft.h, kpr_host_istft.h, kpr_host_mel.h, kpr_host_ops.h, kpr_host_resample.h, kpr_host_griffin_lim.h,
-// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h, kpr_host_cqt_adj.h, kpr_host_fb_wgrad.h next to their kernel headers.  No header calls an entry point.
+// kpr_host_lfilter.h, kpr_host_convolve.h, kpr_host_mix.h, kpr_host_yin.h, kpr_host_cqt.h, kpr_host_cqt_adj.h, kpr_host_fb_wgrad.h, kpr_host_mdct.h next to their kernel headers.  No header calls an entry point.
 // This file: the C ABI and nothing else -- the extern "C" entry points, grouped as in include/kapre_hip.h.  Each is at most api_enter(),
 // the unpacking its C signature needs, and one call into namespace kpr; only the kpr_debug_* functions launch anything here.
 //
@@ -125,6 +128,7 @@
 #include "kpr_cqt_kernels.h"
 #include "kpr_cqt_adj_kernels.h"
 #include "kpr_fb_wgrad_kernels.h"
+#include "kpr_mdct_kernels.h"
 
 #include "kpr_host.h"
 #include "kpr_host_fft.h"
@@ -141,6 +145,7 @@
 #include "kpr_host_cqt.h"
 #include "kpr_host_cqt_adj.h"
 #include "kpr_host_fb_wgrad.h"
+#include "kpr_host_mdct.h"
 
 // ==========================================================================================
 // C ABI
@@ -199,7 +204,7 @@ int kpr_debug_spin_timeout(kpr_stream_t stream) {
 int kpr_set_option(const char* name, int value) {
     const int id = option_id(name);
     if (id < 0) return fail(KPR_E_BADARG, "unknown option '%s'", name ? name : "(null)");
-    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536, 65536, 1 << 30};
+    static const int lo[OPT_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, hi[OPT_COUNT] = {8, 4, 1, 4096, 1, 3, 32, 1, 1, 1, 1, 2, 2, 1, 65536, 65536, 1 << 30, 65536};
     if (value < lo[id] || value > hi[id])
         return fail(KPR_E_BADARG, "option '%s': value %d outside [%d, %d]", name, value, lo[id], hi[id]);
     // kernels removed in round 5 (dominated on every shape of tools/sweep_dispatch.py): the 4-wave ring kernel k_mel_fused
@@ -742,6 +747,26 @@ int kpr_filterbank_wgrad_f32(const float* x, const float* g, int64_t batch, int 
                              int layout, void* workspace, int64_t workspace_bytes, float* gw, kpr_stream_t stream) {
     if (int e = api_enter()) return e;
     return run_fb_wgrad(x, g, batch, channels, frames, n_freq, n_filt, layout, workspace, workspace_bytes, gw, stream);
+}
+
+/* ---- MDCT / inverse MDCT (kpr_mdct_kernels.h) ---------------------------------------------------- */
+int kpr_mdct_plan(int frame_length, int* out) {
+    if (!out) return fail(KPR_E_BADARG, "out must not be NULL");
+    MdctPlan p;
+    if (int e = mdct_plan(frame_length, &p)) return e;
+    out[0] = p.R;
+    out[1] = p.L;
+    return 0;
+}
+int kpr_mdct_f32(const float* x, int64_t batch, int channels, int64_t time, int layout, int frame_length, const float* window, int norm,
+                 int adjoint, int pad_begin, int pad_end, int out_layout, float* out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_mdct_fwd(x, batch, channels, time, layout, frame_length, window, norm, adjoint, pad_begin, pad_end, out_layout, out, stream);
+}
+int kpr_imdct_f32(const float* X, int64_t batch, int channels, int64_t n_frames, int layout, int frame_length, const float* window,
+                  int norm, int adjoint, int pad_begin, int64_t out_len, int out_layout, float* out, kpr_stream_t stream) {
+    if (int e = api_enter()) return e;
+    return run_mdct_inv(X, batch, channels, n_frames, layout, frame_length, window, norm, adjoint, pad_begin, out_len, out_layout, out, stream);
 }
 
 }  // extern "C"

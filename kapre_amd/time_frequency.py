@@ -3,7 +3,7 @@
 Mirror of /root/reference/kapre/time_frequency.py for the hot path: ``STFT`` (:61-203),
 ``InverseSTFT`` (:207-333), ``Magnitude`` (:337-359), ``Phase`` (:363-411),
 ``MagnitudeToDecibel`` (:415-465), ``ApplyFilterbank`` (:469-559), ``Delta`` (:561-644),
-``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim``, ``TimeStretch``, ``HPSS`` and ``CQT`` are this package's own.  Constructor signatures,
+``ConcatenateFrequencyMap`` (:647-744); ``PCEN``, ``CMVN``, ``GriffinLim``, ``TimeStretch``, ``HPSS``, ``CQT``, ``MDCT`` and ``InverseMDCT`` are this package's own.  Constructor signatures,
 defaults, ``get_config`` keys and raised exception types are the reference's; ``call`` runs the
 hand-written gfx950 kernels of libkapre_hip.so through ``kapre_amd._ffi`` (ctypes).  Inputs may be
 numpy arrays or torch tensors; outputs are torch tensors on the GPU (complex64 / float32).
@@ -41,6 +41,8 @@ __all__ = [
     'TimeStretch',
     'HPSS',
     'CQT',
+    'MDCT',
+    'InverseMDCT',
 ]
 
 
@@ -1287,6 +1289,101 @@ class CQT(Layer):
                        'window_name': self.window_name, 'norm': self.norm, 'scale': self.scale, 'center': self.center,
                        'pad_end': self.pad_end, 'output': self.output, 'input_data_format': self.input_data_format_original,
                        'output_data_format': self.output_data_format_original, 'differentiable': self.differentiable})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class MDCT(Layer):
+    """Modified discrete cosine transform of the waveform (``tf.signal.mdct``; ``backend.mdct``): the critically sampled lapped
+    transform of audio codecs.  Frames of ``frame_length`` = N samples (512, 1024, 2048 or 4096) at hop M = N / 2; frame t starts
+    at sample t M, or t M - M with ``pad_begin``; samples outside the signal are zeros; frames as ``STFT``'s with n_fft = N and
+    hop M (``pad_end`` as there).
+
+        X[t, k] = s sum_{n < N} w[n] x[start_t + n] cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)),    k = 0 .. M-1
+
+    s = 2 (``norm=None``, tf.signal's convention) or sqrt(2 / M) (``norm='ortho'``).  ``window_name``: None (the Vorbis window,
+    as in tf.signal), 'sine_window', or a name ``STFT`` accepts.  (batch, time, ch) / (batch, ch, time) float32 -> float32
+    (batch, frames, M, ch) for ``output_data_format`` 'channels_last', (batch, ch, frames, M) for 'channels_first'.  One launch of
+    ``k_mdct`` (kpr_mdct_f32): a fold, one N/4-point complex FFT between two twiddles; the same inputs give the same bits.  An
+    input that requires grad gets its gradient through one launch of ``k_imdct``.  float32 only (float64: ``TypeError``)."""
+
+    def __init__(self, frame_length=2048, window_name=None, norm=None, pad_begin=False, pad_end=False,
+                 input_data_format='default', output_data_format='default', **kwargs):
+        super(MDCT, self).__init__(**kwargs)
+        for data_format in (input_data_format, output_data_format):
+            backend.validate_data_format_str(data_format)
+        self._params = backend.mdct_parameters(frame_length, window_name, norm)
+        self.frame_length, self.window_name, self.norm = int(frame_length), window_name, norm
+        self.pad_begin, self.pad_end = bool(pad_begin), bool(pad_end)
+        self.input_data_format_original = input_data_format
+        self.output_data_format_original = output_data_format
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self._consts = _ffi.DeviceConstants()
+
+    def compute_output_shape(self, input_shape):
+        """(b, t, ch) / (b, ch, t) -> (b, frames, M, ch) / (b, ch, frames, M)"""
+        b, c, t = _ffi.dims_of(input_shape, self.input_data_format)
+        frames = None if t is None else _ffi.mdct_frames(t, self.frame_length, self.pad_begin, self.pad_end)
+        return _ffi.shape_of(self.output_data_format, b, c, frames, self.frame_length // 2)
+
+    def call(self, x):
+        return backend._mdct_run(x, self._consts, self._params, self.pad_begin, self.pad_end, self.input_data_format,
+                                 self.output_data_format)
+
+    def get_config(self):
+        config = super(MDCT, self).get_config()
+        config.update({'frame_length': self.frame_length, 'window_name': self.window_name, 'norm': self.norm,
+                       'pad_begin': self.pad_begin, 'pad_end': self.pad_end,
+                       'input_data_format': self.input_data_format_original,
+                       'output_data_format': self.output_data_format_original})
+        return config
+
+
+@register_keras_serializable(package='Kapre')
+class InverseMDCT(Layer):
+    """The inverse of ``MDCT`` (``tf.signal.inverse_mdct``; ``backend.inverse_mdct``): y_t[n] = s' w[n] sum_k X[t, k]
+    cos((2 pi / N)(n + 1/2 + M/2)(k + 1/2)) with N = 2 M from the input's last coefficient axis, s' = 1 / M (``norm=None``) or
+    sqrt(2 / M) ('ortho'), overlap-added at hop M.  With the same window and norm as the forward layer (Vorbis, sine or
+    Kaiser-Bessel-derived window) ``InverseMDCT(MDCT(x))`` is x on every sample that two frames cover: all of x with
+    ``pad_begin`` and ``pad_end`` on the forward layer and ``pad_begin`` here.  (batch, frames, M, ch) / (batch, ch, frames, M)
+    float32 -> (batch, length, ch) / (batch, ch, length); ``length`` defaults to (frames + 1) M, less the first M with
+    ``pad_begin``, a longer one is filled with zeros.  One launch of ``k_imdct`` (kpr_imdct_f32), no atomics, the same inputs
+    give the same bits; an input that requires grad gets its gradient through one launch of ``k_mdct``.  float32 only."""
+
+    def __init__(self, window_name=None, norm=None, pad_begin=False, length=None, input_data_format='default',
+                 output_data_format='default', **kwargs):
+        super(InverseMDCT, self).__init__(**kwargs)
+        for data_format in (input_data_format, output_data_format):
+            backend.validate_data_format_str(data_format)
+        backend.mdct_parameters(2048, window_name, norm)
+        if length is not None and (isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0):
+            raise ValueError('InverseMDCT: length must be a non-negative integer or None, got %r' % (length,))
+        self.window_name, self.norm, self.pad_begin = window_name, norm, bool(pad_begin)
+        self.length = None if length is None else int(length)
+        self.input_data_format_original = input_data_format
+        self.output_data_format_original = output_data_format
+        self.input_data_format = backend.resolve_data_format(input_data_format)
+        self.output_data_format = backend.resolve_data_format(output_data_format)
+        self._consts = _ffi.DeviceConstants()
+
+    def compute_output_shape(self, input_shape):
+        """(b, frames, M, ch) / (b, ch, frames, M) -> (b, length, ch) / (b, ch, length)"""
+        b, c, frames, m = _ffi.dims_of(input_shape, self.input_data_format)
+        length = self.length
+        if length is None and frames is not None and m is not None:
+            length = (frames + 1) * m - (m if self.pad_begin else 0)
+        return _ffi.shape_of(self.output_data_format, b, c, length)
+
+    def call(self, x):
+        return backend._imdct_run(x, self._consts, self.window_name, self.norm, self.pad_begin, self.length,
+                                  self.input_data_format, self.output_data_format)
+
+    def get_config(self):
+        config = super(InverseMDCT, self).get_config()
+        config.update({'window_name': self.window_name, 'norm': self.norm, 'pad_begin': self.pad_begin, 'length': self.length,
+                       'input_data_format': self.input_data_format_original,
+                       'output_data_format': self.output_data_format_original})
         return config
 
 
