@@ -147,8 +147,9 @@ int kpr_debug_spin_timeout(kpr_stream_t stream);
  *                  two interleaved channels) | 1 = the MFMA kernels of rounds 2-5 for every bank (A/B runs, tests)
  *   "mel_pw_plain" 1 = (default) n_fft 2048 mel launches without decibels on contiguous input rows with a linear output (one
  *                  channel, or channels_first in and out) and a band plan of two rounds / one offset quad (the 128-filter mel bank
- *                  at 44.1 kHz) run k_mel_plain_pw, the plain-output instance of k_mel_pw | 0 = k_mel_pw for those too (A/B runs,
- *                  tests; bit-identical results)
+ *                  at 44.1 kHz) run k_mel_plain_pw, the plain-output instance of k_mel_pw -- or, without padding (no pad_begin, no frame past the
+ *                  end of its item) and with exactly 128 filters, its whole-frames instance k_mel_whole_pw | 2 = k_mel_plain_pw
+ *                  for those too | 0 = k_mel_pw for all of them (A/B runs, tests; bit-identical results)
  *   "cmvn_variant" 0 = automatic (default: kpr_cmvn_f32 / kpr_cmvn_bwd_f32 keep a series of up to resident_frames frames
  *                  (kpr_cmvn_plan) in registers -- one read, one write) | 1 = the streamed form, two sweeps, for every frame count
  *                  (A/B runs, tests; bit-identical results)

@@ -566,39 +566,49 @@ static int launch_mel_pw(const float* x, const Geom& g, const float* window, con
                        (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
     return launch_check("k_mel_pw", NC, W == 4 ? "w4" : W == 8 ? "w8" : "w16");
 }
+// what k_mel_whole_pw needs beyond the plain instance's conditions: every frame inside its item, every output row full
+static bool mel_frames_whole(const Geom& g, int M, int NR) {
+    return g.pad_left == 0 && g.F >= 1 && (long long)(g.F - 1) * g.hop + g.n_fft <= g.T && M == 64 * NR;
+}
 // the plain-output instance k_mel_plain_pw (kpr_mel_pw_kernels.h): n_fft 2048, no decibels, contiguous rows in, linear rows out,
 // a band plan of exactly (NR, CMQ) -- mel_route checks all of it (MelRoute::plain).  Same grid, LDS and ticket split as launch_mel_pw.
-template <int NC, int W, int NR, int CMQ>
+// WHOLE: its whole-frames instance k_mel_whole_pw -- on top of that no left padding, no frame past the end of its item and
+// M = 64 NR (MelRoute::whole; re-checked here, the kernel has no edge fetch and no store tests to fall back on).  Same launch,
+// same label: the two differ in the verbose line only.
+template <int NC, int W, int NR, int CMQ, bool WHOLE>
 static int launch_mel_pw_plain(const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
                                const PackInfo& pi, int M, float* out, hipStream_t st) {
     PwPlan pl{(int)pi.L, (int)pi.NR, (int)pi.CMQ, (int)pi.nlist, M, reinterpret_cast<const unsigned*>(blob) + pi.band_off,
               reinterpret_cast<const unsigned*>(blob), pi.band_off, 0, 0};
     if (pl.L * kPts != NC || pl.NR != NR || pl.CMQ != CMQ) return no_instance("k_mel_plain_pw");
+    if (WHOLE && !mel_frames_whole(g, M, NR)) return no_instance("k_mel_whole_pw");
+    constexpr auto kern = WHOLE ? &k_mel_whole_pw<NC, W, NR, CMQ> : &k_mel_plain_pw<NC, W, NR, CMQ>;
     const size_t lds = pw_lds_bytes(NC, W, NR, CMQ);
     static LdsOptIn lds_opt_in;
-    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(&k_mel_plain_pw<NC, W, NR, CMQ>))) return e;
+    if (int e = allow_big_lds(lds_opt_in, reinterpret_cast<const void*>(kern))) return e;
     int cus = 256;
     if (int e = device_cus(&cus)) return e;
     const long long tickets = g.total_frames;                                   // a ticket = one frame of one wave
     const int per_cu = std::max(1, std::min(16 / W, (int)(160 * 1024 / lds)));  // sixteen waves per CU (128 VGPRs)
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((tickets + W - 1) / W, (long long)per_cu * cus));
     if (opt(OPT_VERBOSE))
-        fprintf(stderr, "[kapre_hip] k_mel_pw<%d,%d,plain>: grid %u, lds %zu B, NR %d CMQ %d list %d, %lld tickets\n", NC, W, grid, lds,
-                pl.NR, pl.CMQ, pl.nlist, tickets);
+        fprintf(stderr, "[kapre_hip] k_mel_pw<%d,%d,%s>: grid %u, lds %zu B, NR %d CMQ %d list %d, %lld tickets\n", NC, W,
+                WHOLE ? "whole" : "plain", grid, lds, pl.NR, pl.CMQ, pl.nlist, tickets);
     if (int e = status_word_ready()) return e;                  // (a stale band plan is reported there)
-    hipLaunchKernelGGL((k_mel_plain_pw<NC, W, NR, CMQ>), dim3(grid), dim3(W * 64), lds, st, x, g, window, tw, pl, out,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(W * 64), lds, st, x, g, window, tw, pl, out,
                        (int)(tickets / grid), (int)(tickets % grid), g_debug_stamps);
     // the general kernel's label with ",plain" behind it: "k_mel_pw<1024,w16>,plain" (what matches the general label matches this one)
     if (int e = launch_check("k_mel_pw", NC, W == 4 ? "w4" : W == 8 ? "w8" : "w16")) return e;
     if (g_launches.size() < 200) g_launches += ",plain";
     return 0;
 }
+template <bool WHOLE>
 static int launch_mel_pw_plain_w(int w, const float* x, const Geom& g, const float* window, const float2* tw, const float* blob,
                                  const PackInfo& pi, int M, float* out, hipStream_t st) {
     switch (w) {
-        case 4:  return launch_mel_pw_plain<1024, 4, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
-        case 16: return launch_mel_pw_plain<1024, 16, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
-        default: return launch_mel_pw_plain<1024, 8, 2, 1>(x, g, window, tw, blob, pi, M, out, st);
+        case 4:  return launch_mel_pw_plain<1024, 4, 2, 1, WHOLE>(x, g, window, tw, blob, pi, M, out, st);
+        case 16: return launch_mel_pw_plain<1024, 16, 2, 1, WHOLE>(x, g, window, tw, blob, pi, M, out, st);
+        default: return launch_mel_pw_plain<1024, 8, 2, 1, WHOLE>(x, g, window, tw, blob, pi, M, out, st);
     }
 }
 constexpr int kPwPairWaves = 12;                                 // waves per workgroup of the PAIR form
@@ -814,6 +824,7 @@ struct MelRoute {
     int cfast;                 // Geom::cfast of the launch
     int w;                     // MEL_PW: waves per workgroup
     int plain;                 // MEL_PW: the plain-output instance k_mel_plain_pw (launch_mel_pw_plain)
+    int whole;                 //   and of that its whole-frames instance k_mel_whole_pw (mel_frames_whole)
     int cl_slots;              // MEL_PW_PAIR: mel_pw_pair_slots
     int rf64;                  // MEL_TS: the 64-frame-round instance (n_fft 512)
     int ws_form;               // MEL_WS, PROD_WS: mel_ws_form
@@ -855,6 +866,8 @@ static MelRoute mel_route(const kpr_stft_geom* s, const Geom& g, int M, bool pac
         // the plain-output instance ("mel_pw_plain" 0 = never: A/B runs, tests); `fits` keeps total_frames below 2^31
         r.plain = n_fft == 2048 && !db_on && (g.C == 1 || (!g.in_cl && !g.out_cl)) && pi.L == 64 && pi.NR == 2 && pi.CMQ == 1 &&
                   opt(OPT_MEL_PW_PLAIN) != 0;
+        // without padding and with 128 filters, its whole-frames instance ("mel_pw_plain" 2 = never: A/B runs, tests)
+        r.whole = r.plain && opt(OPT_MEL_PW_PLAIN) != 2 && mel_frames_whole(g, M, (int)pi.NR);
         if (pair_ok && (mv == 8 || (mv == 0 && pair_auto))) {
             Geom gk = g;
             gk.cfast = cfast;
@@ -994,7 +1007,8 @@ static int run_mel_f32(const float* x, const kpr_stft_geom* s, const float* wind
     auto run = [&]() -> int {
         switch (r.fam) {
             case MEL_PW:
-                if (r.plain) return launch_mel_pw_plain_w(r.w, x, g, window, tw, blob, pinfo, n_filt, out, st);
+                if (r.whole) return launch_mel_pw_plain_w<true>(r.w, x, g, window, tw, blob, pinfo, n_filt, out, st);
+                if (r.plain) return launch_mel_pw_plain_w<false>(r.w, x, g, window, tw, blob, pinfo, n_filt, out, st);
                 return with_pow2(s->n_fft / 2, [&](auto nc) {
                     return launch_mel_pw_w<nc>(r.w, x, g, window, tw, blob, pinfo, n_filt, dbd, stats, out, st);
                 });

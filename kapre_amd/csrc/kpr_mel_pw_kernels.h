@@ -962,4 +962,218 @@ __global__ __launch_bounds__(W * 64, 4) void k_mel_plain_pw(const float* __restr
 #undef PW_STAMP
 }
 
+// ---- k_mel_whole_pw: the plain kernel for launches whose frames are all whole and whose output rows are all full --------------------
+// k_mel_plain_pw still carries, in every frame and in its register budget, the frames a launch without padding cannot contain:
+// the zero-filling edge fetch (fetch_frame_z / frame_pos32) behind a per-ticket interior test, zeros for a wave without a ticket,
+// and the per-store tests `frame exists` / `filter < M` (profiles/mel_pw_whole.md has the listing counts).  The host
+// (mel_route, MelRoute::whole) guarantees on top of the plain instance's conditions:
+//   pad_left == 0 and (F - 1) hop + n_fft <= T: every frame lies inside its item, so every ticket takes the sixteen dwordx2
+//   requests from two scalar bases and nothing else;
+//   M == 64 NR: both rounds store all 64 lanes;
+//   tickets == total_frames, split exactly over the grid: ticket tk < n_wg IS a frame (no fvalid).
+// A wave whose draw finds no ticket requests nothing; its sample registers are set to zero, which nothing reads (see fetch_ticket).
+// With the registers the cold fetch arms held, the lane's 32 mel weights are loaded once per wave instead of once per frame.
+// Prologue, ticket draw, tail_prio, window, FFT, pairing, magnitudes, row layout and the band sums are k_mel_plain_pw's, with the
+// same floating-point operations in the same order: the two give the same bits (tests/test_mel_pw_whole.py).
+// (As there, the name keeps "k_mel_pw" out of the symbol.)
+template <int NC, int W, int NR, int CMQ>
+__global__ __launch_bounds__(W * 64, 4) void k_mel_whole_pw(const float* __restrict__ x, Geom g, const float* __restrict__ window,
+                                                            const float2* __restrict__ twtab, PwPlan pl, float* __restrict__ out,
+                                                            int run_q, int run_r, long long* __restrict__ dbg) {
+    constexpr int L = NC / kPts;
+    static_assert(L == 64, "one frame per wave and ticket");
+    constexpr int M = L * NR;                                             // full rows (the host checks pl.M == M)
+    constexpr int THREADS = W * 64;
+    constexpr int RWD = pw_row_words(NC);
+    typedef typename WsSwzFor<NC>::type WsSwz;
+    static_assert(IsWide<WsSwz>::value, "the n_fft 2048 transform");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef KPR_DEV_STAMPS    /* development: s_memtime stamps of the workgroup dbg[16 * 32] names (tools/stamps_pw.py) */
+    int dbi = 0;
+    const bool stamp_me = dbg && (long long)blockIdx.x == dbg[16 * 32];
+#define PW_STAMP() do { if (stamp_me && lane0 == 0 && dbi < 32) dbg[wave * 32 + dbi++] = (long long)__builtin_readcyclecounter(); } while (0)
+    const unsigned long long wg_r0 = __builtin_amdgcn_s_memrealtime(), wg_c0 = __builtin_readcyclecounter();
+#else
+#define PW_STAMP() do { (void)dbg; } while (0)
+#endif
+    PW_STAMP();
+    typedef const unsigned __attribute__((address_space(4)))* ConstU32;
+    unsigned long long hdra = (unsigned long long)pl.hdr;
+    asm volatile("" : "+s"(hdra));
+
+    float* rows = smem;                                                   // [W][RWD]
+    float* tab = smem + W * RWD;                                          // P | WN | T2
+    f2* winl = reinterpret_cast<f2*>(tab + pw_lds_table_words(L, NR, CMQ));
+    int* ctr = reinterpret_cast<int*>(winl + NC);                         // the workgroup's ticket counter
+
+    const int bx = (int)blockIdx.x;
+    const int t_wg0 = run_q * bx + min(bx, run_r);
+    const int n_wg = run_q + (bx < run_r ? 1 : 0);
+
+    // frame gf = (item bc, frame f) starts at element bc T + f hop, whole inside the item: two scalar bases, immediates
+    auto fetch_ticket = [&](int tk, int lane_, f2 (&dst)[kPts]) {         // tk = ticket of this workgroup, wave-uniform
+        if (tk < n_wg) {
+            const unsigned gf = (unsigned)(t_wg0 + tk);
+            const unsigned bc = magic_div(gf, g.mF, g.sF);
+            const int s0 = (int)(gf - bc * (unsigned)g.F) * g.hop;
+            typedef const char __attribute__((address_space(1)))* GlobalB;
+            typedef const float __attribute__((address_space(1)))* GlobalF;
+            unsigned long long b0 = (unsigned long long)(x + ((long long)bc * g.T + s0));
+            unsigned long long b1 = b0 + 8 * (kPts / 2) * L;
+            asm volatile("" : "+s"(b0), "+s"(b1));
+            const unsigned lo = 8u * (unsigned)(lane_ & (L - 1));
+#pragma unroll
+            for (int m = 0; m < kPts; ++m) {
+                const GlobalB p = (GlobalB)(m < kPts / 2 ? b0 : b1) + lo + 8 * L * (m % (kPts / 2));
+                dst[m] = f2{((GlobalF)p)[0], ((GlobalF)p)[1]};           // (one dwordx2)
+            }
+        } else {
+            // (no ticket: nothing reads these, but left undefined hipcc spilled 36 registers of the prefetch: profiles/mel_pw_whole.md)
+#pragma unroll
+            for (int m = 0; m < kPts; ++m) asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(dst[m].x), "=v"(dst[m].y));
+        }
+    };
+    f2 nz[kPts];
+    int cur = wave;                                                       // the first ticket of every wave is static
+    fetch_ticket(cur, lane0, nz);
+    asm volatile("" : "+s"(hdra) :: "memory");                           // (HDR_LATE: behind the sample requests)
+    const unsigned l6 = ((ConstU32)hdra)[6], l7 = ((ConstU32)hdra)[7], l8 = ((ConstU32)hdra)[8], l9 = ((ConstU32)hdra)[9],
+                   l10 = ((ConstU32)hdra)[10];
+    PW_STAMP();
+    constexpr int WPT = (NC + THREADS - 1) / THREADS;
+    float wa[WPT], wb[WPT];
+#pragma unroll
+    for (int u = 0; u < WPT; ++u) {
+        const int n = 2 * min(tid + u * THREADS, NC - 1);
+        wa[u] = window[min(n, g.win - 1)];
+        wb[u] = window[min(n + 1, g.win - 1)];
+    }
+    static_assert(FftTw<NC, WsSwz>::kNumTw <= kPwTwRegs, "LDS staging area of the twiddle set");
+    f2* twl = reinterpret_cast<f2*>(ctr + 4);                             // [kNumTw][64]
+    if (wave == 0) {
+        FftTw<NC, WsSwz> t0;
+        t0.load(twtab, lane0);
+        t0.for_each_tw([&](f2& v, int i) { twl[i * 64 + lane0] = v; });
+    }
+    PW_STAMP();
+    // (compared BEFORE the first access through pl.sec; the instance's NR / CMQ size the LDS tables and M the stores)
+    if (l6 != pl.band_off || l7 != (unsigned)pl.L || l8 != (unsigned)pl.NR || l9 != (unsigned)pl.CMQ || l10 != (unsigned)pl.nlist ||
+        pl.L != L || pl.NR != NR || pl.CMQ != CMQ || pl.M != M) {
+        if (tid == 0) status_raise(kStStalePlan);
+        return;
+    }
+    {
+        const int nt = pw_lds_table_words(L, NR, CMQ);                   // multiple of 4
+        const uint4* src = reinterpret_cast<const uint4*>(pl.sec + kPwEmaskWords + 32 * L);
+        uint4* dst = reinterpret_cast<uint4*>(tab);
+        for (int i = tid; i < nt / 4; i += THREADS) dst[i] = src[i];
+    }
+#pragma unroll
+    for (int u = 0; u < WPT; ++u) {
+        const int i = tid + u * THREADS, n = 2 * i;
+        if (i < NC) winl[i] = f2{(n < g.win) ? 0.5f * wa[u] : 0.0f, (n + 1 < g.win) ? 0.5f * wb[u] : 0.0f};
+    }
+    if (lane0 < 4) rows[wave * RWD + pw_zero_word(NC) + lane0] = 0.0f;   // the zero words
+    if (tid == 0) *ctr = W;
+    PW_STAMP();
+    lds_barrier();
+    FftTw<NC, WsSwz> tw;
+    tw.for_each_tw([&](f2& v, int i) { v = twl[i * 64 + lane0]; });
+    tw.set_addresses(lane0);
+    PW_STAMP();
+
+    // The lane's 32 mel weights stay in registers ACROSS frames (without the edge fetch they fit: 120 VGPRs, no spill): requested
+    // once, in the wave's first frame, where the plain kernel requests them in every frame.  (Requested behind the barrier
+    // instead, launches of one or two frames per wave lose what the longer ones gain: profiles/mel_pw_whole.md section 5.)
+    f4 wq[8];
+    bool wq_here = false;
+    const bool tail_prio = n_wg < 8 * W;                                  // (k_mel_pw: the end of a short run)
+    if (tail_prio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll 1
+    while (cur < n_wg) {
+        int nxt = 0;
+        int lane_f = lane0;
+        asm volatile("" : "+v"(lane_f));
+        const int lane = lane_f, fl = lane & (L - 1);
+        float* row = rows + wave * RWD;
+        {
+            // ---- samples -> window -> rFFT -> |X| row -------------------------------------------------------------------
+            f2 z[kPts];
+#pragma unroll
+            for (int m = 0; m < kPts; ++m) z[m] = pmul(nz[m], winl[fl + L * m]);
+            tw.refresh();
+            cfft_forward_wide_planar(z, tw, row);
+            if (!wq_here) {                                               // wave-uniform: the first frame
+                pw_load_weights<NC>(pl.sec, fl, wq);
+                wq_here = true;
+            }
+            float mk[kPts / 2], mp[kPts / 2];
+            float mid = 0.0f;
+            rfft_pair<NC>(z, tw, fl, lane, [&](int k, f2 xk, int kp, f2 xp) {
+                const float a = __builtin_amdgcn_sqrtf(xk.x * xk.x + xk.y * xk.y);
+                if (kp >= 0) {
+                    const int m = (k - fl) / L;                           // compile-time after unrolling
+                    mk[m] = a;
+                    mp[m] = __builtin_amdgcn_sqrtf(xp.x * xp.x + xp.y * xp.y);
+                } else mid = a;                                           // k = NC / 2 (lane 0 only)
+            });
+            float* lo = row + fl;
+            float* hi = row + (NC - fl);
+            float* hi0 = hi + ((fl == 0) ? 4 : 0);
+            KPR_LDS_FENCE_W();
+#pragma unroll
+            for (int m = 0; m < kPts / 2; ++m) lo[L * m + 4 * ((L * m) >> 6)] = mk[m];
+#pragma unroll
+            for (int m = 0; m < kPts / 2; ++m) {
+                const int off = -L * m + 4 * ((L * (15 - m)) >> 6);
+                if ((L * (16 - m)) % 64 == 0) hi0[off] = mp[m]; else hi[off] = mp[m];
+            }
+            if (fl == 0) row[pw_mag_word(NC / 2)] = mid;
+        }
+        {   // the next ticket: drawn now, its samples requested now -- they land under this frame's sums and stores
+            unsigned drawn = 0;
+            int lane_p = lane0;
+            asm volatile("" : "+v"(lane_p) :: "memory");                 // nothing of the fetch is computed above here
+            if (lane_p == 0)                                              // one ds_inc_rtn_u32: old + 1 below the wrap value
+                drawn = __builtin_amdgcn_atomic_inc32(reinterpret_cast<unsigned*>(ctr), 0xffffffffu, __ATOMIC_RELAXED, "workgroup");
+            nxt =__builtin_amdgcn_readfirstlane((int)drawn);
+            fetch_ticket(nxt, lane_p, nz);
+            if (tail_prio && nxt >= n_wg) __builtin_amdgcn_s_setprio(0);  // (see tail_prio)
+        }
+        PW_STAMP();
+        // ---- banded mel sums of the row, stores: row gf of the (total_frames, M) output, all of it ---------------------------
+        {
+            const unsigned gf = (unsigned)(t_wg0 + cur);
+            typedef char __attribute__((address_space(1)))* GlobalWB;
+            typedef float __attribute__((address_space(1)))* GlobalWF;
+            unsigned long long ob = (unsigned long long)(out + (long long)gf * M);
+            asm volatile("" : "+s"(ob));                                  // (a scalar base: the rounds' offsets stay immediates)
+            const PwMasks em = pw_load_masks(pl.sec);
+            const unsigned rowb = (unsigned)(size_t)row;
+            KPR_LDS_FENCE_R();
+            const f4a* mq = reinterpret_cast<const f4a*>(row + 16 * fl + 4 * (fl >> 2));
+            const f4 mm[4] = {mq[0], mq[1], mq[2], mq[3]};
+            const float magn = row[pw_mag_word(NC)];                      // |X[Nyquist]| (one address: a broadcast)
+            const unsigned ptr = rowb + reinterpret_cast<const unsigned*>(tab)[fl];
+            KPR_LDS_FENCE_X();
+            const unsigned fo = 4u * (unsigned)fl;
+            pw_band_core_w<NC, false, true, 0, 4, false, NR, CMQ>(row, fl, em, [&](int j) { return wq[j]; }, tab, NR, CMQ, mm, magn, ptr,
+                                                                  [&](int r, float v) {
+                ((GlobalWF)((GlobalWB)ob + fo))[L * r] = v;
+            });
+        }
+        PW_STAMP();
+        cur = nxt;
+    }
+#ifdef KPR_DEV_STAMPS    /* every workgroup: start / end on the constant 100 MHz clock and on the shader clock (dbg[1024 + 4 bx ..]) */
+    if (dbg && tid == 0 && blockIdx.x < 4096) {
+        long long* e = dbg + 1024 + 4 * (long long)blockIdx.x;
+        e[0] = (long long)wg_r0; e[1] = (long long)__builtin_amdgcn_s_memrealtime();
+        e[2] = (long long)wg_c0; e[3] = (long long)__builtin_readcyclecounter();
+    }
+#endif
+#undef PW_STAMP
+}
+
 }  // namespace kpr
